@@ -100,12 +100,19 @@ def parse():
     ap.add_argument("--h2h-rank-chunks", type=int, default=20000, help="chunks of a rank's shard the --h2h-ranks leg runs on")
     ap.add_argument("--cli-chunks", type=int, default=10000, help="chunks of the CLI end-to-end measurement (0 = skip)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: per-base tracks and nuc candidates of a "
+                         "fixed, seeded sample of the chunks, < 64 MB) as DIR/<name>.npy in float64; non-finite results are written as 0 "
+                         "and coded in DIR/<name>_nonfinite.npy")
     ap.add_argument("--dist-backend", default="gloo", choices=["gloo", "nccl"],
                     help="barrier backend.  The path has no collective (chunks are independent), so the default control plane is gloo + a "
                          "device synchronise per rank; nccl additionally forms an RCCL group (probed, used only if every rank has it)")
     ap.add_argument("--share-device", action="store_true",
                     help="functional test of the N>1 path on a 1-GPU box: every rank uses GPU 0 (use with --dist-backend gloo)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def resolve_ranks(gpus, environ):
@@ -451,6 +458,75 @@ def bench_stages(tracks=()):
     return Stages(nuc_sd=10, occ=True, ins=(0, 2000), peaks=dict(min_signal=0, sep=25, boundary=60, order=12), tracks=tracks)
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_TRACKS = ("T_NUC_COV", "T_NFR_COV", "T_RAW", "T_BACKGROUND", "T_NORM", "T_SMOOTH", "T_OCC", "T_OCC_LOWER", "T_OCC_UPPER",
+               "T_OCC_COV", "T_INS")
+DUMP_SEED = 20240601                 # fixed: the same arguments give the same sample
+DUMP_TRACK_BYTES = 48 << 20          # per-base tracks of the sampled chunks; the candidates of those chunks come on top (< 64 MB in all)
+DUMP_INTEGER = ("chunk", "chunk_len", "ins", "peaks_chunk", "peaks_pos")   # integer-valued: always finite, no `_nonfinite` companion
+
+
+def dump_sample(subs):
+    """a fixed, seeded sample of this rank's chunks (indices into the concatenation of `subs`) whose per-base tracks fit the budget"""
+    lens = np.concatenate([np.asarray(s.chunk_len, dtype=np.int64) for s in subs])
+    per_bp = len(DUMP_TRACKS) * 8 + (len(DUMP_TRACKS) - 1) * 4      # float64 values + float32 `_nonfinite` codes (not for T_INS)
+    take, used = [], 0
+    for k in np.random.default_rng(DUMP_SEED).permutation(len(lens)):
+        if used + lens[k] * per_bp > DUMP_TRACK_BYTES:
+            break
+        take.append(k)
+        used += lens[k] * per_bp
+    return np.sort(np.array(take, dtype=np.int64))
+
+
+class OutputDump(object):
+    """collects what a step computed on the sampled chunks, one sub-batch at a time (`collect` has the signature of
+    ResidentShard.step's `consume`), and writes DIR/<name>.npy in float64: per-base tracks `<track>` (the sampled chunks
+    concatenated in chunk order), `chunk` / `chunk_len` (their indices in this rank's chunk list and their lengths) and the
+    candidates of the nuc call (`peaks_chunk`, `peaks_pos`, `peaks_lr`, `peaks_var`, `peaks_z`) on those chunks.
+    Every file holds finite numbers only: the path's NaN / inf results (LR where a term is zero, z = norm / sqrt(var) at var = 0)
+    are written as 0 in `<name>.npy`, and `<name>_nonfinite.npy` (float32, one code per entry: 0 finite, 1 NaN, 2 +inf, 3 -inf)
+    says which entries those are, so that a change between finite and non-finite still shows as a difference"""
+
+    def __init__(self, subs):
+        self.sample = dump_sample(subs)
+        self.first = np.cumsum([0] + [s.n_chunks for s in subs])
+        self.parts = {}
+
+    def collect(self, i, batch, n_cand):
+        from nucleoatac_amd import _lib as L
+        lo, hi = self.first[i], self.first[i + 1]
+        ks = self.sample[(self.sample >= lo) & (self.sample < hi)] - lo
+        if len(ks) == 0:
+            return
+        off = batch.packed.out_off
+        idx = np.concatenate([np.arange(off[k], off[k + 1]) for k in ks])
+        put = lambda name, v: self.parts.setdefault(name, []).append(np.asarray(v, dtype=np.float64))
+        put("chunk", ks + lo)
+        put("chunk_len", batch.packed.chunk_len[ks])
+        for t in DUMP_TRACKS:
+            put(t[2:].lower(), batch.track(getattr(L, t))[idx])
+        cc, cp, lr, var, z = batch.download_peaks(n_cand)
+        sel = np.isin(cc, ks)
+        for name, v in (("peaks_chunk", cc[sel].astype(np.int64) + lo), ("peaks_pos", cp[sel]), ("peaks_lr", lr[sel]),
+                        ("peaks_var", var[sel]), ("peaks_z", z[sel])):
+            put(name, v)
+
+    def write(self, out_dir):
+        os.makedirs(out_dir, exist_ok=True)
+        for name, parts in sorted(self.parts.items()):
+            v = np.concatenate(parts)
+            if name not in DUMP_INTEGER:
+                code = np.zeros(v.shape, dtype=np.float32)
+                code[np.isnan(v)] = 1
+                code[np.isposinf(v)] = 2
+                code[np.isneginf(v)] = 3
+                v = np.where(code == 0, v, 0.0)
+                np.save(os.path.join(out_dir, name + "_nonfinite.npy"), code)
+            assert np.isfinite(v).all(), name
+            np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 # ------------------------------------------------------------------------------------------------ host-to-host pipeline
 def placement(pci):
     """where this rank's host side sits relative to its GPU: the CPUs the process may run on, their NUMA node(s), the GPU's NUMA node
@@ -695,6 +771,14 @@ def main():
     prof = ctx.profile()
     ms_per_step = dt / a.steps * 1e3
     value = total_bp * a.steps / dt / 1e6
+    if a.dump_outputs and rank == 0:
+        dump = OutputDump(subs)
+        if recycle:     # the last step released its outputs sub-batch by sub-batch: one more (untimed) step hands them over
+            shard.step(stages, consume=dump.collect)
+        else:
+            for i, b in enumerate(batches):
+                dump.collect(i, b, shard.last_n[i])
+        dump.write(a.dump_outputs)
     # one more (untimed) step under the shader-clock sampler: the clock every kernel class really ran at (fp64-dense kernels pull
     # the chip below its 2.4 GHz; peaks quoted at 2.4 GHz are not reachable by them)
     clocks = None

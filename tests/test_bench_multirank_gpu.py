@@ -139,30 +139,40 @@ def test_ranks_that_share_a_gpu_are_refused_without_the_switch():
     assert "ranks share a GPU" in out.stderr and "--share-device" in out.stderr
 
 
-def test_eight_ranks_share_device_cfg4():
-    """the N = 8 shape the driver launches for the scaling run, with all eight ranks on GPU 0: configs[3] geometry sharded by
-    balanced_ranges into eight shards, control plane over gloo (RCCL cannot form a communicator on one device and the ranks
-    agree on that collectively), one JSON line with the eight per-rank timing rows; the sharded totals equal one rank's"""
+def test_four_ranks_share_device_cfg4():
+    """an N > 2 shape of the strong-scaling run with all four ranks on GPU 0 (four, so that the ranks and this process stay within six
+    processes with the GPU open): configs[3] geometry sharded by balanced_ranges into four shards, control plane over gloo (RCCL
+    cannot form a communicator on one device and the ranks agree on that collectively), one JSON line with the four per-rank timing
+    rows; the sharded totals equal one rank's"""
     common = ["--workload", "cfg4", "--chunks", "2400", "--sub-chunks", "200", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", "29538", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-device"] + common
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", "29538", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-device"] + common
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
     assert len(lines) == 1
-    d8 = json.loads(lines[0])
+    d4 = json.loads(lines[0])
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d1 = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][-1])
-    assert d8["n_gpus"] == 8 and d8["scaling"] == "strong" and d8["control_plane"] == "gloo"
-    c1, c8 = d1["config"], d8["config"]
-    assert c1["bp_total"] == c8["bp_total"] == 2400 * 10120 and c1["fragments_total"] == c8["fragments_total"]
-    assert c1["candidates_per_step"] == c8["candidates_per_step"]
-    rows = d8["per_rank"]
-    assert [r["rank"] for r in rows] == list(range(8)) and sum(r["bp"] for r in rows) == c8["bp_total"]
+    assert d4["n_gpus"] == 4 and d4["scaling"] == "strong" and d4["control_plane"] == "gloo"
+    c1, c4 = d1["config"], d4["config"]
+    assert c1["bp_total"] == c4["bp_total"] == 2400 * 10120 and c1["fragments_total"] == c4["fragments_total"]
+    assert c1["candidates_per_step"] == c4["candidates_per_step"]
+    rows = d4["per_rank"]
+    assert [r["rank"] for r in rows] == list(range(4)) and sum(r["bp"] for r in rows) == c4["bp_total"]
     assert all(r["ms_per_step"] > 0 and r["generate_s"] >= 0 for r in rows)
-    assert c8["shard_imbalance"]["bp_max_over_mean"] < 1.05 and len(c8["shard_imbalance"]["bp_per_rank"]) == 8
+    assert c4["shard_imbalance"]["bp_max_over_mean"] < 1.05 and len(c4["shard_imbalance"]["bp_per_rank"]) == 4
+    # the eight shards the N = 8 scaling run cuts from the same chunk list (bench.py make_workload's cfg4 split)
+    import numpy as np
+    from nucleoatac_amd.shard import balanced_ranges
+    from nucleoatac_amd.synth import fragment_counts
+    counts = fragment_counts(2400, 667, seed=2)
+    ranges = balanced_ranges(np.full(2400, 10120), np.concatenate(([0], np.cumsum(counts))), 8)
+    bp8 = np.array([(r1 - r0) * 10120 for r0, r1 in ranges], dtype=np.float64)
+    assert len(ranges) == 8 and bp8.sum() == c4["bp_total"] and bp8.max() / bp8.mean() < 1.05
+    assert sum(int(counts[r0:r1].sum()) for r0, r1 in ranges) == c4["fragments_total"]
 
 
 def test_cfg5_independent_samples_with_cov_sweep():
