@@ -43,7 +43,10 @@ enum {
     NATAC_OK = 0,
     NATAC_E_ARG = -1,   /* bad argument / inconsistent sizes */
     NATAC_E_HIP = -2,   /* HIP runtime error (no device, launch failure, ...) */
-    NATAC_E_STATE = -3, /* call order: constants not set, stage not run yet */
+    NATAC_E_STATE = -3, /* call order: constants not set, or an input the call reads holds nothing.  A per-base track holds
+                         * something once the stage that writes it has run (natac_run_nuc: NUC_COV .. SMOOTH; natac_run_occ: OCC ..
+                         * OCC_COV, OCC_PREFILL and the grids; natac_run_ins: INS) or natac_batch_set_track wrote it; each track
+                         * counts on its own, and natac_batch_release_outputs empties them all */
     NATAC_E_NOMEM = -4
 };
 
@@ -191,12 +194,15 @@ int natac_batch_download(natac_batch *b, int track, void *dst, size_t dst_bytes)
 /* copy one per-grid-point array to host (float64[total_grid]). */
 int natac_batch_download_grid(natac_batch *b, int which, double *dst, size_t dst_bytes);
 /* overwrite one float64 per-base track of the batch with host values (total_bp doubles, chunk order): lets any track -- an
- * externally computed one, or a test pattern -- go through the device-side writer (natac_batch_format_track) */
+ * externally computed one, or a test pattern -- go through the device-side writer (natac_batch_format_track).  Only `track`
+ * becomes readable: calls that read other tracks or the grids still need their stage (NATAC_E_STATE), and so do the candidate
+ * statistics of a batch with a bias track (natac_run_nuc forms exp(bias)).  Overwriting NUC_COV leaves the BACKGROUND
+ * natac_run_nuc computed as it was; natac_run_occ then takes OCC_COV from the fragments, not from host-written coverage. */
 int natac_batch_set_track(natac_batch *b, int track, const double *vals, size_t n);
 /* per-chunk status flags (int32[n_chunks]; 0 = ok, bit0 = occupancy likelihood undefined at some grid point
  * -- the reference would raise ValueError at Occupancy.py:118). */
 int natac_batch_status(natac_batch *b, int32_t *dst, size_t dst_bytes);
-/* raw device pointer of a per-base track (for zero-copy consumers); NULL if the stage has not run. */
+/* raw device pointer of a per-base track (for zero-copy consumers); NULL if the track holds nothing (NATAC_E_STATE above). */
 int natac_batch_track_ptr(natac_batch *b, int track, void **dptr);
 
 /* ---- drop-in replacements of the Cython functions (host buffers in / out, synchronous) --- */

@@ -112,6 +112,17 @@ struct natac_bam {
     natac_bamio::Bam *impl = nullptr;
 };
 
+// What each output of a batch holds and who wrote it: the stages and natac_batch_set_track write it, every reader asks need_track().
+// PENDING: formed on the first request from what the stage left (BACKGROUND from d_bnum / d_bcov, OCC_PREFILL from the grids).
+enum TrackState : unsigned char { TS_EMPTY = 0, TS_PENDING, TS_RUN /* a natac_run_* stage */, TS_HOST /* natac_batch_set_track */ };
+struct BatchOutputs {
+    TrackState track[NATAC_T_COUNT] = {};
+    bool grids = false;               // d_grid written by natac_run_occ
+    long long bg_gen = -1;            // model generation d_bnum / d_bcov were formed with (natac_run_nuc); -1: none
+    int nuc_w = -1, nuc_upper = -1;   // V-plot geometry natac_run_nuc ran with (the coverage tracks depend on it)
+    bool occ_cov_by_nuc = false;      // OCC_COV holds natac_run_nuc's nuc_cov + nfr_cov for that geometry
+};
+
 struct natac_batch {
     natac_ctx *ctx = nullptr;
     int nc = 0;
@@ -126,8 +137,6 @@ struct natac_batch {
     int *d_occ_nan = nullptr, n_tiles_os = 0, os_width = 0;
     int2 *d_tiles_os = nullptr, *d_tiles1k = nullptr;
     int n_tiles1k = 0;
-    bool prefill_valid = false;                   // OCC_PREFILL holds this run's values (written by the generic path or on demand)
-    bool bg_valid = false;                        // BACKGROUND holds this run's values (the FFT path leaves it to materialise_bg)
     int2 *d_tiles256 = nullptr, *d_tiles_bg = nullptr, *d_tiles_occ = nullptr, *d_ranges_occ = nullptr, *d_ranges256 = nullptr;
     long long *d_tile256_first = nullptr;   // [nc + 1] first 256-base tile of every chunk (the candidates' way into d_ranges256)
     int *d_order_occ = nullptr;      // natac_tile_heavy: {count, claims, list[HEAVY_CAP], flag bytes[n_tiles_occ]} of the occupancy tiles
@@ -149,7 +158,8 @@ struct natac_batch {
     int nd_upper = 0;
     double *d_track[NATAC_T_COUNT] = {nullptr};
     double *d_grid[3] = {nullptr, nullptr, nullptr};
-    bool nuc_done = false, occ_done = false, ins_done = false, cov_from_nuc = false, ebias_fresh = false;
+    BatchOutputs out;
+    bool ebias_fresh = false;
     // device-side candidate search
     double *d_jitter = nullptr, *d_pk_out = nullptr;
     long long *d_cap_off = nullptr, *d_pk_offs = nullptr;
@@ -159,7 +169,6 @@ struct natac_batch {
     long long n_jitter = 0, pk_cap = 0, pk_n = -1, slot_total = 0;
     int pk_order = -1;
     bool pk_has_stats = false;
-    int nuc_w = -1, nuc_upper = -1;   // V-plot geometry natac_run_nuc ran with (coverage tracks depend on it)
     double *d_bnum = nullptr, *d_bcov = nullptr;   // per-base sum B V / sum B of the background kernel (candidate statistics)
     unsigned char *d_fmt_out = nullptr;            // result of the last natac_batch_format_track (text or BGZF members)
     std::vector<std::pair<unsigned char *, hipEvent_t>> fmt_pending;   // results on their way to the host (natac_batch_format_fetch_begin)
@@ -169,12 +178,10 @@ struct natac_batch {
     std::vector<unsigned long long> fmt_member_pos;
     std::vector<std::string> fmt_names;
     long long fmt_text_bytes = 0;
-    long long nuc_gen = -1;                        // model generation natac_run_nuc ran with
 };
 
 static hipError_t sync_all(natac_ctx *c) { return hipStreamSynchronize(c->stream); }
 
-static int track_ready(natac_batch *b, int t);
 static int fmt_pending_wait(natac_batch *b);
 
 static void prof_begin(natac_ctx *c, int k, natac_ctx::Ev &ev, hipStream_t st = nullptr) {
@@ -1227,7 +1234,7 @@ int natac_batch_release_outputs(natac_batch *b) {
     dev_free(b->d_fmt_out); b->d_fmt_out = nullptr; b->fmt_bytes = -1;
     (void)fmt_pending_wait(b);
     b->pk_cap = 0; b->pk_n = -1; b->opk_cap = 0; b->opk_n = -1;
-    b->nuc_done = b->occ_done = b->ins_done = b->cov_from_nuc = b->prefill_valid = b->bg_valid = false;
+    b->out = BatchOutputs();
     // the per-chunk status words describe the outputs that were just dropped
     HIPCHK(hipMemsetAsync(b->d_status, 0, (size_t)b->nc * sizeof(int), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1308,7 +1315,6 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     hipLaunchKernelGGL((natac_frag_gather<GNBL>), dim3(b->n_tiles256), dim3(256 / GNBL), 0, c->stream, ct, b->d_tiles256, b->d_ranges256, vm,
                        b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_NFR_COV], b->d_track[NATAC_T_RAW],
                        cov_too ? b->d_track[NATAC_T_OCC_COV] : nullptr);
-    b->cov_from_nuc = cov_too;
     prof_end(c, ev);
     prof_begin(c, NATAC_K_BACKGROUND, ev);
     if ((rc = run_exp_bias(b, c->stream, false))) return rc;
@@ -1318,7 +1324,6 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
                            c->d_fft_k, b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_RAW], (double *)nullptr,
                            b->d_track[NATAC_T_NORM], b->d_bnum, b->d_bcov, (unsigned)b->n_tiles_bg, c->d_fft_mtab,
                            c->d_fft_swt, (c->R + 3) / 4);
-        b->bg_valid = false;
     } else if (fast) {
         switch (b->bgG) {
             case 7: launch_bg<7>(b, ct, vm); break;
@@ -1326,12 +1331,10 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
             case 13: launch_bg<13>(b, ct, vm); break;
             default: launch_bg<17>(b, ct, vm); break;
         }
-        b->bg_valid = true;
     } else {
         hipLaunchKernelGGL(natac_background_generic, dim3(b->n_tiles256), dim3(256), 0, c->stream, ct, b->d_tiles256, vm,
                            b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_RAW], b->d_track[NATAC_T_BACKGROUND],
                            b->d_track[NATAC_T_NORM], b->d_bnum, b->d_bcov);
-        b->bg_valid = true;
     }
     prof_end(c, ev);
     prof_begin(c, NATAC_K_SMOOTH_NUC, ev);
@@ -1349,10 +1352,12 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     }
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
-    b->nuc_done = true;
-    b->nuc_gen = c->model_gen;
-    b->nuc_w = c->vw;
-    b->nuc_upper = c->vupper;
+    for (int t : {NATAC_T_NUC_COV, NATAC_T_NFR_COV, NATAC_T_RAW, NATAC_T_NORM, NATAC_T_SMOOTH}) b->out.track[t] = TS_RUN;
+    b->out.track[NATAC_T_BACKGROUND] = use_fft ? TS_PENDING : TS_RUN;
+    b->out.bg_gen = c->model_gen;
+    b->out.nuc_w = c->vw;
+    b->out.nuc_upper = c->vupper;
+    b->out.occ_cov_by_nuc = cov_too;     // OCC_COV itself becomes readable through natac_run_occ only
     return NATAC_OK;
 }
 
@@ -1412,7 +1417,6 @@ static int ensure_block_weights(natac_ctx *c, int M, double sd, int NB) {
 
 // BACKGROUND after the FFT kernel: (bnum * nuc_cov) / bcov per base, the expression of the kernel's own epilogue (natac_fft_bg.hpp)
 static int materialise_bg(natac_batch *b) {
-    if (b->bg_valid) return NATAC_OK;
     natac_ctx *c = b->ctx;
     int rc = ensure_track(b, NATAC_T_BACKGROUND);
     if (rc) return rc;
@@ -1420,13 +1424,12 @@ static int materialise_bg(natac_batch *b) {
     hipLaunchKernelGGL(natac_bg_from_factors, dim3(blocks), dim3(256), 0, c->stream, b->d_bnum, b->d_track[NATAC_T_NUC_COV], b->d_bcov,
                        b->d_track[NATAC_T_BACKGROUND], b->total_bp);
     HIPCHK(hipGetLastError());
-    b->bg_valid = true;
+    b->out.track[NATAC_T_BACKGROUND] = TS_RUN;
     return NATAC_OK;
 }
 
 // OCC_PREFILL (smoothed_vals before call_peaks' NaN fill) is not part of the default pass: written on the first request
 static int materialise_prefill(natac_batch *b) {
-    if (b->prefill_valid) return NATAC_OK;
     natac_ctx *c = b->ctx;
     int rc = ensure_track(b, NATAC_T_OCC_PREFILL);
     if (rc) return rc;
@@ -1434,15 +1437,20 @@ static int materialise_prefill(natac_batch *b) {
     const OccModelDev om = make_occ(c);
     launch_occ_smooth_generic(b, ct, om, 2 * c->flank + 1, b->d_track[NATAC_T_OCC_PREFILL], nullptr, nullptr);
     HIPCHK(hipGetLastError());
-    b->prefill_valid = true;
+    b->out.track[NATAC_T_OCC_PREFILL] = TS_RUN;
     return NATAC_OK;
 }
 
-// tracks that are formed on the first request
-static int materialise_track(natac_batch *b, int track) {
-    if (track == NATAC_T_OCC_PREFILL && b->occ_done) return materialise_prefill(b);
-    if (track == NATAC_T_BACKGROUND && b->nuc_done) return materialise_bg(b);
-    return NATAC_OK;
+// Every read of an output track goes through here: NATAC_E_STATE (before any HIP call) if it holds nothing, formed if pending.
+static int need_track(natac_batch *b, int t) {
+    static const char *const names[NATAC_T_COUNT] = {"NUC_COV", "NFR_COV", "RAW", "BACKGROUND", "NORM", "SMOOTH", "OCC", "OCC_LOWER",
+                                                     "OCC_UPPER", "OCC_COV", "INS", "OCC_PREFILL"};
+    if (t < 0 || t >= NATAC_T_COUNT) return fail(NATAC_E_ARG, "bad track id %d", t);
+    if (b->out.track[t] == TS_EMPTY)
+        return fail(NATAC_E_STATE, "track NATAC_T_%s holds nothing: no stage has written it and natac_batch_set_track has not", names[t]);
+    if (b->out.track[t] != TS_PENDING) return NATAC_OK;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    return t == NATAC_T_BACKGROUND ? materialise_bg(b) : materialise_prefill(b);
 }
 
 // natac_run_occ, part 1: every allocation, table upload and host synchronisation of the stage (nothing is launched that
@@ -1492,7 +1500,6 @@ static int occ_prepare(natac_batch *b) {
         if (!b->d_grid[i] && (rc = dev_alloc(&b->d_grid[i], (size_t)b->total_grid))) return rc;
     for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV})
         if ((rc = ensure_track(b, t))) return rc;
-    b->prefill_valid = false;
     if (!b->d_ebias && b->d_bias && (rc = dev_alloc(&b->d_ebias, (size_t)b->nb))) return rc;
     const bool fast = c->occ_fast_ok && !c->occ_force_general;
     if (fast) {   // per-block sum buffers + tile table of natac_occ_gsum (geometry: step / flank of the model)
@@ -1558,7 +1565,6 @@ static int occ_launch(natac_batch *b) {
     natac_ctx *c = b->ctx;
     const int M = 2 * c->flank + 1;
     int rc;
-    b->prefill_valid = false;
     const ChunkTable ct = make_table(b);
     const OccModelDev om = make_occ(c);
     natac_ctx::Ev ev;
@@ -1635,17 +1641,19 @@ static int occ_launch(natac_batch *b) {
     } else {
         launch_occ_smooth_generic(b, ct, om, M, b->d_track[NATAC_T_OCC_PREFILL], b->d_track[NATAC_T_OCC_LOWER],
                                   b->d_track[NATAC_T_OCC_UPPER]);
-        b->prefill_valid = true;
     }
-    {
-        if (b->nuc_done && b->cov_from_nuc && c->flank == b->nuc_w && c->occ_upper == b->nuc_upper) {
+    {   // OCC_COV: natac_run_nuc's coverage when natac_run_nuc wrote it for this window and size range, else from the fragments
+        const bool same = c->flank == b->out.nuc_w && c->occ_upper == b->out.nuc_upper;
+        if (same && b->out.occ_cov_by_nuc) {
             // natac_frag_gather of natac_run_nuc already wrote OCC_COV = nuc_cov + nfr_cov for this geometry
-        } else if (b->nuc_done && c->flank == b->nuc_w && c->occ_upper == b->nuc_upper)
+        } else if (same && b->out.track[NATAC_T_NUC_COV] == TS_RUN && b->out.track[NATAC_T_NFR_COV] == TS_RUN) {
             hipLaunchKernelGGL(natac_add_tracks, dim3(4096), dim3(256), 0, c->stream, b->d_track[NATAC_T_NUC_COV],
                                b->d_track[NATAC_T_NFR_COV], b->d_track[NATAC_T_OCC_COV], b->total_bp);
-        else
+        } else {
             hipLaunchKernelGGL(natac_occ_cov, dim3(b->n_tiles256), dim3(256), 0, c->stream, ct, b->d_tiles256, c->occ_upper, c->flank,
                                b->d_track[NATAC_T_OCC_COV]);
+            b->out.occ_cov_by_nuc = false;
+        }
     }
     prof_end(c, ev);
     prof_begin(c, NATAC_K_OCC_FILL, ev, c->stream);
@@ -1657,7 +1665,9 @@ static int occ_launch(natac_batch *b) {
                            b->d_track[NATAC_T_OCC]);
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
-    b->occ_done = true;
+    for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV}) b->out.track[t] = TS_RUN;
+    b->out.track[NATAC_T_OCC_PREFILL] = blk ? TS_PENDING : TS_RUN;
+    b->out.grids = true;
     return NATAC_OK;
 }
 
@@ -1694,7 +1704,15 @@ static int ins_launch(natac_batch *b, int lower, int upper) {
     }
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
-    b->ins_done = true;
+    b->out.track[NATAC_T_INS] = TS_RUN;
+    return NATAC_OK;
+}
+
+// what launch_candidates reads of the batch: NUC_COV, NORM and, with a bias track, exp(bias) (formed by natac_run_nuc)
+static int need_candidate_inputs(natac_batch *b) {
+    int rc;
+    if ((rc = need_track(b, NATAC_T_NUC_COV)) || (rc = need_track(b, NATAC_T_NORM))) return rc;
+    if (b->d_bias && !b->d_ebias) return fail(NATAC_E_STATE, "natac_run_nuc must run before the candidate statistics (exp(bias))");
     return NATAC_OK;
 }
 
@@ -1702,7 +1720,8 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
                          double *var, double *z) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     natac_ctx *c = b->ctx;
-    if (!b->nuc_done) return fail(NATAC_E_STATE, "natac_run_nuc must run before natac_run_candidates");
+    int rc = need_candidate_inputs(b);
+    if (rc) return rc;
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !lr || !var || !z))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
     if (n_cand > 0x7fffffffLL) return fail(NATAC_E_ARG, "too many candidates");
@@ -1714,7 +1733,6 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
     }
     int *d_cc = nullptr, *d_cp = nullptr;
     double *d_out = nullptr;
-    int rc;
     if ((rc = dev_upload(c, &d_cc, cand_chunk, (size_t)n_cand))) return rc;
     if ((rc = dev_upload(c, &d_cp, cand_pos, (size_t)n_cand))) { dev_free(d_cc); return rc; }
     if ((rc = dev_alloc(&d_out, (size_t)3 * n_cand))) { dev_free(d_cc); dev_free(d_cp); return rc; }
@@ -1723,7 +1741,7 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
     natac_ctx::Ev ev;
     prof_begin(c, NATAC_K_CAND, ev);
     launch_candidates(c, ct, vm, d_cc, d_cp, n_cand, b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_NORM],
-                      b->nuc_gen == c->model_gen ? b->d_bnum : nullptr, b->nuc_gen == c->model_gen ? b->d_bcov : nullptr, d_out,
+                      b->out.bg_gen == c->model_gen ? b->d_bnum : nullptr, b->out.bg_gen == c->model_gen ? b->d_bcov : nullptr, d_out,
                       d_out + n_cand,
                       d_out + 2 * n_cand, b->ranges256_w == c->vw ? b->d_tile256_first : nullptr, b->ranges256_w == c->vw ? b->d_ranges256 : nullptr);
     prof_end(c, ev);
@@ -1742,13 +1760,13 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
                              double *var) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     natac_ctx *c = b->ctx;
-    if (!b->nuc_done) return fail(NATAC_E_STATE, "natac_run_nuc must run before natac_run_candidates_cov");
+    int rc = need_track(b, NATAC_T_NUC_COV);
+    if (rc) return rc;
     if (mode < 0 || mode > 2) return fail(NATAC_E_ARG, "mode must be 0 (closed form), 1 (literal) or 2 (closed form in fp32)");
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !var))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
     HIPCHK(hipSetDevice(c->device));
-    int rc = ensure_srow(c);
-    if (rc) return rc;
+    if ((rc = ensure_srow(c))) return rc;
     for (int64_t k = 0; k < n_cand; ++k) {
         const int ci = cand_chunk[k];
         if (ci < 0 || ci >= b->nc || cand_pos[k] < 0 || cand_pos[k] >= b->h_len[ci])
@@ -1925,7 +1943,7 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
         if (with_stats) {
             const VMatDev vm = make_vmat(c);
             launch_candidates(c, ct, vm, b->d_pk_chunk, b->d_pk_pos, total, b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_NORM],
-                              b->nuc_gen == c->model_gen ? b->d_bnum : nullptr, b->nuc_gen == c->model_gen ? b->d_bcov : nullptr,
+                              b->out.bg_gen == c->model_gen ? b->d_bnum : nullptr, b->out.bg_gen == c->model_gen ? b->d_bcov : nullptr,
                               b->d_pk_out, b->d_pk_out + b->pk_cap, b->d_pk_out + 2 * b->pk_cap,
                               b->ranges256_w == c->vw ? b->d_tile256_first : nullptr, b->ranges256_w == c->vw ? b->d_ranges256 : nullptr);
         }
@@ -1941,7 +1959,8 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
 int natac_run_peaks(natac_batch *b, double min_signal, int sep, int boundary, int order, const double *jitter, int64_t n_jitter,
                     int64_t *n_cand) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
-    if (!b->nuc_done) return fail(NATAC_E_STATE, "natac_run_nuc must run before natac_run_peaks");
+    int rc;
+    if ((rc = need_track(b, NATAC_T_SMOOTH)) || (rc = need_candidate_inputs(b))) return rc;
     return run_peaks_impl(b, b->d_track[NATAC_T_NORM], b->d_track[NATAC_T_SMOOTH], true, min_signal, sep, boundary, order, jitter,
                           n_jitter, n_cand);
 }
@@ -1950,21 +1969,20 @@ int natac_run_track_peaks(natac_batch *b, int track, double min_signal, int sep,
                           int64_t n_jitter, int64_t *n_peaks) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     if (track == NATAC_T_INS) return fail(NATAC_E_ARG, "peak search needs a float64 track");
-    int rc = track_ready(b, track);
+    int rc = need_track(b, track);
     if (rc) return rc;
-    HIPCHK(hipSetDevice(b->ctx->device));
-    if ((rc = materialise_track(b, track))) return rc;
     return run_peaks_impl(b, b->d_track[track], nullptr, false, min_signal, sep, boundary, order, jitter, n_jitter, n_peaks);
 }
 
 int natac_run_occ_peaks(natac_batch *b, double min_occ, int sep, const double *jitter, int64_t n_jitter, int64_t *n_peaks) {
     if (!b || !n_peaks) return fail(NATAC_E_ARG, "null argument");
-    if (!b->occ_done) return fail(NATAC_E_STATE, "natac_run_occ must run before natac_run_occ_peaks");
+    int rc;
+    for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV}) if ((rc = need_track(b, t))) return rc;
     natac_ctx *c = b->ctx;
     const int U = c->occ_upper;
     if (U > 1024) return fail(NATAC_E_ARG, "upper > 1024");
     // OccChunk.callPeaks: call_peaks(smoothed_vals, sep, min_signal = min_occ), boundary = sep / 2, order = 1 (Occupancy.py:227)
-    int rc = run_peaks_impl(b, b->d_track[NATAC_T_OCC], nullptr, false, min_occ, sep, sep / 2, 1, jitter, n_jitter, n_peaks);
+    rc = run_peaks_impl(b, b->d_track[NATAC_T_OCC], nullptr, false, min_occ, sep, sep / 2, 1, jitter, n_jitter, n_peaks);
     if (rc) return rc;
     const long long n = *n_peaks;
     if (n > b->opk_cap) {
@@ -2054,22 +2072,13 @@ int natac_download_peaks(natac_batch *b, int64_t n, int32_t *cand_chunk, int32_t
     return NATAC_OK;
 }
 
-static int track_ready(natac_batch *b, int t) {
-    if (t < 0 || t >= NATAC_T_COUNT) return fail(NATAC_E_ARG, "bad track id %d", t);
-    const bool nuc = (t <= NATAC_T_SMOOTH), occ = (t >= NATAC_T_OCC && t <= NATAC_T_OCC_COV) || t == NATAC_T_OCC_PREFILL;
-    if ((nuc && !b->nuc_done) || (occ && !b->occ_done) || (t == NATAC_T_INS && !b->ins_done))
-        return fail(NATAC_E_STATE, "track %d has not been computed yet", t);
-    return NATAC_OK;
-}
-
 int natac_batch_download(natac_batch *b, int track, void *dst, size_t dst_bytes) {
     if (!b || !dst) return fail(NATAC_E_ARG, "null argument");
-    int rc = track_ready(b, track);
+    int rc = need_track(b, track);
     if (rc) return rc;
     const size_t need = (size_t)b->total_bp * (track == NATAC_T_INS ? sizeof(int) : sizeof(double));
     if (dst_bytes != need) return fail(NATAC_E_ARG, "destination holds %zu bytes, track needs %zu", dst_bytes, need);
     HIPCHK(hipSetDevice(b->ctx->device));
-    if ((rc = materialise_track(b, track))) return rc;
     HIPCHK(hipMemcpyAsync(dst, b->d_track[track], need, hipMemcpyDeviceToHost, b->ctx->stream));
     HIPCHK(sync_all(b->ctx));
     prof_collect(b->ctx);
@@ -2079,7 +2088,7 @@ int natac_batch_download(natac_batch *b, int track, void *dst, size_t dst_bytes)
 int natac_batch_download_grid(natac_batch *b, int which, double *dst, size_t dst_bytes) {
     if (!b || !dst) return fail(NATAC_E_ARG, "null argument");
     if (which < 0 || which > 2) return fail(NATAC_E_ARG, "bad grid id");
-    if (!b->occ_done) return fail(NATAC_E_STATE, "natac_run_occ has not run");
+    if (!b->out.grids) return fail(NATAC_E_STATE, "natac_run_occ has not run");
     const size_t need = (size_t)b->total_grid * sizeof(double);
     if (dst_bytes != need) return fail(NATAC_E_ARG, "destination holds %zu bytes, grid needs %zu", dst_bytes, need);
     HIPCHK(hipSetDevice(b->ctx->device));
@@ -2094,13 +2103,15 @@ int natac_batch_set_track(natac_batch *b, int track, const double *vals, size_t 
     if (n != (size_t)b->total_bp) return fail(NATAC_E_ARG, "track needs %lld values, got %zu", b->total_bp, n);
     natac_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->device));
+    int rc;
+    // a pending background is formed from NUC_COV: it keeps the values natac_run_nuc gave it
+    if (track == NATAC_T_NUC_COV && b->out.track[NATAC_T_BACKGROUND] == TS_PENDING && (rc = materialise_bg(b))) return rc;
     HIPCHK(sync_all(c));
-    int rc = ensure_track(b, track);
-    if (rc) return rc;
+    if ((rc = ensure_track(b, track))) return rc;
     HIPCHK(hipMemcpyAsync(b->d_track[track], vals, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (track <= NATAC_T_SMOOTH) { b->nuc_done = true; if (track == NATAC_T_BACKGROUND) b->bg_valid = true; }   // the stage flags only gate downloads / the writer
-    else { b->occ_done = true; if (track == NATAC_T_OCC_PREFILL) b->prefill_valid = true; }
+    b->out.track[track] = TS_HOST;      // and no other track changes state
+    if (track == NATAC_T_OCC_COV) b->out.occ_cov_by_nuc = false;
     return NATAC_OK;
 }
 
@@ -2116,11 +2127,10 @@ int natac_batch_status(natac_batch *b, int32_t *dst, size_t dst_bytes) {
 int natac_batch_track_ptr(natac_batch *b, int track, void **dptr) {
     if (!b || !dptr) return fail(NATAC_E_ARG, "null argument");
     if (track < 0 || track >= NATAC_T_COUNT) return fail(NATAC_E_ARG, "bad track id");
-    if ((track == NATAC_T_OCC_PREFILL && b->occ_done) || (track == NATAC_T_BACKGROUND && b->nuc_done)) {
-        HIPCHK(hipSetDevice(b->ctx->device));
-        int rc = materialise_track(b, track);
-        if (rc) return rc;
-    }
+    *dptr = nullptr;
+    if (b->out.track[track] == TS_EMPTY) return NATAC_OK;
+    int rc = need_track(b, track);
+    if (rc) return rc;
     *dptr = b->d_track[track];
     return NATAC_OK;
 }
@@ -2419,12 +2429,11 @@ int natac_batch_format_track(natac_batch *b, int track, const int32_t *chrom_id,
                              const int64_t *chunk_start, int write_zero, int compress, int64_t *n_bytes, int64_t *n_text_bytes,
                              int64_t *n_lines, int32_t *n_hard) {
     if (!b || !chrom_id || !names || !chunk_start || n_names <= 0) return fail(NATAC_E_ARG, "null argument");
-    int rc = track_ready(b, track);
+    int rc = need_track(b, track);
     if (rc) return rc;
     natac_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
-    if ((rc = materialise_track(b, track))) return rc;
     if (track != NATAC_T_INS)
         return format_values(b, b->d_track[track], chrom_id, names, n_names, chunk_start, write_zero, compress, n_bytes, n_text_bytes, n_lines,
                              n_hard);
@@ -3088,13 +3097,12 @@ int natac_store_adopt(natac_store *s, natac_batch *b, int32_t n_tracks, const in
     *segment = -1;
     if (n_hard) *n_hard = 0;
     natac_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->device));
     int rc;
     for (int i = 0; i < n_tracks; ++i) {
         if (tracks[i] == NATAC_T_INS) return fail(NATAC_E_ARG, "float64 tracks only");
-        if ((rc = track_ready(b, tracks[i]))) return rc;
-        if ((rc = materialise_track(b, tracks[i]))) return rc;
+        if ((rc = need_track(b, tracks[i]))) return rc;
     }
+    HIPCHK(hipSetDevice(c->device));
     if (b->total_bp >= 0xffffffffLL) return fail(NATAC_E_ARG, "batch too long (%lld bases)", b->total_bp);
     {   // budget first: nothing is launched or allocated for a segment the store will not keep
         const long long need = (long long)n_tracks * b->total_bp * (long long)sizeof(double);

@@ -227,6 +227,68 @@ def test_argument_errors(ctx):
     b.free()
 
 
+def test_each_output_is_readable_only_once_written(ctx):
+    """natac_batch_set_track makes exactly its own track readable: a call that reads any other output of the batch is a state
+    error (NATAC_E_STATE), never a kernel or copy on a buffer nothing wrote; a host write of nuc_cov leaves the background
+    natac_run_nuc left to be formed on request as it was; every float64 track reads back bit for bit what the host wrote."""
+    import ctypes as C
+    from nucleoatac_amd.device import TrackStore
+    pk = make_synthetic_chunks(3, 500, 60, seed=2)
+    n, chroms = pk.total_bp, ["chr1"] * pk.n_chunks
+    rng = np.random.default_rng(5)
+
+    def state_error(call):
+        with pytest.raises(L.NatacError) as e:
+            call()
+        assert e.value.code == -3, e.value
+
+    b = ctx.upload(pk)
+    b.set_track(L.T_NORM, rng.random(n))
+    p = C.c_void_p(1)
+    assert b._lib.natac_batch_track_ptr(b._h, L.T_BACKGROUND, C.byref(p)) == 0 and p.value is None   # holds nothing: NULL
+    store = TrackStore()
+    state_error(lambda: b.track(L.T_BACKGROUND))
+    state_error(lambda: b.format_track(L.T_BACKGROUND, chroms, pk.chunk_start))
+    state_error(lambda: store.adopt(b, [L.T_BACKGROUND]))
+    state_error(b.run_peaks)                                   # SMOOTH
+    state_error(lambda: b.run_candidates([0], [5]))            # NUC_COV
+    b.set_track(L.T_SMOOTH, rng.random(n))
+    b.set_track(L.T_NUC_COV, rng.random(n))
+    state_error(b.run_peaks)                                   # exp(bias) of the candidate statistics: natac_run_nuc forms it
+    state_error(lambda: b.run_candidates([0], [5]))
+    store.close()
+    b.free()
+    b = ctx.upload(pk)
+    b.set_track(L.T_OCC, rng.random(n))
+    state_error(lambda: b.track(L.T_OCC_PREFILL))
+    state_error(b.run_occ_peaks)
+    state_error(lambda: b.grid(L.G_OCC))
+    b.free()
+
+    ref, b = ctx.upload(pk), ctx.upload(pk)
+    for x in (ref, b):
+        x.run_nuc(10)
+    zeros = np.zeros(n)
+    b.set_track(L.T_NUC_COV, zeros)
+    assert np.array_equal(b.track(L.T_BACKGROUND), ref.track(L.T_BACKGROUND)) and np.array_equal(b.track(L.T_NUC_COV), zeros)
+    for x in (ref, b):
+        x.run_occ()
+    assert np.array_equal(b.track(L.T_OCC_COV), ref.track(L.T_OCC_COV))      # from the fragments, not from the host's nuc_cov
+    ref.free()
+    b.free()
+
+    b = ctx.upload(pk)
+    tracks = [t for t in range(L.T_OCC_PREFILL + 1) if t != L.T_INS]
+    vals = {t: rng.normal(size=n) for t in tracks}
+    for t in tracks:
+        vals[t][rng.integers(0, n, 50)] = np.nan
+        vals[t][rng.integers(0, n, 50)] = -0.0
+        b.set_track(t, vals[t])
+    for t in tracks:
+        assert np.array_equal(b.track(t).view(np.uint64), vals[t].view(np.uint64)), t
+    b.free()
+
+
 def test_zero_probability_bins_reproduce_reference_failure():
     """a size bin with probability 0 in BOTH distributions makes every log-likelihood -inf (0*log 0 = NaN -> -inf,
     Occupancy.py:112-114): the reference dies with ValueError at :118; the library flags the chunk and writes NaN.
