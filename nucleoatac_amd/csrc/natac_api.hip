@@ -330,11 +330,14 @@ static void launch_candidates(natac_ctx *c, const ChunkTable &ct, const VMatDev 
     const int EW = c->W + ((c->vupper - 2) >> 1) + ((c->vupper - 1) >> 1);
     const int ZN = (((c->vupper - 2) >> 1) + ((c->vupper - 1) >> 1) + 5 + 32) & ~1, ON = (c->W + 1) & ~1;
     const size_t lds4 = ((size_t)4 * CAND_PER_WAVE * ((EW + 1) & ~1) + ZN + ON) * sizeof(double);
+    // The paired-row and four-per-wave kernels give each lane the template columns `lane` and `lane + 64`, nothing more: templates
+    // wider than 128 columns take natac_candidates (a column loop), whatever NATAC_CAND_OLD / NATAC_CAND_FULL ask for.
+    const bool per_wave = c->W <= 2 * WAVE;
     // paired-row kernel (natac_cand.hpp): needs the background kernel's window sums, no single-cell row, whole row pairs, a template
-    // at least 64 columns wide (every lane's first column exists) and
+    // 64 to 128 columns wide (every lane's first column exists) and
     // a model without exact zeros (those take the per-cell zero test of natac_candidates4).  NATAC_CAND_OLD=1: validation.
     const size_t ldsp = (size_t)4 * CAND_PER_WAVE * CANDP_STRIDE * sizeof(double);
-    bool paired = bnum && bcov && c->vlower >= 2 && (c->R & 1) == 0 && c->W >= 64 && !vm.has_zero && EW <= CANDP_STRIDE &&
+    bool paired = per_wave && bnum && bcov && c->vlower >= 2 && (c->R & 1) == 0 && c->W >= 64 && !vm.has_zero && EW <= CANDP_STRIDE &&
                   !getenv("NATAC_CAND_FULL") && !getenv("NATAC_CAND_OLD");
     if (paired && (c->lrt_gen != c->model_gen || !c->d_lrt)) {      // log(V / s) of the current model, on the launch stream (natac_lr_table)
         if (!c->d_lrt || c->lrt_cap < (size_t)c->R * c->W) {
@@ -363,7 +366,7 @@ static void launch_candidates(natac_ctx *c, const ChunkTable &ct, const VMatDev 
                                bnum, bcov, tile_first, ranges256, lr, var, z);
         return;
     }
-    if (lds4 <= 64 * 1024) {
+    if (per_wave && lds4 <= 64 * 1024) {
         const long long per_block = 4 * CAND_PER_WAVE;
         if (bnum && bcov && !getenv("NATAC_CAND_FULL"))   // NATAC_CAND_FULL=1: all four window sums in the kernel (validation)
             hipLaunchKernelGGL((natac_candidates4<true>), dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), lds4, c->stream,
@@ -371,7 +374,7 @@ static void launch_candidates(natac_ctx *c, const ChunkTable &ct, const VMatDev 
         else
             hipLaunchKernelGGL((natac_candidates4<false>), dim3((unsigned)((n + per_block - 1) / per_block)), dim3(256), lds4, c->stream,
                                ct, vm, d_cc, d_cp, (int)n, nuc_cov, norm, bnum, bcov, lr, var, z);
-    } else {   // very wide templates: one workgroup per candidate
+    } else {   // templates wider than 128 columns or windows too wide for four per wave in LDS: one workgroup per candidate
         hipLaunchKernelGGL(natac_candidates, dim3((unsigned)n), dim3(256), (size_t)(EW + 2) * sizeof(double), c->stream, ct, vm, d_cc,
                            d_cp, nuc_cov, norm, lr, var, z);
     }

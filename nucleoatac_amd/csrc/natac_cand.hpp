@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) natac_lr_table(const double *__restrict__
 constexpr int CANDP_STRIDE = 376;   // doubles per candidate window in LDS (compile-time: every LDS address of the sweep is a
                                     // running base register + an immediate); V-plots with W + upper - 2 > 376 use natac_candidates4
 
-// LODD: parity of vm.lower.  Requires vm.lower >= 2, R even, W >= 64, EW <= CANDP_STRIDE, bnum / bcov of the current model
+// LODD: parity of vm.lower.  Requires vm.lower >= 2, R even, 64 <= W <= 128, EW <= CANDP_STRIDE, bnum / bcov of the current model
 // (host-checked).
 template <bool LODD>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) natac_candidates_paired(

@@ -1439,7 +1439,8 @@ __global__ void __launch_bounds__(256) natac_insertions(ChunkTable ct, int lower
 }
 
 // ------------------------------------------------------------------------------------------------
-// K7  candidate statistics: one workgroup per candidate position p of a chunk.
+// K7  candidate statistics: one workgroup per candidate position p of a chunk, any template width (the only candidate kernel for
+//     templates wider than 128 columns).
 //   window cells (r, c): insert size i = vlower + r, centre x = p - w + c
 //   B0 = E[x-(i-1)//2] E[x+i//2],  B = sizes[i] B0
 //   S_B = sum B, S_BV = sum B V, S_BV2 = sum B V^2, S_B0V = sum V B0
@@ -1476,23 +1477,21 @@ __global__ void __launch_bounds__(256) natac_candidates(ChunkTable ct, VMatDev v
     __syncthreads();
     double sB = 0, sBV = 0, sBV2 = 0, sB0V = 0;
     int zero = 0;
-    // 2-D sweep without integer division: 128 lanes across the window columns, two row phases
-    {
-        const int c = threadIdx.x & 127;
-        if (c < vm.W) {
-            for (int r = threadIdx.x >> 7; r < vm.R; r += 2) {
-                const int i = vm.lower + r;
-                const int hl = floor_half(i - 1), hr = floor_half(i);
-                const double b0 = (hl == -hr) ? Et[c + A] : Et[c + A - hl] * Et[c + A + hr];
-                const double bb = vm.srow[r] * b0;
-                const double v = vm.mat[r * vm.W + c];
-                const double vb0 = v * b0;
-                sB += bb;
-                sBV = fma(bb, v, sBV);
-                sBV2 = fma(bb * v, v, sBV2);
-                sB0V += vb0;
-                if (vb0 == 0.0 || bb == 0.0) zero = 1;
-            }
+    // 2-D sweep without integer division: 128 lanes across the window columns (a lane takes every 128th column of templates wider
+    // than that), two row phases
+    for (int c = threadIdx.x & 127; c < vm.W; c += 128) {
+        for (int r = threadIdx.x >> 7; r < vm.R; r += 2) {
+            const int i = vm.lower + r;
+            const int hl = floor_half(i - 1), hr = floor_half(i);
+            const double b0 = (hl == -hr) ? Et[c + A] : Et[c + A - hl] * Et[c + A + hr];
+            const double bb = vm.srow[r] * b0;
+            const double v = vm.mat[r * vm.W + c];
+            const double vb0 = v * b0;
+            sB += bb;
+            sBV = fma(bb, v, sBV);
+            sBV2 = fma(bb * v, v, sBV2);
+            sB0V += vb0;
+            if (vb0 == 0.0 || bb == 0.0) zero = 1;
         }
     }
     sB = wave_sum(sB); sBV = wave_sum(sBV); sBV2 = wave_sum(sBV2); sB0V = wave_sum(sB0V);
@@ -1540,7 +1539,8 @@ __global__ void __launch_bounds__(256) natac_candidates(ChunkTable ct, VMatDev v
 
 // K7b  the same statistics, four candidates per wave: every template value V[r,c] is loaded once per lane and applied to
 // four candidate windows whose exp(bias) slices sit in LDS (4x less L2 template traffic, 4 independent dependency chains,
-// no block-level synchronisation: DPP wave reductions only).  Workgroup = 4 waves = 16 candidates.
+// no block-level synchronisation: DPP wave reductions only).  Workgroup = 4 waves = 16 candidates.  A lane owns template columns
+// `lane` and `lane + 64`: W <= 128 (host-checked; wider templates take natac_candidates).
 constexpr int CAND_PER_WAVE = 4;
 
 // first index in the sorted array a[lo, hi) with a[idx] >= key, found by the whole wave: 64 evenly spaced probes per step

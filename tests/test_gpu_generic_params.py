@@ -1,6 +1,10 @@
-"""GPU: non-default parameters take the generic kernels (natac_background_generic, natac_occ_mle<0,0>, natac_occ_cov,
-runtime-width smoothing): trimmed V-plot (W = 101, rows 110..240), occupancy with step 3 / flank 45 / upper 200,
-smoothing sd 7, a 65-point alpha grid -- all against the oracle."""
+"""GPU: non-default model parameters against the oracle.  V-plots of other shapes (W = 101 / 121 / 41, rows 110..240, 111..240,
+107..250, 1..60) with smoothing sd 7: the FFT background for lower >= 2, natac_background_generic for the V-plot that includes insert
+size 1, natac_candidates_paired<false> / natac_candidates4<true>, runtime-width smoothing (natac_smooth_same).  Occupancy with step 3 /
+flank 45 / upper 200 / 65 alphas: the block-sum path (natac_occ_gsum / natac_occ_decide, natac_occ_smooth_blk<3>) and natac_occ_cov;
+any odd step <= 9 and flank on the block-sum path against the general kernel; step > 9 and grids of more than 101 alphas on the
+general kernel's three instantiations (natac_occ_mle<0,0,0>, <5,60,0,1>, <5,60,0>), runtime-width occupancy smoothing (natac_occ_smooth)
+and natac_fill_nan_min."""
 import numpy as np
 import pytest
 
@@ -58,6 +62,8 @@ def test_generic_vmat_geometry(vlo, vup, w):
 
 
 def test_generic_occupancy_parameters():
+    """step 3 / flank 45 / upper 200 / 65 alphas: the block-sum kernels (natac_occ_gsum / natac_occ_decide) and natac_occ_smooth_blk<3>;
+    occupancy coverage from the fragments (natac_occ_cov: no nucleosome stage ran)"""
     from nucleoatac_amd.device import Context
     from oracle import natac_oracle as O
     upper, flank, step = 200, 45, 3
@@ -186,3 +192,46 @@ def test_heavy_tiles_first_does_not_show_in_any_result():
         oc = O.occ_chunk_tracks(l.astype(np.int64), n.astype(np.int64), 0, 2120, pk.chunk_bias(k), -246, nucp, nfrp)
         for gi, key in enumerate(("occ", "occ_lower", "occ_upper")):
             assert_track(expand_grid(out["1"][gi][k * nk:(k + 1) * nk], 2120, 5), oc[key], key, exact=True)
+
+
+@pytest.mark.parametrize("step,flank,n_alpha", [(11, 60, 101), (13, 45, 101), (5, 60, 112), (5, 60, 120)])
+def test_general_occupancy_kernel_arms(step, flank, n_alpha):
+    """the general kernel's arms, none of which the block-sum path reaches: a step over 9 (natac_occ_mle<0,0,0>, then the runtime-width
+    smoothing natac_occ_smooth and the NaN fill natac_fill_nan_min) and step 5 / flank 60 with more than 101 alphas
+    (natac_occ_mle<5,60,0,1> up to 16 x OCC_RA = 112 of them, natac_occ_mle<5,60,0> above); sparse chunks leave NaN grid points to
+    smooth around and to fill"""
+    from nucleoatac_amd.device import Context
+    from oracle import natac_oracle as O
+    nucp, nfrp = synth_occ_distributions(251)
+    Lc = 1203
+    counts = np.full(12, 330, dtype=np.int64)
+    counts[3::4] = 10
+    pk = make_synthetic_chunks(12, Lc, 330, seed=step * 1000 + n_alpha, counts=counts)
+    with Context(0) as c:
+        c.set_occ_model(nucp, nfrp, alphas=np.linspace(0, 1, n_alpha), step=step, flank=flank)
+        b = c.upload(pk)
+        b.run_occ()
+        assert not b.status().any()
+        grids = [b.grid(g) for g in (L.G_OCC, L.G_LOWER, L.G_UPPER)]
+        tr = {t: b.split(b.track(t)) for t in (L.T_OCC, L.T_OCC_PREFILL, L.T_OCC_LOWER, L.T_OCC_UPPER, L.T_OCC_COV)}
+        b.free()
+    nk = len(range((step - 1) // 2, Lc, step))
+    filled = 0
+    for k in (0, 3, 7, 11):
+        l, n = pk.chunk_frags(k)
+        oc = O.occ_chunk_tracks(l.astype(np.int64), n.astype(np.int64), 0, Lc, pk.chunk_bias(k), -246, nucp, nfrp, flank=flank, step=step,
+                                n_alpha=n_alpha)
+        for gi, key in enumerate(("occ", "occ_lower", "occ_upper")):
+            assert_track(expand_grid(grids[gi][k * nk:(k + 1) * nk], Lc, step), oc[key], key, exact=True)
+        sv = oc["smoothed_vals"]
+        assert_track(tr[L.T_OCC_PREFILL][k], sv, "smoothed")
+        assert_track(tr[L.T_OCC_LOWER][k], oc["smoothed_lower"], "smoothed_lower")
+        assert_track(tr[L.T_OCC_UPPER][k], oc["smoothed_upper"], "smoothed_upper")
+        assert_track(tr[L.T_OCC_COV][k], oc["cov"], "cov", exact=True)
+        # the occupancy track with the chunk's minimum in the smoothing's NaN gaps (as call_peaks fills them, utils.py:94-97)
+        gap = np.isnan(sv)
+        want = sv.copy()
+        want[gap] = np.nanmin(sv)
+        assert_track(tr[L.T_OCC][k], want, "filled")
+        filled += int(gap.sum())
+    assert filled > 0
