@@ -11,6 +11,8 @@
  *         pyatac/fragments.pyx:71   getStrandedInsertions         -> natac_get_stranded_insertions
  *         pyatac/fragments.pyx:123  getFragmentSizesFromChunkList -> natac_fragment_sizes
  *         nucleoatac/multinomial_cov.pyx:20 calculateCov          -> natac_calculate_cov
+ *   (3) `pyatac pwm`'s window counts (pyatac/get_pwm.py:21-40, tracks.py:179-201) -> natac_insertion_seq_counts
+ *       and its background base counts (pyatac/seq.py:47-72)                   -> natac_base_counts
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -35,9 +37,9 @@ extern "C" {
 #endif
 
 /* bumped whenever an entry point is added, removed or changes meaning (2: round 5 removed natac_run_nuc_occ, added natac_bg_tiling /
- * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait);
- * the binding refuses another version */
-#define NATAC_ABI_VERSION 3
+ * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
+ * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`); the binding refuses another version */
+#define NATAC_ABI_VERSION 4
 
 enum {
     NATAC_OK = 0,
@@ -238,6 +240,20 @@ int natac_make_bias_mat(natac_ctx *ctx, const double *bias_log, int64_t nb, int6
  * log_pwm[nrow x K] = log(PWM.mat), nucleotides[nrow] the PWM's row letters; out[n-K+1]. */
 int natac_pwm_bias(natac_ctx *ctx, const uint8_t *seq, int64_t n, const double *log_pwm, const uint8_t *nucleotides,
                    int nrow, int K, double *out);
+/* _pwmHelper, pyatac/get_pwm.py:21-40, with InsertionTrack.calculateInsertions + getInsertionSequences (sym != 0) or
+ * calculateStrandedInsertions + getStrandedInsertionSequences (sym == 0), pyatac/tracks.py:164-201 and fragments.pyx:43-97, summed over
+ * a packed chunk list: chunk_len / frag_off / frag_lpos / frag_ilen as natac_pack_chunks gives them (lpos relative to the chunk start,
+ * ATAC shift applied), seq[seq_off[k] .. seq_off[k+1]) = the upper-case bases of [start_k - flank, end_k + flank) (K - 1 more than the
+ * chunk).  A fragment counts if lower <= ilen < upper; its ends l and l + ilen - 1 each count if they lie in the chunk.  counts[4 x K]
+ * (rows A C G T, K = 2*flank + 1, other bases in no row) and n_ins = the number of counted ends are exact int64 sums, overwritten.
+ * flank in [0, 1000].  kernel_ms (may be NULL): device time of the counting kernel alone. */
+int natac_insertion_seq_counts(natac_ctx *ctx, int32_t n_chunks, const int32_t *chunk_len, const int64_t *frag_off, const int32_t *frag_lpos,
+                               const int32_t *frag_ilen, const int64_t *seq_off, const uint8_t *seq, int flank, int lower, int upper, int sym,
+                               int64_t *counts, int64_t *n_ins, double *kernel_ms);
+/* the numerators of seq.getNucFreqs / getNucFreqsFromChunkList, pyatac/seq.py:47-72: counts[4] = the A, C, G, T bases (upper or lower
+ * case) of seq[start[i] .. end[i]) summed over the n_ranges ranges, int64, overwritten; overlapping ranges count once per range. */
+int natac_base_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int32_t n_ranges, const int64_t *start, const int64_t *end,
+                      int64_t *counts);
 /* signal.correlate(sub, vmat, mode='valid')[0] as used by SignalTrack.calculateSignal / BiasTrack
  * (nucleoatac/NucleosomeCalling.py:34-36, 60-63): sub[R x ncol], vmat[R x W] row-major, out[ncol-W+1]. */
 int natac_correlate_valid(natac_ctx *ctx, const double *sub, int64_t ncol, const double *vmat, int R, int W, double *out);

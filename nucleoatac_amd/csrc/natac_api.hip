@@ -19,6 +19,7 @@
 #include "natac_fasta.hpp"
 #include "natac_fuzzfit.hpp"
 #include "natac_bedtab.hpp"
+#include "natac_pwmfit.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -2379,6 +2380,123 @@ int natac_pwm_bias(natac_ctx *c, const uint8_t *seq, int64_t n, const double *lo
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     dev_free(d_s); dev_free(d_n); dev_free(d_p); dev_free(d_o);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "pwm_bias: %s", hipGetErrorString(e));
+    return NATAC_OK;
+}
+
+int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_len, const int64_t *frag_off, const int32_t *frag_lpos,
+                               const int32_t *frag_ilen, const int64_t *seq_off, const uint8_t *seq, int flank, int lower, int upper, int sym,
+                               int64_t *counts, int64_t *n_ins, double *kernel_ms) {
+    using namespace natac_pwmfit;
+    if (!c || !counts || !n_ins) return fail(NATAC_E_ARG, "null argument");
+    if (flank < 0 || flank > PF_MAX_FLANK) return fail(NATAC_E_ARG, "flank must be in [0, %d] (got %d)", PF_MAX_FLANK, flank);
+    if (upper <= lower) return fail(NATAC_E_ARG, "upper (%d) <= lower (%d)", upper, lower);
+    if (nc < 0) return fail(NATAC_E_ARG, "negative chunk count");
+    if (nc > 0 && (!chunk_len || !frag_off || !seq_off)) return fail(NATAC_E_ARG, "null argument");
+    const int K = 2 * flank + 1;
+    if (kernel_ms) *kernel_ms = 0;
+    for (int i = 0; i < 4 * K; ++i) counts[i] = 0;
+    *n_ins = 0;
+    if (nc == 0) return NATAC_OK;
+    // the kernel trusts both offset arrays: every window access lies in [seq_off[k], seq_off[k+1]), every fragment in one chunk
+    if (frag_off[0] != 0 || seq_off[0] != 0) return fail(NATAC_E_ARG, "frag_off[0] and seq_off[0] must be 0");
+    for (int k = 0; k < nc; ++k) {
+        if (chunk_len[k] < 0) return fail(NATAC_E_ARG, "chunk %d: negative length", k);
+        if (frag_off[k + 1] < frag_off[k]) return fail(NATAC_E_ARG, "frag_off must be non-decreasing (chunk %d)", k);
+        if (seq_off[k + 1] - seq_off[k] != (int64_t)chunk_len[k] + K - 1)
+            return fail(NATAC_E_ARG, "seq_off: chunk %d has %lld bases, its window [start - %d, end + %d) needs %lld", k,
+                        (long long)(seq_off[k + 1] - seq_off[k]), flank, flank, (long long)chunk_len[k] + K - 1);
+    }
+    const long long nf = frag_off[nc], ns = seq_off[nc];
+    if (nf > 0 && (!frag_lpos || !frag_ilen)) return fail(NATAC_E_ARG, "null argument");
+    if (ns > 0 && !seq) return fail(NATAC_E_ARG, "null argument");
+    if (nf >= (1LL << 40)) return fail(NATAC_E_ARG, "too many fragments in one call");
+    if (nf == 0) return NATAC_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int *d_len = nullptr, *d_l = nullptr, *d_n = nullptr;
+    long long *d_fo = nullptr, *d_so = nullptr;
+    unsigned char *d_s = nullptr;
+    unsigned long long *d_out = nullptr;
+    auto release = [&]() { dev_free(d_len); dev_free(d_l); dev_free(d_n); dev_free(d_fo); dev_free(d_so); dev_free(d_s); dev_free(d_out); };
+    int rc;
+    if ((rc = dev_upload(c, &d_len, chunk_len, (size_t)nc)) || (rc = dev_upload(c, &d_fo, (const long long *)frag_off, (size_t)nc + 1)) ||
+        (rc = dev_upload(c, &d_so, (const long long *)seq_off, (size_t)nc + 1)) || (rc = dev_upload(c, &d_l, frag_lpos, (size_t)nf)) ||
+        (rc = dev_upload(c, &d_n, frag_ilen, (size_t)nf)) || (rc = dev_upload(c, &d_s, (const unsigned char *)seq, (size_t)ns)) ||
+        (rc = dev_alloc(&d_out, (size_t)4 * K + 1))) {
+        release();
+        return rc;
+    }
+    std::vector<unsigned long long> h((size_t)4 * K + 1);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipMemsetAsync(d_out, 0, h.size() * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess && kernel_ms) {
+        e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
+    }
+    if (e == hipSuccess) {
+        const int CW = K < 64 ? K : 64;
+        const long long nseg = (nf + PF_SEG - 1) / PF_SEG;
+        const int bx = (int)std::min<long long>((nseg + PF_BLOCK / 64 - 1) / (PF_BLOCK / 64), 2048);
+        hipLaunchKernelGGL(natac_ins_seq_counts, dim3(bx, (K + CW - 1) / CW), dim3(PF_BLOCK), 0, c->stream, d_fo, d_l, d_n, nf, (int)nc,
+                           d_len, d_so, d_s, flank, lower, upper, sym ? 1 : 0, d_out, d_out + 4 * K);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && kernel_ms) e = hipEventRecord(e1, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && kernel_ms) {
+        float ms = 0;
+        e = hipEventElapsedTime(&ms, e0, e1);
+        *kernel_ms = ms;
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    release();
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "insertion_seq_counts: %s", hipGetErrorString(e));
+    for (int i = 0; i < 4 * K; ++i) counts[i] = (int64_t)h[i];
+    *n_ins = (int64_t)h[4 * K];
+    return NATAC_OK;
+}
+
+int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, const int64_t *start, const int64_t *end, int64_t *counts) {
+    using namespace natac_pwmfit;
+    if (!c || !counts || n < 0 || nr < 0) return fail(NATAC_E_ARG, "null argument or negative size");
+    if (nr > 0 && (!start || !end)) return fail(NATAC_E_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) counts[i] = 0;
+    std::vector<long long> cum((size_t)nr + 1, 0);
+    for (int i = 0; i < nr; ++i) {
+        if (start[i] < 0 || end[i] < start[i] || end[i] > n)
+            return fail(NATAC_E_ARG, "range %d [%lld, %lld) outside [0, %lld)", i, (long long)start[i], (long long)end[i], (long long)n);
+        cum[i + 1] = cum[i] + (end[i] - start[i]);
+    }
+    const long long total = cum[nr];
+    if (total == 0) return NATAC_OK;
+    if (!seq) return fail(NATAC_E_ARG, "null argument");
+    // lane counters are 32-bit: a block adds at most ceil(total / blocks) bases
+    const long long bx = std::min<long long>((total + PF_SPAN - 1) / PF_SPAN, 8192);
+    if ((total + bx - 1) / bx >= (1LL << 31)) return fail(NATAC_E_ARG, "ranges too long for one call");
+    HIPCHK(hipSetDevice(c->device));
+    unsigned char *d_s = nullptr;
+    long long *d_st = nullptr, *d_cum = nullptr;
+    unsigned long long *d_out = nullptr;
+    auto release = [&]() { dev_free(d_s); dev_free(d_st); dev_free(d_cum); dev_free(d_out); };
+    int rc;
+    if ((rc = dev_upload(c, &d_s, (const unsigned char *)seq, (size_t)n)) || (rc = dev_upload(c, &d_st, (const long long *)start, (size_t)nr)) ||
+        (rc = dev_upload(c, &d_cum, cum.data(), cum.size())) || (rc = dev_alloc(&d_out, 4))) {
+        release();
+        return rc;
+    }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    hipError_t e = hipMemsetAsync(d_out, 0, sizeof h, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(natac_base_count, dim3((unsigned)bx), dim3(PF_BLOCK), 0, c->stream, d_s, (int)nr, d_st, d_cum, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    release();
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "base_counts: %s", hipGetErrorString(e));
+    for (int i = 0; i < 4; ++i) counts[i] = (int64_t)h[i];
     return NATAC_OK;
 }
 

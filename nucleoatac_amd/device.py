@@ -307,6 +307,42 @@ class Context(object):
                                          logp.shape[1], _ptr(out)))
         return out
 
+    def insertion_seq_counts(self, chunk_len, frag_off, frag_lpos, frag_ilen, seq_off, seq, flank, lower=0, upper=2000, sym=True,
+                             with_kernel_ms=False):
+        """window counts of `pyatac pwm` over a packed chunk list (_pwmHelper, pyatac/get_pwm.py:21-40): (M int64[4, 2*flank+1] with
+        rows A C G T, n = counted insertions), exact.  seq[seq_off[k]:seq_off[k+1]] = the bases of [start_k - flank, end_k + flank).
+        with_kernel_ms: also return the counting kernel's device time in ms."""
+        cl = np.ascontiguousarray(chunk_len, dtype=np.int32)
+        fo = np.ascontiguousarray(frag_off, dtype=np.int64)
+        fl = np.ascontiguousarray(frag_lpos, dtype=np.int32)
+        fi = np.ascontiguousarray(frag_ilen, dtype=np.int32)
+        so = np.ascontiguousarray(seq_off, dtype=np.int64)
+        sq = np.ascontiguousarray(seq, dtype=np.uint8)
+        if fo.shape[0] != cl.shape[0] + 1 or so.shape[0] != cl.shape[0] + 1:
+            raise ValueError("frag_off and seq_off need n_chunks + 1 entries")
+        if fl.shape != fi.shape or (cl.shape[0] and (fo[-1] != fl.shape[0] or so[-1] != sq.shape[0])):
+            raise ValueError("frag_off / seq_off do not match the fragment and sequence arrays")
+        K = 2 * int(flank) + 1
+        counts = np.zeros((4, max(K, 1)), dtype=np.int64)
+        n = C.c_int64(0)
+        ms = C.c_double(0)
+        L.check(self._lib.natac_insertion_seq_counts(self._h, cl.shape[0], _ptr(cl), _ptr(fo), _ptr(fl), _ptr(fi), _ptr(so), _ptr(sq),
+                                                     int(flank), int(lower), int(upper), 1 if sym else 0, _ptr(counts), C.byref(n),
+                                                     C.byref(ms)))
+        return (counts, n.value, ms.value) if with_kernel_ms else (counts, n.value)
+
+    def base_counts(self, seq, starts=None, ends=None):
+        """int64[4]: the A, C, G, T bases of seq[starts[i]:ends[i]] summed over the ranges (default: the whole array); the numerators of
+        seq.getNucFreqs / getNucFreqsFromChunkList (pyatac/seq.py:47-72)"""
+        sq = np.ascontiguousarray(seq, dtype=np.uint8)
+        st = np.ascontiguousarray([0] if starts is None else starts, dtype=np.int64)
+        en = np.ascontiguousarray([sq.shape[0]] if ends is None else ends, dtype=np.int64)
+        if st.shape != en.shape:
+            raise ValueError("starts and ends differ in length")
+        out = np.zeros(4, dtype=np.int64)
+        L.check(self._lib.natac_base_counts(self._h, _ptr(sq), sq.shape[0], st.shape[0], _ptr(st), _ptr(en), _ptr(out)))
+        return out
+
     def correlate_valid(self, sub, vmat):
         """signal.correlate(sub, vmat, mode='valid')[0] (nucleoatac/NucleosomeCalling.py:34-36)."""
         sub, vmat = _f64(sub), _f64(vmat)

@@ -4,7 +4,7 @@ import os
 import numpy as np
 
 from . import seq
-from .tracks import Track
+from .tracks import Track, _py2_float_str
 
 _DATA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "data")
 
@@ -24,15 +24,22 @@ class PWM(object):
         self.down = down
         self.nucleotides = nucleotides
 
-    def save(self, filename):
+    def save(self, filename, py2_floats=False):
+        """descriptor file (pyatac/bias.py:31-46); values as repr, or with py2_floats=True as the reference's Python 2 str(float)
+        wrote them (12 significant digits, what `pyatac pwm` writes)"""
+        fmt = _py2_float_str if py2_floats else repr
         with open(filename, "w") as out:
             out.write("#PWM Descriptor File\n#Contains PWM and pertinent information\n")
             out.write("#up\n%d\n#down\n%d\n#nucleotides\n%s\n#mat\n" % (self.up, self.down, "\t".join(self.nucleotides)))
             for row in self.mat:
-                out.write("\t".join(repr(float(x)) for x in row) + "\n")
+                out.write("\t".join(fmt(float(x)) for x in row) + "\n")
 
     @staticmethod
     def open(name):
+        """a built-in table name, a descriptor file, or a PWM object (returned as it is: a matrix fitted in the same process, e.g. by
+        `pyatac pwm`, can be handed to occ / nuc through the API)"""
+        if isinstance(name, PWM):
+            return name
         if name in BUILTIN_PWMS:
             t = np.load(os.path.join(_DATA, "tn5_pwm_tables.npz"), allow_pickle=False)
             return PWM(np.array(t[name + "_mat"]), int(t[name + "_up"]), int(t[name + "_down"]),

@@ -178,3 +178,53 @@ def seq_to_mat(sequence, nucleotides):
     for i, word in enumerate(nucleotides):
         mat[i] = [1.0 if sequence[j:j + k] == word else 0.0 for j in range(n)]
     return mat
+
+
+ACGT = ["A", "C", "G", "T"]       # row order of natac_insertion_seq_counts / natac_base_counts
+
+
+def acgt_rows(nucleotides):
+    """rows of the device's A C G T counts that give `nucleotides` in its order; the device counts single bases only"""
+    k = len(nucleotides[0])
+    if not all(len(x) == k for x in nucleotides):
+        raise Exception("Usage Error! Nucleotides must all be of same length! No mixing single nucleotides with dinucleotides, etc")
+    bad = [x for x in nucleotides if x not in ACGT]
+    if bad:
+        raise NotImplementedError("only the single bases A, C, G, T are counted on the device (got %s)" % ", ".join(bad))
+    return [ACGT.index(x) for x in nucleotides]
+
+
+def getNucFreqs(fasta, nucleotides):
+    """genome-wide base frequencies (pyatac/seq.py:47-58): base counts over every record of the FASTA divided by the total length,
+    N and every other letter included -- the frequencies do not sum to 1 when the genome has Ns.  Counts by natac_base_counts."""
+    from .. import get_context
+    rows = acgt_rows(nucleotides)
+    fs = FastaStore.open(fasta)
+    out = np.zeros(4, dtype=np.int64)
+    n = 0
+    for c in fs.references:
+        s = fs.seqs[c]
+        if len(s):
+            out += get_context().base_counts(s)
+        n += len(s)
+    return out[rows].astype(np.float64) / float(n)
+
+
+def getNucFreqsFromChunkList(chunks, fasta, nucleotides):
+    """base frequencies inside the regions (pyatac/seq.py:61-72): counts over every chunk's [start, end) divided by the summed
+    lengths; overlapping chunks count twice.  One natac_base_counts call per chromosome."""
+    from .. import get_context
+    rows = acgt_rows(nucleotides)
+    fs = FastaStore.open(fasta)
+    by_chrom = {}
+    for ch in chunks:
+        by_chrom.setdefault(ch.chrom, []).append((ch.start, ch.end))
+    out = np.zeros(4, dtype=np.int64)
+    n = 0
+    for c, iv in by_chrom.items():
+        s = fs.seqs[c]
+        st = np.clip(np.array([a for a, _ in iv], dtype=np.int64), 0, len(s))       # what a fetch past the end returns
+        en = np.clip(np.array([b for _, b in iv], dtype=np.int64), st, len(s))
+        out += get_context().base_counts(s, st, en)
+        n += int(np.sum(en - st))
+    return out[rows].astype(np.float64) / float(n)

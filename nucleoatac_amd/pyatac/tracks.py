@@ -186,6 +186,50 @@ class InsertionTrack(Track):
         self.vals = self.plus + self.minus
 
 
+    def getInsertionSequences(self, fasta, nucleotides=["C", "G", "A", "T"], up=10, down=10):
+        """base content around the insertions of the track (pyatac/tracks.py:179-189): column j sums vals[i] * onehot(seq[i - up + j])
+        -- natac_insertion_seq_counts"""
+        return _insertion_sequences(self, fasta, nucleotides, up, down, self.vals, None)
+
+    def getStrandedInsertionSequences(self, fasta, nucleotides=["C", "G", "A", "T"], up=10, down=10):
+        """the same with strand (pyatac/tracks.py:190-201): plus ends as above, minus ends add the complemented window read right to
+        left, onehot(complement(seq[i + up - j])) -- natac_insertion_seq_counts"""
+        return _insertion_sequences(self, fasta, nucleotides, up, down, self.plus, self.minus)
+
+
+def _insertion_sequences(track, fasta, nucleotides, up, down, plus, minus):
+    """the window counts of one track on the device.  Each insertion becomes a fragment with exactly one end inside the track: a
+    plus (or unstranded) insertion at i is a fragment starting at i that ends past the track, a minus insertion at i one that starts
+    before the track and ends at i; the kernel's flank is max(up, down) and columns [flank - up, flank + down] are the window."""
+    from .. import get_context
+    from .seq import FastaStore, acgt_rows
+    rows = acgt_rows(nucleotides)
+    L = track.length()
+    F = max(up, down)
+
+    def units(v):
+        v = np.zeros(L) if v is None else np.asarray(v, dtype=np.float64)
+        if v.shape != (L,) or np.any(v < 0) or np.any(v != np.floor(v)):
+            raise ValueError("insertion counts must be non-negative integers, one per base of the track")
+        return np.repeat(np.arange(L, dtype=np.int64), v.astype(np.int64))
+
+    p, m = units(plus), units(minus)
+    mat = np.zeros((len(nucleotides), up + down + 1))
+    if len(p) + len(m) == 0:
+        return mat
+    s = FastaStore.open(fasta).seqs[track.chrom]
+    a, b = track.start - F, track.end + F
+    if a < 0 or b > len(s):
+        raise Exception("track %s:%d-%d is too close to the chromosome end for a window of %d bases" % (track.chrom, track.start,
+                                                                                                           track.end, F))
+    lpos = np.concatenate([p, np.full(len(m), -1, np.int64)]).astype(np.int32)
+    ilen = np.concatenate([L + 1 - p, m + 2]).astype(np.int32)
+    counts, _ = get_context().insertion_seq_counts([L], [0, len(lpos)], lpos, ilen, [0, b - a], s[a:b], F, 0, L + 2,
+                                                   sym=minus is None)
+    mat[:] = counts[rows, F - up:F + down + 1]
+    return mat
+
+
 class CoverageTrack(Track):
     """fragment-centre coverage in a flat window (pyatac/tracks.py:204-222)"""
 
