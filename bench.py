@@ -10,18 +10,27 @@ Workloads (--workload):
                   VMat (146 x 121).  With N > 1 every rank owns its own shard of the same shape (weak scaling).
   cfg3-heavy      the same windows with Poisson fragment counts and 1 % of the chunks 10x denser (heavy-tailed load).
   cfg5            BASELINE.json configs[4]: 8 independent samples, one per GPU (every rank its own 12,500-chunk configs[2]-like set
-                  with its own seed: replicas, weak scaling); after the timed steps every rank runs the multinomial_cov tolerance
-                  sweep (literal O(N^2) fp64 / closed form fp64 / closed form fp32 at the candidates of 200 chunks) and rank 0
-                  reports the worst relative errors over all samples.
+                  with its own seed: replicas, weak scaling); with --full, after the timed steps every rank runs the
+                  multinomial_cov tolerance sweep (literal O(N^2) fp64 / closed form fp64 / closed form fp32 at the candidates of
+                  200 chunks) and rank 0 reports the worst relative errors over all samples.
   cfg4            BASELINE.json configs[3]: ~300k tiles x 10 kb (10,120 bp), ~200 M fragments, the chunk list sharded across
                   the N ranks by sum(L) + kappa sum(F) (nucleoatac_amd/shard.py): STRONG scaling, total work fixed.  Every
                   rank draws the same cheap per-chunk count vector, balances, and generates only its own shard in
                   counter-seeded blocks; a shard is processed in sub-batches whose outputs are recycled
                   (natac_batch_release_outputs) when they do not all fit in HBM.
 
-Also reported (rank 0, N = 1): the host-to-host rate -- packed inputs in (pinned) host memory -> per-base tracks back in
-(pinned) host memory, sub-batches pipelined over six contexts so that uploads, kernels and downloads overlap -- and the CPU
-baseline (the oracle in the reference's Pool.map shape on the box's host cores).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints its line: `value` / `ms_per_step`, the
+per-kernel times and roofline of the timed steps (HIP events on the launch stream, committed PMC summaries).  Everything else that
+needs work of its own runs only with --full:
+  * rank 0, N = 1: the CPU baseline (the oracle in the reference's Pool.map shape on the box's host cores), the host-to-host rate
+    -- packed inputs in (pinned) host memory -> per-base tracks back in (pinned) host memory, sub-batches pipelined over six
+    contexts so that uploads, kernels and downloads overlap -- as float64 arrays and as bedGraph.gz bytes, and `nucleoatac run`
+    end to end from input files (cfg3);
+  * rank 0: one more step under the shader-clock sampler (`roofline.clock_ghz`);
+  * every rank: one download of a batch's output tracks (`host.download_5_tracks_and_candidates_s`) and, with cfg5, the
+    multinomial_cov tolerance sweep.
+--no-cpu-baseline, --no-h2h and --cli-chunks 0 leave single legs out of a --full run.  --h2h-ranks (N > 1) is a leg of its own
+and runs with or without --full.
 
 Launch: python bench.py --gpus N            (N = 1 by default)
 `--gpus N` MEANS N ranks, one per GPU, whoever launches it: started plainly with N > 1 (no WORLD_SIZE in the environment) the script
@@ -87,10 +96,13 @@ def parse():
     ap.add_argument("--sub-chunks", type=int, default=20000, help="cfg4: chunks per sub-batch")
     ap.add_argument("--recycle", choices=["auto", "on", "off"], default="auto",
                     help="release every sub-batch's outputs after its stages (auto: when they do not all fit in HBM)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (see the module docstring): CPU baseline, host-to-host "
+                         "rates, CLI end to end, shader clocks, a track download, cfg5's tolerance sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-chunks", type=int, default=0, help="chunks in the CPU baseline's optimised-mode sample (0 = 2000)")
     ap.add_argument("--cpu-literal-chunks", type=int, default=0, help="chunks in the literal-mode sample (0 = auto)")
-    ap.add_argument("--no-h2h", action="store_true", help="skip the pipelined host-to-host measurement")
+    ap.add_argument("--no-h2h", action="store_true", help="--full without the pipelined host-to-host measurement")
     ap.add_argument("--h2h-sub", type=int, default=2500, help="chunks per pipelined sub-batch")
     ap.add_argument("--h2h-threads", type=int, default=6, help="contexts (host threads) of the host-to-host pipeline")
     ap.add_argument("--h2h-text-sub", type=int, default=0, help="chunks per sub-batch of the bedGraph.gz form (0: 5000, or --h2h-sub if that is given)")
@@ -98,7 +110,7 @@ def parse():
     ap.add_argument("--h2h-ranks", action="store_true", help="N > 1: every rank also runs the host-to-host pipeline on (a part of) its shard, "
                     "all ranks at once; the rates are reported per rank")
     ap.add_argument("--h2h-rank-chunks", type=int, default=20000, help="chunks of a rank's shard the --h2h-ranks leg runs on")
-    ap.add_argument("--cli-chunks", type=int, default=10000, help="chunks of the CLI end-to-end measurement (0 = skip)")
+    ap.add_argument("--cli-chunks", type=int, default=10000, help="chunks of the CLI end-to-end measurement of --full (0 = skip)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rank 0: per-base tracks and nuc candidates of a "
@@ -702,9 +714,9 @@ def main():
     t_gen = time.time() - t_gen
     my_bp = sum(s.total_bp for s in subs)
     my_frags = sum(s.n_frags for s in subs)
-    # CPU baseline first (rank 0, N=1 only): it forks worker processes, so run it before the HIP context exists
+    # --full: CPU baseline first (rank 0, N=1 only): it forks worker processes, so run it before the HIP context exists
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and subs:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and subs:
         cpu = cpu_baseline(subs[0], par, sizes, nucp, nfrp, a.cpu_chunks, a.cpu_literal_chunks)
 
     from nucleoatac_amd.device import Context as _Ctx
@@ -782,7 +794,7 @@ def main():
     # one more (untimed) step under the shader-clock sampler: the clock every kernel class really ran at (fp64-dense kernels pull
     # the chip below its 2.4 GHz; peaks quoted at 2.4 GHz are not reachable by them)
     clocks = None
-    if rank == 0 and not recycle:
+    if a.full and rank == 0 and not recycle:
         try:
             ctx.clock_trace_start(max_samples=20000, interval_us=50)
             step()
@@ -796,7 +808,7 @@ def main():
     # PCIe-inclusive figure of a resident batch (never `value`): one upload + one download of the per-base tracks that the
     # writers consume, pageable memory, no overlap -- the pipelined host-to-host rate follows below
     t_dn = None
-    if not recycle and batches:
+    if a.full and not recycle and batches:
         t_dn = time.time()
         for t in (L.T_NORM, L.T_SMOOTH, L.T_OCC, L.T_OCC_LOWER, L.T_OCC_UPPER):
             batches[0].track(t)
@@ -804,7 +816,7 @@ def main():
         t_dn = time.time() - t_dn
         assert np.isfinite(cand[4][:1000]).any()
     cov_sweep = None
-    if a.workload == "cfg5" and batches:
+    if a.full and a.workload == "cfg5" and batches:
         # calculateCov variants (nucleoatac/multinomial_cov.pyx:20-31) at every candidate of 200 chunks of this rank's sample
         b0 = batches[0]
         cc, cp, _lr, var, _z = b0.run_peaks(min_signal=0, sep=25, boundary=60, order=12)
@@ -843,7 +855,7 @@ def main():
         dist.all_gather_object(rows, (rank, mine["host_to_host_mbp_s"], mine["pcie_gbs_down"], mine["seconds"]))
         for r, v, g, sec in rows:
             per_rank[r].update(host_to_host_mbp_s=v, host_to_host_pcie_gbs_down=g, host_to_host_seconds=sec)
-    if rank == 0 and world == 1 and not a.no_h2h and a.workload != "cfg4":
+    if a.full and rank == 0 and world == 1 and not a.no_h2h and a.workload != "cfg4":
         ctx.close()
         ctx = None
         h2h = host_to_host(subs[0], local_rank, par, sizes, nucp, nfrp, a.steps, a.h2h_sub, a.h2h_threads)
@@ -856,7 +868,7 @@ def main():
         t_thr = a.h2h_text_threads or (a.h2h_threads if explicit else 10)
         h2h["as_bedgraph_gz"] = host_to_host(subs[0], local_rank, par, sizes, nucp, nfrp, a.steps, t_sub, t_thr, as_text=True)
     e2e = None
-    if rank == 0 and world == 1 and a.cli_chunks > 0 and a.workload == "cfg3":
+    if a.full and rank == 0 and world == 1 and a.cli_chunks > 0 and a.workload == "cfg3":
         if ctx is not None:
             ctx.close()
             ctx = None

@@ -61,7 +61,7 @@ def test_two_ranks_run_the_host_to_host_pipeline_side_by_side():
 
 
 def test_single_rank_default_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--chunks", "3000", "--cpu-chunks", "32",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--chunks", "3000", "--cpu-chunks", "32",
                           "--cpu-literal-chunks", "16", "--h2h-sub", "1000", "--cli-chunks", "400"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][-1])
@@ -88,6 +88,25 @@ def test_single_rank_default_contract():
     assert e["real_inputs"]["occ_mbp_s"] > 0 and e["real_inputs"]["bam_gb"] > 0      # the same windows from a real .bam + .fa
     ts = d["roofline"]["traffic_source"]
     assert ts is None or set(("file", "collected_at_source_sha16", "current_source_sha16", "stale")) <= set(ts)
+
+
+def test_single_rank_plain_run_is_lean():
+    """a run without --full times the steps and prints the headline line; the legs that need work of their own (CPU baseline,
+    host-to-host, CLI end to end, shader-clock step, track download) are left out"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--chunks", "3000", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().split("\n") if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mbp/s through occ+nuc signal pipeline" and d["unit"] == "Mbp/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 3000 * 2120 * 2 / (d["ms_per_step"] * 2 / 1e3) / 1e6) < 1e-3 * d["value"]
+    assert d["kernels_ms_per_step"]["background"] > 0 and d["roofline"]["launches"] == 2
+    for k in ("cpu_baseline", "host_to_host", "cli_end_to_end", "multinomial_cov_sweep"):
+        assert k not in d, k
+    assert d["value_host_to_host"] is None and d["roofline"]["clock_ghz"] is None
+    assert d["host"]["download_5_tracks_and_candidates_s"] is None
 
 
 def test_cfg4_strong_scaling_two_ranks_share_device():
@@ -179,7 +198,7 @@ def test_cfg5_independent_samples_with_cov_sweep():
     """--workload cfg5 (BASELINE configs[4]): one independent sample per rank + the multinomial_cov tolerance sweep, 2 ranks on GPU 0"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29539", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg5", "--chunks", "1500", "--steps", "1",
-           "--warmup", "1", "--share-device", "--no-cpu-baseline"]
+           "--warmup", "1", "--share-device", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.strip().split("\n") if l.startswith("{")][-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run on the GPU box from the repo root:  bash tools/collect_profiles.sh [OUTDIR]
-# Kernel-trace statistics of the default bench, separate PMC passes (each under its own timeout), the default bench line.
+# Kernel-trace statistics of the default bench, separate PMC passes (each under its own timeout), the --full bench line.
 R=$PWD
 OUT=${1:-$R/gpurun_out/prof}
 case $OUT in /*) ;; *) OUT=$R/$OUT ;; esac
@@ -18,5 +18,5 @@ for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS
   dirs="$dirs /tmp/pmc$i"
 done
 python $R/tools/pmc_summarize.py $OUT/pmc_summary.csv $dirs
-cd $R && timeout 400 python bench.py > $OUT/bench_default.log 2>&1; grep '^{' $OUT/bench_default.log > $OUT/bench_default.json
+cd $R && timeout 400 python bench.py --full > $OUT/bench_default.log 2>&1; grep '^{' $OUT/bench_default.log > $OUT/bench_default.json
 tail -c 400 $OUT/bench_default.json
