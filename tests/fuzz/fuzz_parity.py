@@ -11,23 +11,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from helpers import assert_track, cancel_scale, golden  # noqa: E402
+from helpers import assert_track, call_peaks_stable, cancel_scale, golden  # noqa: E402
 from nucleoatac_amd import _lib as L  # noqa: E402
 from nucleoatac_amd.device import Context  # noqa: E402
 from nucleoatac_amd.packing import PackedChunks  # noqa: E402
 from nucleoatac_amd.synth import synth_occ_distributions, synth_size_distribution  # noqa: E402
 from oracle import natac_oracle as O  # noqa: E402
-
-
-def call_peaks_stable(sigvals, **kw):
-    """O.call_peaks with reduce_peaks' argsort made STABLE.  The reference sorts with numpy's default introsort
-    (pyatac/utils.py:61), so among peaks of exactly equal height -- occupancy saturated at 1.0 over a dense stretch -- its
-    visiting order depends on the numpy build; the device uses the stable order (ties: the later position first), which
-    is what the unstable sort returns whenever it does not permute equal keys."""
-    import unittest.mock as mock
-    real = np.argsort
-    with mock.patch.object(np, "argsort", lambda a, *x, **k: real(a, kind="stable")):
-        return O.call_peaks(sigvals, **kw)
 
 
 def one_round(ctx, rng, par, sizes, nucp, nfrp, rnd):

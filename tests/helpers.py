@@ -38,6 +38,18 @@ def golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
 
 
+def call_peaks_stable(sigvals, **kw):
+    """O.call_peaks (the oracle's restatement of utils.call_peaks) with reduce_peaks' argsort made STABLE.  The reference sorts
+    with numpy's default introsort (pyatac/utils.py:61), so among peaks of exactly equal height -- occupancy saturated at 1.0 over a
+    dense stretch -- its visiting order depends on the numpy build; the device uses the stable order (ties: the later position
+    first), which is what the unstable sort returns whenever it does not permute equal keys.  Fills NaNs of `sigvals` in place."""
+    import unittest.mock as mock
+    from oracle import natac_oracle as O
+    real = np.argsort
+    with mock.patch.object(np, "argsort", lambda a, *x, **k: real(a, kind="stable")):
+        return O.call_peaks(sigvals, **kw)
+
+
 def packed_from_golden(g, with_bias=True):
     """PackedChunks from a tests/golden/chunks_*.npz case (absolute l/n per chunk, reference bias track)."""
     nc = int(g["n_chunks"])
