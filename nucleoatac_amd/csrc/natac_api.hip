@@ -52,39 +52,79 @@ static int fail(int code, const char *fmt, ...) {
                         hipGetErrorString(e_), __FILE__, __LINE__);                                   \
     } while (0)
 
+static hipError_t pool_alloc(void **p, size_t bytes);     // the caching pool, defined below
+static void dev_free(void *p);
+
+// The owner of one pool block of n elements of T (move-only): the block goes back to the pool when the owner is reset or destroyed,
+// so whoever holds it must know the block's queued work has finished by then -- the context and the batch free theirs after draining
+// their stream, a call's temporaries live in a StreamTemps.  Converts to T * for launches and copies.
+template <class T>
+class PoolBuf {
+  public:
+    PoolBuf() = default;
+    PoolBuf(PoolBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    PoolBuf &operator=(PoolBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~PoolBuf() { reset(); }
+    void reset() { dev_free(p_); p_ = nullptr; n_ = 0; }
+    // the old block goes first; n == 0 takes one element.  On failure the owner stays empty.
+    hipError_t alloc(size_t n) {
+        reset();
+        if (n == 0) n = 1;
+        void *p = nullptr;
+        const hipError_t e = pool_alloc(&p, n * sizeof(T));
+        if (e == hipSuccess) { p_ = (T *)p; n_ = n; }
+        return e;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t size() const { return n_; }
+
+  private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
+template <class T>
+static int dev_alloc(PoolBuf<T> &buf, size_t n) {
+    HIPCHK(buf.alloc(n));
+    return NATAC_OK;
+}
+
 struct natac_ctx {
     int device = 0;
     hipStream_t stream = nullptr;    // every stage, uploads, drop-ins: one stream
     hipStream_t copy_stream = nullptr;   // natac_batch_format_fetch_begin: a finished result leaves the device while the next track is formatted
     hipDeviceProp_t prop;
     // constants
-    double *d_vmat = nullptr, *d_vmat_pad = nullptr, *d_srow = nullptr, *d_sizes = nullptr;   // d_vmat_pad: VMatDev::matp
-    double *d_lrt = nullptr;         // VMatDev::lrt (natac_lr_table), formed for model generation lrt_gen
+    PoolBuf<double> d_vmat, d_vmat_pad, d_srow, d_sizes;   // d_vmat_pad: VMatDev::matp
+    PoolBuf<double> d_lrt;           // VMatDev::lrt (natac_lr_table), formed for model generation lrt_gen
     long long lrt_gen = -1;
-    size_t lrt_cap = 0;
     int vlower = 0, vupper = 0, vw = 0, R = 0, W = 0, sizes_upper = 0;
     bool have_vmat = false, have_sizes = false, srow_dirty = true;
     bool vmat_zero = false, srow_zero = false;
     long long model_gen = 0;         // bumped by natac_set_vmat / natac_set_sizes
     // FFT background path: twiddles (once) and template spectra (per V-plot)
-    double *d_fft_tw = nullptr, *d_fft_k = nullptr;
-    double *d_fft_mtab = nullptr, *d_fft_swt = nullptr;   // natac_fft_edge_table_mfma (the edge pass of extended tiles)
+    PoolBuf<double> d_fft_tw, d_fft_k;
+    PoolBuf<double> d_fft_mtab, d_fft_swt;   // natac_fft_edge_table_mfma (the edge pass of extended tiles)
     bool bg_ext = true;              // NATAC_BG_EXT=0: no extended FFT tiles (A-B timing / validation of the edge pass)
     bool fft_dirty = true, bg_direct = false, occ_ordered = true, occ_zero_nfr = false;
     std::vector<double> h_sizes;
-    double *d_nucp = nullptr, *d_nfrp = nullptr, *d_alphas = nullptr;
+    PoolBuf<double> d_nucp, d_nfrp, d_alphas;
     int occ_upper = 0, n_alpha = 0, step = 0, halfstep = 0, flank = 0;
     double cutoff = 0;
     bool have_occ = false;
     int occ_zero_flags = 0;          // zero pattern of nuc_probs / nfr_probs (bits as in the MLE kernel)
     // fast occupancy path (natac_occ_fast.hpp): model tables + eligibility
-    double *d_occ_q4 = nullptr, *d_occ_rho = nullptr;
+    PoolBuf<double> d_occ_q4, d_occ_rho;
     int occ_nm = 0;
     bool occ_fast_ok = false, occ_force_general = false, occ_rn16 = false;
     double occ_b_floor = 0;          // see OccModelDev::b_floor
     // gaussian windows (cached by (M, sd))
-    double *d_win_nuc = nullptr, *d_win_occ = nullptr;
-    double *d_wb_occ = nullptr;      // block weights of natac_occ_smooth_blk for (win_occ_M, wb_step)
+    PoolBuf<double> d_win_nuc, d_win_occ;
+    PoolBuf<double> d_wb_occ;        // block weights of natac_occ_smooth_blk for (win_occ_M, wb_step)
     int wb_M = 0, wb_step = 0;
     int win_nuc_M = 0, win_occ_M = 0;
     double win_nuc_sd = -1, win_occ_sd = -1;
@@ -105,8 +145,8 @@ struct natac_ctx {
     struct Iv { int k; float t0, t1; };
     std::vector<Iv> ck_iv;
     // device-side track writer (natac_textz.hpp): power-of-ten table of the '%.12g' formatter, CRC-32 tables
-    natac_text::P10 *d_p10 = nullptr;
-    natac_deflate::CrcTables *d_crc = nullptr;
+    PoolBuf<natac_text::P10> d_p10;
+    PoolBuf<natac_deflate::CrcTables> d_crc;
 };
 
 struct natac_bam {
@@ -131,48 +171,49 @@ struct natac_batch {
     int bias_left = 0, bias_right = 0;
     std::vector<int> h_len;
     std::vector<long long> h_out_off, h_grid_off;
-    int *d_len = nullptr, *d_lpos = nullptr, *d_ilen = nullptr, *d_centre = nullptr, *d_status = nullptr;
-    long long *d_frag_off = nullptr, *d_bias_off = nullptr, *d_out_off = nullptr, *d_grid_off = nullptr;
-    double *d_bias = nullptr, *d_ebias = nullptr;
-    unsigned long long *d_occ_minkey = nullptr;   // natac_occ_smooth_blk: per-chunk minimum finite smoothed occupancy (double_key)
-    int *d_occ_nan = nullptr, n_tiles_os = 0, os_width = 0;
-    int2 *d_tiles_os = nullptr, *d_tiles1k = nullptr;
+    PoolBuf<int> d_len, d_lpos, d_ilen, d_centre, d_status;
+    PoolBuf<long long> d_frag_off, d_bias_off, d_out_off, d_grid_off;
+    PoolBuf<double> d_bias, d_ebias;
+    PoolBuf<unsigned long long> d_occ_minkey;   // natac_occ_smooth_blk: per-chunk minimum finite smoothed occupancy (double_key)
+    PoolBuf<int> d_occ_nan;
+    int n_tiles_os = 0, os_width = 0;
+    PoolBuf<int2> d_tiles_os, d_tiles1k;
     int n_tiles1k = 0;
-    int2 *d_tiles256 = nullptr, *d_tiles_bg = nullptr, *d_tiles_occ = nullptr, *d_ranges_occ = nullptr, *d_ranges256 = nullptr;
-    long long *d_tile256_first = nullptr;   // [nc + 1] first 256-base tile of every chunk (the candidates' way into d_ranges256)
-    int *d_order_occ = nullptr;      // natac_tile_heavy: {count, claims, list[HEAVY_CAP], flag bytes[n_tiles_occ]} of the occupancy tiles
+    PoolBuf<int2> d_tiles256, d_tiles_bg, d_tiles_occ, d_ranges_occ, d_ranges256;
+    PoolBuf<long long> d_tile256_first;   // [nc + 1] first 256-base tile of every chunk (the candidates' way into d_ranges256)
+    PoolBuf<int> d_order_occ;        // natac_tile_heavy: {count, claims, list[HEAVY_CAP], flag bytes[n_tiles_occ]} of the occupancy tiles
     int ranges256_w = -1;
     int ranges_occ_key[3] = {-1, -1, -1};   // (step, halfstep, flank) the occupancy tiles' fragment ranges were formed for
     int n_tiles256 = 0, n_tiles_bg = 0, n_tiles_occ = 0, bgG = 0;   // bgG: lanes' output count of the direct kernel, -1 = FFT tiles
     int grid_step = 0, grid_half = 0;
     // fast occupancy path: per-block sums of g_n / g_f, their tile table and the list of tiles left to natac_occ_mle
-    long long *d_blk_off = nullptr;
+    PoolBuf<long long> d_blk_off;
     long long total_blocks = 0;
-    double *d_gsum = nullptr;
-    int2 *d_tiles_gs = nullptr;
+    PoolBuf<double> d_gsum;
+    PoolBuf<int2> d_tiles_gs;
     int n_tiles_gs = 0, gs_Q = -1;
-    int *d_defer = nullptr;          // [0] = count, [1 ..] = tile indices
-    // occupancy peaks (natac_run_occ_peaks): OccPeak values + keep flags of the last search, per-chunk nuc_dist
-    double *d_opk_vals = nullptr, *d_nuc_dist = nullptr;
-    int *d_opk_keep = nullptr;
+    PoolBuf<int> d_defer;            // [0] = count, [1 ..] = tile indices
+    // occupancy peaks (natac_run_occ_peaks): OccPeak values + keep flags of the last search (opk_cap apart), per-chunk nuc_dist
+    PoolBuf<double> d_opk_vals, d_nuc_dist;
+    PoolBuf<int> d_opk_keep;
     long long opk_cap = 0, opk_n = -1;
     int nd_upper = 0;
-    double *d_track[NATAC_T_COUNT] = {nullptr};
-    double *d_grid[3] = {nullptr, nullptr, nullptr};
+    PoolBuf<double> d_track[NATAC_T_COUNT];
+    PoolBuf<double> d_grid[3];
     BatchOutputs out;
     bool ebias_fresh = false;
     // device-side candidate search
-    double *d_jitter = nullptr, *d_pk_out = nullptr;
-    long long *d_cap_off = nullptr, *d_pk_offs = nullptr;
-    int *d_slot = nullptr, *d_pk_count = nullptr, *d_pk_chunk = nullptr, *d_pk_pos = nullptr;
-    double *d_pk_big = nullptr;       // natac_peaks_chunk: global (sig, pos, state) lists of chunks with more maxima than fit in LDS
-    long long pk_big_slots = 0;
+    // (d_pk_chunk, d_pk_pos and the three columns of d_pk_out hold pk_cap candidates each)
+    PoolBuf<double> d_jitter, d_pk_out;
+    PoolBuf<long long> d_cap_off, d_pk_offs;
+    PoolBuf<int> d_slot, d_pk_count, d_pk_chunk, d_pk_pos;
+    PoolBuf<double> d_pk_big;         // natac_peaks_chunk: global (sig, pos, state) lists of chunks with more maxima than fit in LDS
     long long n_jitter = 0, pk_cap = 0, pk_n = -1, slot_total = 0;
     int pk_order = -1;
     bool pk_has_stats = false;
-    double *d_bnum = nullptr, *d_bcov = nullptr;   // per-base sum B V / sum B of the background kernel (candidate statistics)
-    unsigned char *d_fmt_out = nullptr;            // result of the last natac_batch_format_track (text or BGZF members)
-    std::vector<std::pair<unsigned char *, hipEvent_t>> fmt_pending;   // results on their way to the host (natac_batch_format_fetch_begin)
+    PoolBuf<double> d_bnum, d_bcov;                // per-base sum B V / sum B of the background kernel (candidate statistics)
+    PoolBuf<unsigned char> d_fmt_out;              // result of the last natac_batch_format_track (text or BGZF members)
+    std::vector<std::pair<PoolBuf<unsigned char>, hipEvent_t>> fmt_pending;   // results on their way to the host (natac_batch_format_fetch_begin)
     long long fmt_bytes = -1;
     // tabix records of that result (compress mode): runs of lines per leaf bin, member offsets, chromosome names
     std::vector<natac_textz::GroupRec> fmt_groups;
@@ -291,19 +332,42 @@ static void dev_free(void *p) {
 }
 
 template <class T>
-static int dev_alloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(pool_alloc((void **)p, n * sizeof(T)));
-    return NATAC_OK;
-}
-template <class T>
-static int dev_upload(natac_ctx *c, T **p, const T *src, size_t n) {
-    int rc = dev_alloc(p, n);
+static int dev_upload(natac_ctx *c, PoolBuf<T> &buf, const T *src, size_t n) {
+    int rc = dev_alloc(buf, n);
     if (rc) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(hipMemcpyAsync(buf, src, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     return NATAC_OK;
 }
+
+// The device temporaries of one call, freed when the scope ends.  The pool may hand a freed block to another context at once, so
+// a block may go back only once its stream has finished with it: on the normal path the call's last synchronisation has seen to
+// that; an early exit may leave kernels or copies queued, and the scope then drains the stream before it frees.
+class StreamTemps {
+  public:
+    explicit StreamTemps(natac_ctx *c) : c_(c) {}
+    ~StreamTemps() {
+        if (!bufs_.empty() && hipStreamQuery(c_->stream) != hipSuccess) (void)hipStreamSynchronize(c_->stream);
+    }
+    // as dev_alloc / dev_upload, into a block the scope owns (n == 0 takes one element of T)
+    template <class T>
+    int alloc(T **p, size_t n) {
+        bufs_.emplace_back();
+        int rc = dev_alloc(bufs_.back(), std::max<size_t>(n, 1) * sizeof(T));
+        *p = (T *)bufs_.back().get();
+        return rc;
+    }
+    template <class T>
+    int upload(T **p, const T *src, size_t n) {
+        int rc = alloc(p, n);
+        if (rc) return rc;
+        if (n) HIPCHK(hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, c_->stream));
+        return NATAC_OK;
+    }
+
+  private:
+    natac_ctx *c_;
+    std::vector<PoolBuf<unsigned char>> bufs_;
+};
 
 // pick the per-lane output count G of the background kernel: minimise idle lanes (sum of tile widths) with a small
 // penalty for the halo work of narrow tiles.
@@ -341,13 +405,8 @@ static void launch_candidates(natac_ctx *c, const ChunkTable &ct, const VMatDev 
     bool paired = per_wave && bnum && bcov && c->vlower >= 2 && (c->R & 1) == 0 && c->W >= 64 && !vm.has_zero && EW <= CANDP_STRIDE &&
                   !getenv("NATAC_CAND_FULL") && !getenv("NATAC_CAND_OLD");
     if (paired && (c->lrt_gen != c->model_gen || !c->d_lrt)) {      // log(V / s) of the current model, on the launch stream (natac_lr_table)
-        if (!c->d_lrt || c->lrt_cap < (size_t)c->R * c->W) {
-            dev_free(c->d_lrt);
-            c->d_lrt = nullptr;
-            c->lrt_cap = 0;
-            if (dev_alloc(&c->d_lrt, (size_t)c->R * c->W) == NATAC_OK) c->lrt_cap = (size_t)c->R * c->W;
-            else paired = false;                                     // out of memory: the per-cell kernel below needs no table
-        }
+        if (c->d_lrt.size() < (size_t)c->R * c->W && dev_alloc(c->d_lrt, (size_t)c->R * c->W) != NATAC_OK)
+            paired = false;                                          // out of memory: the per-cell kernel below needs no table
         if (paired) {
             hipLaunchKernelGGL(natac_lr_table, dim3((unsigned)((c->R * c->W + 255) / 256)), dim3(256), 0, c->stream, c->d_vmat, c->d_srow, c->R, c->W,
                                c->d_lrt);
@@ -398,33 +457,26 @@ static void launch_bg(natac_batch *b, const ChunkTable &ct, const VMatDev &vm) {
 static int ensure_text_tables(natac_ctx *c) {
     if (c->d_p10 && c->d_crc) return NATAC_OK;
     int rc;
-    if (!c->d_p10 && (rc = dev_upload(c, &c->d_p10, natac_text::H_P10, sizeof(natac_text::H_P10) / sizeof(natac_text::P10)))) return rc;
+    if (!c->d_p10 && (rc = dev_upload(c, c->d_p10, natac_text::H_P10, sizeof(natac_text::H_P10) / sizeof(natac_text::P10)))) return rc;
     if (!c->d_crc) {
         natac_deflate::CrcTables t;
         natac_deflate::crc_init(t);
-        if ((rc = dev_upload(c, &c->d_crc, &t, 1))) return rc;
+        if ((rc = dev_upload(c, c->d_crc, &t, 1))) return rc;
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return NATAC_OK;
 }
 
-struct TmpFree {               // frees device temporaries at scope exit
-    std::vector<void *> v;
-    ~TmpFree() { for (void *p : v) dev_free(p); }
-    template <class T> T *keep(T *p) { v.push_back((void *)p); return p; }
-};
-
 // exclusive scan of in[0..n) into out[0..n], out[n] = total (device arrays; n > 0).  The block sums are a temporary of the CALLER's scope
 // (`tmp`, freed after the caller's last synchronisation): freeing them here needed a stream synchronisation per scan -- six per formatted
 // track -- because the pool may hand a freed block to another context at once.
 template <class T>
-static int dev_scan(natac_ctx *c, const T *in, long long n, unsigned long long *out, TmpFree &tmp) {
+static int dev_scan(natac_ctx *c, const T *in, long long n, unsigned long long *out, StreamTemps &tmp) {
     using namespace natac_textz;
     const long long nblk = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
     unsigned long long *sums = nullptr;
-    int rc = dev_alloc(&sums, (size_t)nblk + 1);
+    int rc = tmp.alloc(&sums, (size_t)nblk + 1);
     if (rc) return rc;
-    tmp.keep(sums);
     hipLaunchKernelGGL((tz_scan_block_sums<T>), dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, sums);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nblk);
     hipLaunchKernelGGL((tz_scan_final<T>), dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, sums, out);
@@ -434,13 +486,12 @@ static int dev_scan(natac_ctx *c, const T *in, long long n, unsigned long long *
 }
 
 // the two scans over a track's runs (byte offsets and indices of its lines) in one pass over the length array (tz_scan2_*)
-static int dev_scan2(natac_ctx *c, const unsigned char *in, long long n, unsigned long long *out_sum, unsigned long long *out_cnt, TmpFree &tmp) {
+static int dev_scan2(natac_ctx *c, const unsigned char *in, long long n, unsigned long long *out_sum, unsigned long long *out_cnt, StreamTemps &tmp) {
     using namespace natac_textz;
     const long long nblk = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
     unsigned long long *sums = nullptr;
-    int rc = dev_alloc(&sums, 2 * ((size_t)nblk + 1));
+    int rc = tmp.alloc(&sums, 2 * ((size_t)nblk + 1));
     if (rc) return rc;
-    tmp.keep(sums);
     hipLaunchKernelGGL(tz_scan2_block_sums, dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, nblk, sums);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nblk);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums + nblk + 1, nblk);
@@ -458,8 +509,7 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     natac_ctx *c = b->ctx;
     int rc = ensure_text_tables(c);
     if (rc) return rc;
-    dev_free(b->d_fmt_out);
-    b->d_fmt_out = nullptr;
+    b->d_fmt_out.reset();
     b->fmt_bytes = -1;
     b->fmt_groups.clear();
     b->fmt_member_pos.clear();
@@ -486,7 +536,7 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     }
     const int line_cap = std::min<int>(MAX_LINE, (int)max_name + 2 * std::max(natac_text::digits_i64(max_coord), natac_text::digits_i64(min_coord)) + VTXT + 4);
     if (b->total_bp >= 0xffffffffLL) return fail(NATAC_E_ARG, "batch too long for the device writer (%lld bases)", b->total_bp);
-    TmpFree tmp;
+    StreamTemps tmp(c);
     char *d_names = nullptr;
     int *d_noff = nullptr, *d_cid = nullptr, *d_tc = nullptr, *d_C = nullptr, *d_hard = nullptr;
     long long *d_cs = nullptr, *d_line_off = nullptr;
@@ -494,34 +544,34 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     unsigned int *d_R = nullptr;
     unsigned char *d_len8 = nullptr, *d_text = nullptr;
 #define TRYF(x) do { if ((rc = (x)) != NATAC_OK) return rc; } while (0)
-    TRYF(dev_upload(c, &d_names, cat.data(), cat.size())); tmp.keep(d_names);
-    TRYF(dev_upload(c, &d_noff, noff.data(), noff.size())); tmp.keep(d_noff);
-    TRYF(dev_upload(c, &d_cid, chrom_id, (size_t)b->nc)); tmp.keep(d_cid);
-    TRYF(dev_upload(c, (long long **)&d_cs, (const long long *)chunk_start, (size_t)b->nc)); tmp.keep(d_cs);
-    TRYF(dev_alloc(&d_hard, 1)); tmp.keep(d_hard);
+    TRYF(tmp.upload(&d_names, cat.data(), cat.size()));
+    TRYF(tmp.upload(&d_noff, noff.data(), noff.size()));
+    TRYF(tmp.upload(&d_cid, chrom_id, (size_t)b->nc));
+    TRYF(tmp.upload(&d_cs, (const long long *)chunk_start, (size_t)b->nc));
+    TRYF(tmp.alloc(&d_hard, 1));
     HIPCHK(hipMemsetAsync(d_hard, 0, sizeof(int), c->stream));
     TextJob job;
     job.vals = d_vals; job.out_off = b->d_out_off; job.chunk_len = b->d_len; job.tiles = b->d_tiles256; job.ntiles = b->n_tiles256;
     job.chrom_id = d_cid; job.chunk_start = d_cs; job.names = d_names; job.name_off = d_noff; job.p10 = c->d_p10;
     job.write_zero = write_zero & 1; job.keep_before_nan = (write_zero >> 1) & 1;
     const int nt = b->n_tiles256;
-    TRYF(dev_alloc(&d_tc, (size_t)nt)); tmp.keep(d_tc);
-    TRYF(dev_alloc(&d_tb, (size_t)nt + 1)); tmp.keep(d_tb);
+    TRYF(tmp.alloc(&d_tc, (size_t)nt));
+    TRYF(tmp.alloc(&d_tb, (size_t)nt + 1));
     hipLaunchKernelGGL(tz_flags_count, dim3(nt), dim3(256), 0, c->stream, job, d_tc);
     TRYF(dev_scan(c, d_tc, (long long)nt, d_tb, tmp));
     unsigned long long nruns = 0;
     HIPCHK(hipMemcpyAsync(&nruns, d_tb + nt, sizeof nruns, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    TRYF(dev_alloc(&d_R, (size_t)nruns)); tmp.keep(d_R);
-    TRYF(dev_alloc(&d_C, (size_t)nruns)); tmp.keep(d_C);
+    TRYF(tmp.alloc(&d_R, (size_t)nruns));
+    TRYF(tmp.alloc(&d_C, (size_t)nruns));
     hipLaunchKernelGGL(tz_scatter_runs, dim3(nt), dim3(256), 0, c->stream, job, d_tb, d_R, d_C);
-    TRYF(dev_alloc(&d_len8, (size_t)nruns)); tmp.keep(d_len8);
+    TRYF(tmp.alloc(&d_len8, (size_t)nruns));
     const unsigned rb = (unsigned)((nruns + 255) / 256);
     unsigned long long *d_vtxt = nullptr;             // text of every run's value (tz_line_len -> tz_write_lines)
-    TRYF(dev_alloc(&d_vtxt, (size_t)nruns * (natac_textz::VTXT / 8))); tmp.keep(d_vtxt);
+    TRYF(tmp.alloc(&d_vtxt, (size_t)nruns * (natac_textz::VTXT / 8)));
     hipLaunchKernelGGL(tz_line_len, dim3(rb), dim3(256), 0, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_hard, d_vtxt);
-    TRYF(dev_alloc(&d_boff, (size_t)nruns + 1)); tmp.keep(d_boff);
-    TRYF(dev_alloc(&d_lidx, (size_t)nruns + 1)); tmp.keep(d_lidx);
+    TRYF(tmp.alloc(&d_boff, (size_t)nruns + 1));
+    TRYF(tmp.alloc(&d_lidx, (size_t)nruns + 1));
     TRYF(dev_scan2(c, d_len8, (long long)nruns, d_boff, d_lidx, tmp));
     unsigned long long n_text = 0, nlines = 0;
     int hard = 0;
@@ -534,33 +584,36 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     if (n_lines) *n_lines = (int64_t)nlines;
     if (n_hard) *n_hard = hard;
     if (n_text == 0) { b->fmt_bytes = 0; if (n_bytes) *n_bytes = 0; return NATAC_OK; }
-    TRYF(dev_alloc(&d_text, (size_t)n_text + 64));
-    TRYF(dev_alloc(&d_line_off, (size_t)nlines + 1)); tmp.keep(d_line_off);
+    if (compress) {
+        TRYF(tmp.alloc(&d_text, (size_t)n_text + 64));
+    } else {           // the text is the result: written in place (a failed call leaves fmt_bytes at -1)
+        TRYF(dev_alloc(b->d_fmt_out, (size_t)n_text + 64));
+        d_text = b->d_fmt_out;
+    }
+    TRYF(tmp.alloc(&d_line_off, (size_t)nlines + 1));
     int *d_lcid = nullptr;
     long long *d_lbeg = nullptr, *d_lend = nullptr;
     if (compress) {
-        TRYF(dev_alloc(&d_lcid, (size_t)nlines)); tmp.keep(d_lcid);
-        TRYF(dev_alloc(&d_lbeg, (size_t)nlines)); tmp.keep(d_lbeg);
-        TRYF(dev_alloc(&d_lend, (size_t)nlines)); tmp.keep(d_lend);
+        TRYF(tmp.alloc(&d_lcid, (size_t)nlines));
+        TRYF(tmp.alloc(&d_lbeg, (size_t)nlines));
+        TRYF(tmp.alloc(&d_lend, (size_t)nlines));
     }
     hipLaunchKernelGGL(tz_write_lines, dim3(rb), dim3(256), (size_t)256 * line_cap + 32, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_boff, d_lidx, d_vtxt, d_text,
                        d_line_off, d_lcid, d_lbeg, d_lend);
     if (!compress) {
         hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { dev_free(d_text); return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e)); }
-        b->d_fmt_out = d_text;
+        if (e != hipSuccess) return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e));
         b->fmt_bytes = (long long)n_text;
         if (n_bytes) *n_bytes = (int64_t)n_text;
         return NATAC_OK;
     }
-    tmp.keep(d_text);
     namespace nd = natac_deflate;
     const long long nblk = ((long long)n_text + nd::BLK - 1) / nd::BLK;
     unsigned int *d_hist = nullptr, *d_sizes = nullptr;
     nd::Codes *d_codes = nullptr;
-    unsigned char *d_regions = nullptr, *d_out = nullptr;
+    unsigned char *d_regions = nullptr;
     unsigned long long *d_pos = nullptr;
-    TRYF(dev_alloc(&d_hist, (size_t)nd::NLL + nd::ND)); tmp.keep(d_hist);
+    TRYF(tmp.alloc(&d_hist, (size_t)nd::NLL + nd::ND));
     HIPCHK(hipMemsetAsync(d_hist, 0, (nd::NLL + nd::ND) * sizeof(unsigned int), c->stream));
     // line segments per member -> offsets of the per-segment records pass A of the emit kernel leaves for its pass B
     unsigned int *d_nseg = nullptr;
@@ -568,14 +621,14 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     unsigned int *d_stage = nullptr;
     unsigned short *d_segbits = nullptr;
     long long *d_k0 = nullptr;
-    TRYF(dev_alloc(&d_nseg, (size_t)nblk)); tmp.keep(d_nseg);
-    TRYF(dev_alloc(&d_segbase, (size_t)nblk + 1)); tmp.keep(d_segbase);
-    TRYF(dev_alloc(&d_k0, (size_t)nblk)); tmp.keep(d_k0);
+    TRYF(tmp.alloc(&d_nseg, (size_t)nblk));
+    TRYF(tmp.alloc(&d_segbase, (size_t)nblk + 1));
+    TRYF(tmp.alloc(&d_k0, (size_t)nblk));
     hipLaunchKernelGGL(tz_member_nseg, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, c->stream, d_line_off, (long long)nlines,
                        (long long)n_text, nblk, d_nseg, d_k0);
     TRYF(dev_scan(c, d_nseg, nblk, d_segbase, tmp));
-    TRYF(dev_alloc(&d_segbits, (size_t)nlines + (size_t)nblk + 64)); tmp.keep(d_segbits);  // every line once + one more per straddled member border
-    TRYF(dev_alloc(&d_stage, (size_t)nblk * STAGE_WORDS)); tmp.keep(d_stage);             // the lines' finished bits between the emit kernel's two passes
+    TRYF(tmp.alloc(&d_segbits, (size_t)nlines + (size_t)nblk + 64));  // every line once + one more per straddled member border
+    TRYF(tmp.alloc(&d_stage, (size_t)nblk * STAGE_WORDS));             // the lines' finished bits between the emit kernel's two passes
     // token histogram of a sample of the members (every member of a small batch): natac_deflate.hpp, sample_stride
     const int stride = nd::sample_stride(nblk);
     const long long counted = (nblk + stride - 1) / stride;
@@ -588,11 +641,11 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     nd::finish_hist(hist, hist + nd::NLL, counted, stride);      // one end-of-block per counted member; a code for every symbol when sampled
     nd::Codes codes;
     if (!nd::build_codes(hist, hist + nd::NLL, codes)) return fail(NATAC_E_ARG, "format_track: Huffman table description too long");
-    TRYF(dev_upload(c, &d_codes, &codes, 1)); tmp.keep(d_codes);
-    TRYF(dev_alloc(&d_regions, (size_t)nblk * nd::REGION)); tmp.keep(d_regions);
+    TRYF(tmp.upload(&d_codes, &codes, 1));
+    TRYF(tmp.alloc(&d_regions, (size_t)nblk * nd::REGION));
     HIPCHK(hipMemsetAsync(d_regions, 0, (size_t)nblk * nd::REGION, c->stream));
-    TRYF(dev_alloc(&d_sizes, (size_t)nblk)); tmp.keep(d_sizes);
-    TRYF(dev_alloc(&d_pos, (size_t)nblk + 1)); tmp.keep(d_pos);
+    TRYF(tmp.alloc(&d_sizes, (size_t)nblk));
+    TRYF(tmp.alloc(&d_pos, (size_t)nblk + 1));
     const size_t lds_emit = 65536 + ((sizeof(nd::Codes) + 15) & ~(size_t)15);
     hipLaunchKernelGGL(tz_emit_members, dim3((unsigned)nblk), dim3(TZ_THREADS), lds_emit, c->stream, d_text, (long long)n_text, d_line_off,
                        (long long)nlines, d_nseg, d_k0, d_segbase, d_stage, d_segbits, d_codes, c->d_crc, d_regions, d_sizes);
@@ -606,15 +659,15 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
         long long *d_first = nullptr;
         GroupRec *d_rec = nullptr;
         const unsigned lb = (unsigned)((nlines + 255) / 256);
-        TRYF(dev_alloc(&d_gf, (size_t)nlines)); tmp.keep(d_gf);
-        TRYF(dev_alloc(&d_gidx, (size_t)nlines + 1)); tmp.keep(d_gidx);
+        TRYF(tmp.alloc(&d_gf, (size_t)nlines));
+        TRYF(tmp.alloc(&d_gidx, (size_t)nlines + 1));
         hipLaunchKernelGGL(tz_group_flags, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_lcid, d_lbeg, d_lend, d_gf);
         TRYF(dev_scan(c, d_gf, (long long)nlines, d_gidx, tmp));
         unsigned long long ngroups = 0;
         HIPCHK(hipMemcpyAsync(&ngroups, d_gidx + nlines, sizeof ngroups, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        TRYF(dev_alloc(&d_first, (size_t)ngroups)); tmp.keep(d_first);
-        TRYF(dev_alloc(&d_rec, (size_t)ngroups)); tmp.keep(d_rec);
+        TRYF(tmp.alloc(&d_first, (size_t)ngroups));
+        TRYF(tmp.alloc(&d_rec, (size_t)ngroups));
         hipLaunchKernelGGL(tz_group_starts, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_gf, d_gidx, d_first);
         hipLaunchKernelGGL(tz_group_records, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, c->stream, (long long)ngroups, d_first,
                            (long long)nlines, d_lcid, d_lbeg, d_lend, d_line_off, (long long)n_text, d_rec);
@@ -623,13 +676,12 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     const unsigned long long total = b->fmt_member_pos[(size_t)nblk];
-    TRYF(dev_alloc(&d_out, (size_t)total + 64));
-    hipLaunchKernelGGL(tz_compact, dim3((unsigned)nblk), dim3(256), 0, c->stream, d_regions, d_sizes, d_pos, d_out);
+    TRYF(dev_alloc(b->d_fmt_out, (size_t)total + 64));
+    hipLaunchKernelGGL(tz_compact, dim3((unsigned)nblk), dim3(256), 0, c->stream, d_regions, d_sizes, d_pos, b->d_fmt_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { dev_free(d_out); return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e));
 #undef TRYF
-    b->d_fmt_out = d_out;
     b->fmt_bytes = (long long)total;
     if (n_bytes) *n_bytes = (int64_t)total;
     return NATAC_OK;
@@ -712,12 +764,6 @@ void natac_ctx_destroy(natac_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     prof_collect(c);
-    dev_free(c->d_vmat); dev_free(c->d_vmat_pad); dev_free(c->d_srow); dev_free(c->d_sizes); dev_free(c->d_lrt);
-    dev_free(c->d_nucp); dev_free(c->d_nfrp); dev_free(c->d_alphas);
-    dev_free(c->d_win_nuc); dev_free(c->d_win_occ); dev_free(c->d_wb_occ);
-    dev_free(c->d_fft_tw); dev_free(c->d_fft_k); dev_free(c->d_fft_mtab); dev_free(c->d_fft_swt);
-    dev_free(c->d_occ_q4); dev_free(c->d_occ_rho);
-    dev_free(c->d_p10); dev_free(c->d_crc);
     if (c->t0) (void)hipEventDestroy(c->t0);
     if (c->t1) (void)hipEventDestroy(c->t1);
     if (c->ck_stream) (void)hipStreamDestroy(c->ck_stream);
@@ -725,7 +771,7 @@ void natac_ctx_destroy(natac_ctx *c) {
     if (c->d_ck) (void)hipFree(c->d_ck);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;      // the pool blocks go back with the members
 }
 
 int natac_ctx_sync(natac_ctx *c) {
@@ -761,18 +807,14 @@ int natac_set_vmat(natac_ctx *c, const double *mat, int lower, int upper, int w)
     if (lower < 0 || upper <= lower || w < 0) return fail(NATAC_E_ARG, "bad vmat geometry lower=%d upper=%d w=%d", lower, upper, w);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
-    dev_free(c->d_vmat);
-    c->d_vmat = nullptr;
     c->vlower = lower; c->vupper = upper; c->vw = w; c->R = upper - lower; c->W = 2 * w + 1;
-    int rc = dev_upload(c, &c->d_vmat, mat, (size_t)c->R * c->W);
+    int rc = dev_upload(c, c->d_vmat, mat, (size_t)c->R * c->W);
     if (rc) return rc;
     {   // the same rows between VPAD zero columns (natac_frag_gather)
         const int WP = c->W + 2 * VPAD;
         std::vector<double> padded((size_t)c->R * WP, 0.0);
         for (int r = 0; r < c->R; ++r) std::copy(mat + (size_t)r * c->W, mat + (size_t)(r + 1) * c->W, padded.begin() + (size_t)r * WP + VPAD);
-        dev_free(c->d_vmat_pad);
-        c->d_vmat_pad = nullptr;
-        if ((rc = dev_upload(c, &c->d_vmat_pad, padded.data(), padded.size()))) return rc;
+        if ((rc = dev_upload(c, c->d_vmat_pad, padded.data(), padded.size()))) return rc;
         HIPCHK(sync_all(c));   // `padded` is a local
     }
     c->vmat_zero = false;
@@ -789,9 +831,7 @@ int natac_set_sizes(natac_ctx *c, const double *sizes, int upper) {
     if (!c || !sizes || upper <= 0) return fail(NATAC_E_ARG, "bad argument");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
-    dev_free(c->d_sizes);
-    c->d_sizes = nullptr;
-    int rc = dev_upload(c, &c->d_sizes, sizes, (size_t)upper);
+    int rc = dev_upload(c, c->d_sizes, sizes, (size_t)upper);
     if (rc) return rc;
     c->h_sizes.assign(sizes, sizes + upper);
     HIPCHK(sync_all(c));
@@ -812,12 +852,11 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
     if (step % 2 == 0) step -= 1; /* Occupancy.py:190-191 */
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
-    dev_free(c->d_nucp); dev_free(c->d_nfrp); dev_free(c->d_alphas);
-    c->d_nucp = c->d_nfrp = c->d_alphas = nullptr;
+    c->d_nucp.reset(); c->d_nfrp.reset(); c->d_alphas.reset();
     int rc;
-    if ((rc = dev_upload(c, &c->d_nucp, nuc_probs, (size_t)upper))) return rc;
-    if ((rc = dev_upload(c, &c->d_nfrp, nfr_probs, (size_t)upper))) return rc;
-    if ((rc = dev_upload(c, &c->d_alphas, alphas, (size_t)n_alpha))) return rc;
+    if ((rc = dev_upload(c, c->d_nucp, nuc_probs, (size_t)upper))) return rc;
+    if ((rc = dev_upload(c, c->d_nfrp, nfr_probs, (size_t)upper))) return rc;
+    if ((rc = dev_upload(c, c->d_alphas, alphas, (size_t)n_alpha))) return rc;
     HIPCHK(sync_all(c));
     {
         int zf = 0;
@@ -842,8 +881,7 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
         // step up to 9 (kernel instantiations; the CLI's --step), a window of at least one step (any --flank: a whole number of
         // step-blocks + the first (2 flank + 1) % step bases of the next one), and a probability range that keeps four likelihood
         // factors inside the fp64 range
-        dev_free(c->d_occ_q4); dev_free(c->d_occ_rho);
-        c->d_occ_q4 = c->d_occ_rho = nullptr;
+        c->d_occ_q4.reset(); c->d_occ_rho.reset();
         bool ok = n_alpha <= OD_NA && step <= 9 && 2 * flank + 1 >= step;
         for (int a = 0; ok && a < n_alpha; ++a) ok = alphas[a] >= 0.0 && alphas[a] <= 1.0 && (a == 0 || alphas[a] > alphas[a - 1]);
         double rmin = std::numeric_limits<double>::infinity(), rmax = 0.0, pmin = 1.0;
@@ -891,8 +929,8 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
                 q4[(size_t)4 * (j >> 1) + (j & 1)] = nuc_probs[j];
                 q4[(size_t)4 * (j >> 1) + 2 + (j & 1)] = nfr_probs[j];
             }
-            if ((rc = dev_upload(c, &c->d_occ_q4, q4.data(), q4.size()))) return rc;
-            if ((rc = dev_upload(c, &c->d_occ_rho, rho.data(), rho.size()))) return rc;
+            if ((rc = dev_upload(c, c->d_occ_q4, q4.data(), q4.size()))) return rc;
+            if ((rc = dev_upload(c, c->d_occ_rho, rho.data(), rho.size()))) return rc;
             HIPCHK(sync_all(c));
         }
     }
@@ -905,9 +943,7 @@ static int ensure_srow(natac_ctx *c) {
     if (!c->have_sizes) return fail(NATAC_E_STATE, "natac_set_sizes has not been called");
     if (c->sizes_upper < c->vupper) return fail(NATAC_E_ARG, "sizes cover [0,%d) but vmat.upper is %d", c->sizes_upper, c->vupper);
     if (!c->srow_dirty) return NATAC_OK;
-    dev_free(c->d_srow);
-    c->d_srow = nullptr;
-    int rc = dev_alloc(&c->d_srow, (size_t)c->R);
+    int rc = dev_alloc(c->d_srow, (size_t)c->R);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(c->d_srow, c->d_sizes + c->vlower, (size_t)c->R * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     c->srow_zero = false;
@@ -974,10 +1010,8 @@ static int build_tiles_bg(natac_batch *b, int TV, bool ext_ok) {
             }
         }
     }
-    dev_free(b->d_tiles_bg);
-    b->d_tiles_bg = nullptr;
     b->n_tiles_bg = (int)tiles.size();
-    int rc = dev_upload(b->ctx, &b->d_tiles_bg, tiles.data(), tiles.size());
+    int rc = dev_upload(b->ctx, b->d_tiles_bg, tiles.data(), tiles.size());
     if (rc) return rc;
     HIPCHK(sync_all(b->ctx));  // `tiles` is a local
     return NATAC_OK;
@@ -998,21 +1032,18 @@ static int ensure_fft(natac_ctx *c) {
             int k = 0; double dlt = 0.0;
             if (sscanf(e, "%d:%lf", &k, &dlt) == 2 && k >= 0 && k < natac::FFT_N) tw[2 * (size_t)k] += dlt;
         }
-        if ((rc = dev_upload(c, &c->d_fft_tw, tw.data(), tw.size()))) return rc;
+        if ((rc = dev_upload(c, c->d_fft_tw, tw.data(), tw.size()))) return rc;
         HIPCHK(sync_all(c));
     }
     if (!c->fft_dirty) return NATAC_OK;
     HIPCHK(sync_all(c));
-    dev_free(c->d_fft_k);
-    c->d_fft_k = nullptr;
     const int npair = (c->R + 1) / 2;
-    if ((rc = dev_alloc(&c->d_fft_k, (size_t)npair * 2 * natac::FFT_N))) return rc;
+    if ((rc = dev_alloc(c->d_fft_k, (size_t)npair * 2 * natac::FFT_N))) return rc;
     hipLaunchKernelGGL(natac_fft_template, dim3(npair), dim3(64), 0, c->stream, c->d_vmat, c->d_srow, c->R, c->W, c->d_fft_tw, c->d_fft_k);
     if (c->W >= natac::FFT_EXT) {
-        dev_free(c->d_fft_mtab); dev_free(c->d_fft_swt);
-        c->d_fft_mtab = c->d_fft_swt = nullptr;
+        c->d_fft_mtab.reset(); c->d_fft_swt.reset();
         const int NJ = (c->R + 3) / 4;
-        if ((rc = dev_alloc(&c->d_fft_mtab, (size_t)2 * NJ * 64)) || (rc = dev_alloc(&c->d_fft_swt, (size_t)4 * NJ))) return rc;
+        if ((rc = dev_alloc(c->d_fft_mtab, (size_t)2 * NJ * 64)) || (rc = dev_alloc(c->d_fft_swt, (size_t)4 * NJ))) return rc;
         hipLaunchKernelGGL(natac_fft_edge_table_mfma, dim3((2 * NJ * 64 + 255) / 256), dim3(256), 0, c->stream, c->d_vmat, c->d_srow, c->R, c->W, NJ,
                            c->d_fft_mtab, c->d_fft_swt);
     }
@@ -1021,11 +1052,9 @@ static int ensure_fft(natac_ctx *c) {
     return NATAC_OK;
 }
 
-static int ensure_window(natac_ctx *c, double **slot, int *slotM, double *slotsd, int M, double sd, double *slotsum = nullptr) {
-    if (*slot && *slotM == M && *slotsd == sd) return NATAC_OK;
+static int ensure_window(natac_ctx *c, PoolBuf<double> &slot, int *slotM, double *slotsd, int M, double sd, double *slotsum = nullptr) {
+    if (slot && *slotM == M && *slotsd == sd) return NATAC_OK;
     HIPCHK(sync_all(c));
-    dev_free(*slot);
-    *slot = nullptr;
     // scipy.signal.gaussian(M, sd): exp(-0.5 (n/sd)^2), n = arange(M) - (M-1)/2   (pyatac/utils.py:40)
     std::vector<double> w((size_t)M);
     for (int i = 0; i < M; ++i) {
@@ -1053,7 +1082,7 @@ static int run_exp_bias(natac_batch *b, hipStream_t st, bool from_occ) {
     if (from_occ && b->ebias_fresh) { b->ebias_fresh = false; return NATAC_OK; }
     b->ebias_fresh = !from_occ;
     int rc;
-    if (!b->d_ebias && (rc = dev_alloc(&b->d_ebias, (size_t)b->nb))) return rc;
+    if (!b->d_ebias && (rc = dev_alloc(b->d_ebias, (size_t)b->nb))) return rc;
     const int blocks = (int)std::min<long long>((b->nb + 255) / 256, 16384);
     hipLaunchKernelGGL(natac_exp_bias, dim3(blocks), dim3(256), 0, st, b->d_bias, b->d_ebias, b->nb);
     return NATAC_OK;
@@ -1083,7 +1112,7 @@ static OccModelDev make_occ(natac_ctx *c) {
     return o;
 }
 
-static int build_tiles(natac_batch *b, int width, int2 **d_out, int *n_out, bool grid_units = false, int step = 1, int half = 0) {
+static int build_tiles(natac_batch *b, int width, PoolBuf<int2> &d_out, int *n_out, bool grid_units = false, int step = 1, int half = 0) {
     std::vector<int2> tiles;
     tiles.reserve((size_t)(b->total_bp / std::max(1, width)) + b->nc);
     for (int i = 0; i < b->nc; ++i) {
@@ -1091,8 +1120,6 @@ static int build_tiles(natac_batch *b, int width, int2 **d_out, int *n_out, bool
         if (grid_units) n = (b->h_len[i] > half) ? (b->h_len[i] - half + step - 1) / step : 0;
         for (int x = 0; x < n; x += width) tiles.push_back(make_int2(i, x));
     }
-    dev_free(*d_out);
-    *d_out = nullptr;
     *n_out = (int)tiles.size();
     int rc = dev_upload(b->ctx, d_out, tiles.data(), tiles.size());
     if (rc) return rc;
@@ -1128,35 +1155,41 @@ int natac_batch_create(natac_ctx *c, int32_t nc, const int32_t *chunk_len, const
     }
     b->total_bp = b->h_out_off[nc];
     b->nb = bias_off ? bias_off[nc] : 0;
-    int rc = NATAC_OK;
-#define TRY(x) do { if ((rc = (x)) != NATAC_OK) { natac_batch_free(b); return rc; } } while (0)
-    TRY(dev_upload(c, &b->d_len, chunk_len, (size_t)nc));
-    TRY(dev_upload(c, (long long **)&b->d_frag_off, (const long long *)frag_off, (size_t)nc + 1));
-    TRY(dev_upload(c, &b->d_lpos, frag_lpos, (size_t)nf));
-    TRY(dev_upload(c, &b->d_ilen, frag_ilen, (size_t)nf));
-    TRY(dev_alloc(&b->d_centre, (size_t)nf));
-    TRY(dev_upload(c, &b->d_out_off, b->h_out_off.data(), (size_t)nc + 1));
-    if (bias_off) {
-        TRY(dev_upload(c, (long long **)&b->d_bias_off, (const long long *)bias_off, (size_t)nc + 1));
-        if (bias_log) TRY(dev_upload(c, &b->d_bias, bias_log, (size_t)b->nb));
-        else TRY(dev_alloc(&b->d_bias, (size_t)b->nb));           // filled on the device (natac_batch_create_from_seq)
+    // what fails after an upload was queued leaves the cleanup to natac_batch_free: it drains the stream before the blocks go back
+    auto upload = [&]() -> int {
+        int rc;
+        if ((rc = dev_upload(c, b->d_len, chunk_len, (size_t)nc)) ||
+            (rc = dev_upload(c, b->d_frag_off, (const long long *)frag_off, (size_t)nc + 1)) ||
+            (rc = dev_upload(c, b->d_lpos, frag_lpos, (size_t)nf)) || (rc = dev_upload(c, b->d_ilen, frag_ilen, (size_t)nf)) ||
+            (rc = dev_alloc(b->d_centre, (size_t)nf)) || (rc = dev_upload(c, b->d_out_off, b->h_out_off.data(), (size_t)nc + 1)))
+            return rc;
+        if (bias_off) {
+            if ((rc = dev_upload(c, b->d_bias_off, (const long long *)bias_off, (size_t)nc + 1))) return rc;
+            if (bias_log) rc = dev_upload(c, b->d_bias, bias_log, (size_t)b->nb);
+            else rc = dev_alloc(b->d_bias, (size_t)b->nb);           // filled on the device (natac_batch_create_from_seq)
+            if (rc) return rc;
+        }
+        if ((rc = dev_alloc(b->d_status, (size_t)nc))) return rc;
+        hipError_t e = hipMemsetAsync(b->d_status, 0, (size_t)nc * sizeof(int), c->stream);
+        if (e != hipSuccess) return fail(NATAC_E_HIP, "memset: %s", hipGetErrorString(e));
+        if (nf > 0) {
+            int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
+            hipLaunchKernelGGL(natac_frag_centres, dim3(blocks), dim3(256), 0, c->stream, b->d_lpos, b->d_ilen, b->d_centre, nf);
+        }
+        if ((rc = build_tiles(b, 256, b->d_tiles256, &b->n_tiles256))) return rc;
+        {
+            std::vector<long long> first((size_t)nc + 1, 0);
+            for (int i = 0; i < nc; ++i) first[(size_t)i + 1] = first[i] + (chunk_len[i] + 255) / 256;
+            if ((rc = dev_upload(c, b->d_tile256_first, first.data(), first.size()))) return rc;
+        }
+        e = hipStreamSynchronize(c->stream);  // host buffers may be released by the caller after return
+        if (e != hipSuccess) return fail(NATAC_E_HIP, "upload: %s", hipGetErrorString(e));
+        return NATAC_OK;
+    };
+    if (int rc = upload()) {
+        natac_batch_free(b);
+        return rc;
     }
-    TRY(dev_alloc(&b->d_status, (size_t)nc));
-    hipError_t e = hipMemsetAsync(b->d_status, 0, (size_t)nc * sizeof(int), c->stream);
-    if (e != hipSuccess) { natac_batch_free(b); return fail(NATAC_E_HIP, "memset: %s", hipGetErrorString(e)); }
-    if (nf > 0) {
-        int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
-        hipLaunchKernelGGL(natac_frag_centres, dim3(blocks), dim3(256), 0, c->stream, b->d_lpos, b->d_ilen, b->d_centre, nf);
-    }
-    TRY(build_tiles(b, 256, &b->d_tiles256, &b->n_tiles256));
-    {
-        std::vector<long long> first((size_t)nc + 1, 0);
-        for (int i = 0; i < nc; ++i) first[(size_t)i + 1] = first[i] + (chunk_len[i] + 255) / 256;
-        TRY(dev_upload(c, &b->d_tile256_first, first.data(), first.size()));
-    }
-    e = hipStreamSynchronize(c->stream);  // host buffers may be released by the caller after return
-    if (e != hipSuccess) { natac_batch_free(b); return fail(NATAC_E_HIP, "upload: %s", hipGetErrorString(e)); }
-#undef TRY
     *out = b;
     return NATAC_OK;
 }
@@ -1177,14 +1210,15 @@ int natac_batch_create_from_seq(natac_ctx *c, int32_t nc, const int32_t *chunk_l
     int rc = natac_batch_create(c, nc, chunk_len, frag_off, frag_lpos, frag_ilen, boff.data(), nullptr, bias_left, bias_right, out);
     if (rc) return rc;
     natac_batch *b = *out;
+    StreamTemps tmp(c);
     unsigned char *d_s = nullptr, *d_n = nullptr;
     long long *d_so = nullptr;
     double *d_p = nullptr;
     const size_t nseq = (size_t)seq_off[nc];
-    if ((rc = dev_upload(c, &d_s, (const unsigned char *)seq, nseq)) == NATAC_OK &&
-        (rc = dev_upload(c, (long long **)&d_so, (const long long *)seq_off, (size_t)nc + 1)) == NATAC_OK &&
-        (rc = dev_upload(c, &d_n, (const unsigned char *)nucleotides, (size_t)nrow)) == NATAC_OK &&
-        (rc = dev_upload(c, &d_p, log_pwm, (size_t)nrow * K)) == NATAC_OK) {
+    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, nseq)) == NATAC_OK &&
+        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)nc + 1)) == NATAC_OK &&
+        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) == NATAC_OK &&
+        (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)) == NATAC_OK) {
         int maxlen = 0;
         for (int i = 0; i < nc; ++i) maxlen = std::max(maxlen, chunk_len[i] + bias_left + bias_right);
         const unsigned gx = (unsigned)std::min(16, (maxlen + 1023) / 1024);
@@ -1194,7 +1228,6 @@ int natac_batch_create_from_seq(natac_ctx *c, int32_t nc, const int32_t *chunk_l
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) rc = fail(NATAC_E_HIP, "pwm score: %s", hipGetErrorString(e));
     }
-    dev_free(d_s); dev_free(d_so); dev_free(d_n); dev_free(d_p);
     if (rc) { natac_batch_free(b); *out = nullptr; }
     return rc;
 }
@@ -1204,23 +1237,8 @@ void natac_batch_free(natac_batch *b) {
     (void)hipSetDevice(b->ctx->device);
     (void)sync_all(b->ctx);
     prof_collect(b->ctx);
-    dev_free(b->d_len); dev_free(b->d_lpos); dev_free(b->d_ilen); dev_free(b->d_centre); dev_free(b->d_status);
-    dev_free(b->d_frag_off); dev_free(b->d_bias_off); dev_free(b->d_out_off); dev_free(b->d_grid_off); dev_free(b->d_bias);
-    dev_free(b->d_ebias);
-    dev_free(b->d_occ_minkey); dev_free(b->d_occ_nan); dev_free(b->d_tiles_os); dev_free(b->d_tiles1k);
-    dev_free(b->d_tiles256); dev_free(b->d_tiles_bg); dev_free(b->d_tiles_occ); dev_free(b->d_ranges_occ); dev_free(b->d_ranges256);
-    dev_free(b->d_tile256_first);
-    dev_free(b->d_order_occ);
-    dev_free(b->d_jitter); dev_free(b->d_pk_out); dev_free(b->d_cap_off);
-    dev_free(b->d_pk_offs); dev_free(b->d_slot); dev_free(b->d_pk_count); dev_free(b->d_pk_chunk); dev_free(b->d_pk_pos);
-    dev_free(b->d_pk_big);
-    for (int i = 0; i < NATAC_T_COUNT; ++i) dev_free(b->d_track[i]);
-    dev_free(b->d_bnum); dev_free(b->d_bcov); dev_free(b->d_fmt_out);
     (void)fmt_pending_wait(b);
-    dev_free(b->d_blk_off); dev_free(b->d_gsum); dev_free(b->d_tiles_gs); dev_free(b->d_defer);
-    dev_free(b->d_opk_vals); dev_free(b->d_nuc_dist); dev_free(b->d_opk_keep);
-    for (int i = 0; i < 3; ++i) dev_free(b->d_grid[i]);
-    delete b;
+    delete b;      // the pool blocks go back with the members
 }
 
 int natac_batch_release_outputs(natac_batch *b) {
@@ -1229,13 +1247,11 @@ int natac_batch_release_outputs(natac_batch *b) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
     prof_collect(c);
-    for (int i = 0; i < NATAC_T_COUNT; ++i) { dev_free(b->d_track[i]); b->d_track[i] = nullptr; }
-    for (int i = 0; i < 3; ++i) { dev_free(b->d_grid[i]); b->d_grid[i] = nullptr; }
-    dev_free(b->d_bnum); dev_free(b->d_bcov); dev_free(b->d_gsum); dev_free(b->d_pk_out);
-    dev_free(b->d_pk_chunk); dev_free(b->d_pk_pos); dev_free(b->d_opk_vals); dev_free(b->d_opk_keep); dev_free(b->d_nuc_dist);
-    b->d_bnum = b->d_bcov = b->d_gsum = b->d_pk_out = b->d_opk_vals = b->d_nuc_dist = nullptr;
-    b->d_pk_chunk = b->d_pk_pos = b->d_opk_keep = nullptr;
-    dev_free(b->d_fmt_out); b->d_fmt_out = nullptr; b->fmt_bytes = -1;
+    for (auto &t : b->d_track) t.reset();
+    for (auto &g : b->d_grid) g.reset();
+    b->d_bnum.reset(); b->d_bcov.reset(); b->d_gsum.reset(); b->d_pk_out.reset();
+    b->d_pk_chunk.reset(); b->d_pk_pos.reset(); b->d_opk_vals.reset(); b->d_opk_keep.reset(); b->d_nuc_dist.reset();
+    b->d_fmt_out.reset(); b->fmt_bytes = -1;
     (void)fmt_pending_wait(b);
     b->pk_cap = 0; b->pk_n = -1; b->opk_cap = 0; b->opk_n = -1;
     b->out = BatchOutputs();
@@ -1255,7 +1271,7 @@ int natac_batch_info(natac_batch *b, int64_t *total_bp, int64_t *total_grid, int
 
 static int ensure_track(natac_batch *b, int t) {
     if (b->d_track[t]) return NATAC_OK;
-    return dev_alloc(&b->d_track[t], (size_t)b->total_bp);  // INS uses the first half of a double slot (int32)
+    return dev_alloc(b->d_track[t], (size_t)b->total_bp);  // INS uses the first half of a double slot (int32)
 }
 
 int natac_run_nuc(natac_batch *b, double smooth_sd) {
@@ -1272,7 +1288,7 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
                     b->bias_left, b->bias_right);
     for (int i = 0; i < b->nc; ++i)
         if (b->h_len[i] < M) return fail(NATAC_E_ARG, "chunk %d shorter (%d) than the smoothing window (%d)", i, b->h_len[i], M);
-    if ((rc = ensure_window(c, &c->d_win_nuc, &c->win_nuc_M, &c->win_nuc_sd, M, smooth_sd, &c->win_nuc_sum))) return rc;
+    if ((rc = ensure_window(c, c->d_win_nuc, &c->win_nuc_M, &c->win_nuc_sd, M, smooth_sd, &c->win_nuc_sum))) return rc;
     const bool use_fft = fft_bg_applicable(c);
     // The background track itself is an output only with --write_all (run_nuc.py:22-39: _nucHelper returns it, run_nuc writes it only
     // then); the FFT kernel leaves its two factors per base (bnum, bcov: the candidates read them) and T_BACKGROUND is formed from them
@@ -1280,8 +1296,8 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     for (int t : {NATAC_T_NUC_COV, NATAC_T_NFR_COV, NATAC_T_RAW, NATAC_T_NORM, NATAC_T_SMOOTH})
         if ((rc = ensure_track(b, t))) return rc;
     if (!use_fft && (rc = ensure_track(b, NATAC_T_BACKGROUND))) return rc;
-    if (!b->d_bnum && (rc = dev_alloc(&b->d_bnum, (size_t)b->total_bp))) return rc;
-    if (!b->d_bcov && (rc = dev_alloc(&b->d_bcov, (size_t)b->total_bp))) return rc;
+    if (!b->d_bnum && (rc = dev_alloc(b->d_bnum, (size_t)b->total_bp))) return rc;
+    if (!b->d_bcov && (rc = dev_alloc(b->d_bcov, (size_t)b->total_bp))) return rc;
     const bool fast = !use_fft && (c->W == 121 && c->vlower >= 2);
     if (use_fft) {
         if ((rc = ensure_fft(c))) return rc;
@@ -1295,16 +1311,16 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     } else if (fast) {
         const int G = choose_bg_G(b, c->W);
         if (G != b->bgG) {
-            if ((rc = build_tiles(b, 64 * G, &b->d_tiles_bg, &b->n_tiles_bg))) return rc;
+            if ((rc = build_tiles(b, 64 * G, b->d_tiles_bg, &b->n_tiles_bg))) return rc;
             b->bgG = G;
         }
     }
-    if (!b->d_ebias && b->d_bias && (rc = dev_alloc(&b->d_ebias, (size_t)b->nb))) return rc;
+    if (!b->d_ebias && b->d_bias && (rc = dev_alloc(b->d_ebias, (size_t)b->nb))) return rc;
     const ChunkTable ct = make_table(b);
     const VMatDev vm = make_vmat(c);
     natac_ctx::Ev ev;
-    if (!b->d_ranges256 && (rc = dev_alloc(&b->d_ranges256, (size_t)b->n_tiles256))) return rc;
-    if ((M - 1) / 2 == 30 && !b->d_tiles1k && (rc = build_tiles(b, 1024, &b->d_tiles1k, &b->n_tiles1k))) return rc;
+    if (!b->d_ranges256 && (rc = dev_alloc(b->d_ranges256, (size_t)b->n_tiles256))) return rc;
+    if ((M - 1) / 2 == 30 && !b->d_tiles1k && (rc = build_tiles(b, 1024, b->d_tiles1k, &b->n_tiles1k))) return rc;
     prof_begin(c, NATAC_K_FRAG_GATHER, ev);
     if (b->ranges256_w != c->vw) {
         hipLaunchKernelGGL(natac_tile_ranges256, dim3((b->n_tiles256 + 255) / 256), dim3(256), 0, c->stream, ct, b->d_tiles256,
@@ -1388,8 +1404,6 @@ static int occ_smooth_blocks(int h, int step) {
 static int ensure_block_weights(natac_ctx *c, int M, double sd, int NB) {
     if (c->d_wb_occ && c->wb_M == M && c->wb_step == c->step) return NATAC_OK;
     HIPCHK(sync_all(c));
-    dev_free(c->d_wb_occ);
-    c->d_wb_occ = nullptr;
     const int h = (M - 1) / 2, step = c->step;
     std::vector<double> w((size_t)M), wb((size_t)step * NB + step);     // + the full denominators wb[NB][j] of the clean sweep
     for (int i = 0; i < M; ++i) {           // as ensure_window
@@ -1411,7 +1425,7 @@ static int ensure_block_weights(natac_ctx *c, int M, double sd, int NB) {
         for (int bi = 0; bi < NB; ++bi) den = std::fma(wb[(size_t)bi * step + j], 1.0, den);
         wb[(size_t)NB * step + j] = den;
     }
-    int rc = dev_upload(c, &c->d_wb_occ, wb.data(), wb.size());
+    int rc = dev_upload(c, c->d_wb_occ, wb.data(), wb.size());
     if (rc) return rc;
     HIPCHK(sync_all(c));
     c->wb_M = M;
@@ -1473,7 +1487,7 @@ static int occ_prepare(natac_batch *b) {
     for (int i = 0; i < b->nc; ++i)
         if (b->h_len[i] < M) return fail(NATAC_E_ARG, "chunk %d shorter (%d) than the occupancy window (%d)", i, b->h_len[i], M);
     int rc;
-    if ((rc = ensure_window(c, &c->d_win_occ, &c->win_occ_M, &c->win_occ_sd, M, sd))) return rc;
+    if ((rc = ensure_window(c, c->d_win_occ, &c->win_occ_M, &c->win_occ_sd, M, sd))) return rc;
     if (!b->d_grid_off || b->grid_step != c->step) {
         b->h_grid_off.assign((size_t)b->nc + 1, 0);
         for (int i = 0; i < b->nc; ++i) {
@@ -1482,29 +1496,23 @@ static int occ_prepare(natac_batch *b) {
         }
         b->total_grid = b->h_grid_off[b->nc];
         HIPCHK(sync_all(c));
-        dev_free(b->d_grid_off);
-        b->d_grid_off = nullptr;
-        if ((rc = dev_upload(c, &b->d_grid_off, b->h_grid_off.data(), (size_t)b->nc + 1))) return rc;
-        for (int i = 0; i < 3; ++i) {
-            dev_free(b->d_grid[i]);
-            b->d_grid[i] = nullptr;
-            if ((rc = dev_alloc(&b->d_grid[i], (size_t)b->total_grid))) return rc;
-        }
-        if ((rc = build_tiles(b, OCC_T * OCC_NP, &b->d_tiles_occ, &b->n_tiles_occ, true, c->step, c->halfstep))) return rc;
-        dev_free(b->d_ranges_occ); dev_free(b->d_order_occ);
-        b->d_ranges_occ = nullptr; b->d_order_occ = nullptr;
-        if ((rc = dev_alloc(&b->d_ranges_occ, (size_t)b->n_tiles_occ))) return rc;
-        if ((rc = dev_alloc(&b->d_order_occ, (size_t)2 + HEAVY_CAP + ((size_t)b->n_tiles_occ + 3) / 4))) return rc;
+        if ((rc = dev_upload(c, b->d_grid_off, b->h_grid_off.data(), (size_t)b->nc + 1))) return rc;
+        for (auto &g : b->d_grid)
+            if ((rc = dev_alloc(g, (size_t)b->total_grid))) return rc;
+        if ((rc = build_tiles(b, OCC_T * OCC_NP, b->d_tiles_occ, &b->n_tiles_occ, true, c->step, c->halfstep))) return rc;
+        b->d_ranges_occ.reset(); b->d_order_occ.reset();
+        if ((rc = dev_alloc(b->d_ranges_occ, (size_t)b->n_tiles_occ))) return rc;
+        if ((rc = dev_alloc(b->d_order_occ, (size_t)2 + HEAVY_CAP + ((size_t)b->n_tiles_occ + 3) / 4))) return rc;
         b->ranges_occ_key[0] = -1;       // new tile table: ranges not formed yet
         b->gs_Q = -1;                    // ... and the block tables of natac_occ_gsum follow the grid
         b->grid_step = c->step;
         b->grid_half = c->halfstep;
     }
     for (int i = 0; i < 3; ++i)      // released by natac_batch_release_outputs
-        if (!b->d_grid[i] && (rc = dev_alloc(&b->d_grid[i], (size_t)b->total_grid))) return rc;
+        if (!b->d_grid[i] && (rc = dev_alloc(b->d_grid[i], (size_t)b->total_grid))) return rc;
     for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV})
         if ((rc = ensure_track(b, t))) return rc;
-    if (!b->d_ebias && b->d_bias && (rc = dev_alloc(&b->d_ebias, (size_t)b->nb))) return rc;
+    if (!b->d_ebias && b->d_bias && (rc = dev_alloc(b->d_ebias, (size_t)b->nb))) return rc;
     const bool fast = c->occ_fast_ok && !c->occ_force_general;
     if (fast) {   // per-block sum buffers + tile table of natac_occ_gsum (geometry: step / flank of the model)
         const int Q = (2 * c->flank + 1) / c->step;      // whole step-blocks of a window; the rest is a prefix of the next block
@@ -1518,16 +1526,15 @@ static int occ_prepare(natac_batch *b) {
                 for (int x = 0; x < nblk; x += GS_BLOCKS) tiles.push_back(make_int2(i, x));
             }
             b->total_blocks = bo[b->nc];
-            dev_free(b->d_blk_off); dev_free(b->d_gsum); dev_free(b->d_tiles_gs); dev_free(b->d_defer);
-            b->d_blk_off = nullptr; b->d_gsum = nullptr; b->d_tiles_gs = nullptr; b->d_defer = nullptr;
-            if ((rc = dev_upload(c, &b->d_blk_off, bo.data(), bo.size()))) return rc;
-            if ((rc = dev_upload(c, &b->d_tiles_gs, tiles.data(), tiles.size()))) return rc;
+            b->d_blk_off.reset(); b->d_gsum.reset(); b->d_tiles_gs.reset(); b->d_defer.reset();
+            if ((rc = dev_upload(c, b->d_blk_off, bo.data(), bo.size()))) return rc;
+            if ((rc = dev_upload(c, b->d_tiles_gs, tiles.data(), tiles.size()))) return rc;
             HIPCHK(sync_all(c));
             b->n_tiles_gs = (int)tiles.size();
-            if ((rc = dev_alloc(&b->d_defer, (size_t)b->n_tiles_occ + 1))) return rc;
+            if ((rc = dev_alloc(b->d_defer, (size_t)b->n_tiles_occ + 1))) return rc;
             b->gs_Q = Q;
         }
-        if (!b->d_gsum && (rc = dev_alloc(&b->d_gsum, (size_t)4 * b->total_blocks))) return rc;
+        if (!b->d_gsum && (rc = dev_alloc(b->d_gsum, (size_t)4 * b->total_blocks))) return rc;
     }
     // geometry checks + tables of the smoothing pass
     {
@@ -1553,11 +1560,11 @@ static int occ_prepare(natac_batch *b) {
         const int NB = occ_smooth_blocks((M - 1) / 2, c->step);
         if ((rc = ensure_block_weights(c, M, sd, NB))) return rc;
         if (b->os_width != 256 * c->step) {
-            if ((rc = build_tiles(b, 256 * c->step, &b->d_tiles_os, &b->n_tiles_os))) return rc;
+            if ((rc = build_tiles(b, 256 * c->step, b->d_tiles_os, &b->n_tiles_os))) return rc;
             b->os_width = 256 * c->step;
         }
-        if (!b->d_occ_minkey && (rc = dev_alloc(&b->d_occ_minkey, (size_t)b->nc))) return rc;
-        if (!b->d_occ_nan && (rc = dev_alloc(&b->d_occ_nan, (size_t)b->nc))) return rc;
+        if (!b->d_occ_minkey && (rc = dev_alloc(b->d_occ_minkey, (size_t)b->nc))) return rc;
+        if (!b->d_occ_nan && (rc = dev_alloc(b->d_occ_nan, (size_t)b->nc))) return rc;
     } else {
         if ((rc = ensure_track(b, NATAC_T_OCC_PREFILL))) return rc;
     }
@@ -1701,10 +1708,10 @@ static int ins_launch(natac_batch *b, int lower, int upper) {
     for (int i = 0; i < b->nc; ++i) maxL = std::max(maxL, b->h_len[i]);
     if ((size_t)maxL * sizeof(int) <= 60 * 1024) {
         hipLaunchKernelGGL(natac_insertions_lds, dim3(b->nc), dim3(256), (size_t)maxL * sizeof(int), c->stream, ct, lower, upper,
-                           (int *)b->d_track[NATAC_T_INS]);
+                           (int *)b->d_track[NATAC_T_INS].get());
     } else {
         HIPCHK(hipMemsetAsync(b->d_track[NATAC_T_INS], 0, (size_t)b->total_bp * sizeof(int), c->stream));
-        hipLaunchKernelGGL(natac_insertions, dim3(b->nc), dim3(256), 0, c->stream, ct, lower, upper, (int *)b->d_track[NATAC_T_INS]);
+        hipLaunchKernelGGL(natac_insertions, dim3(b->nc), dim3(256), 0, c->stream, ct, lower, upper, (int *)b->d_track[NATAC_T_INS].get());
     }
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
@@ -1735,11 +1742,12 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
         if (ci < 0 || ci >= b->nc || cand_pos[k] < 0 || cand_pos[k] >= b->h_len[ci])
             return fail(NATAC_E_ARG, "candidate %lld out of range (chunk %d pos %d)", (long long)k, ci, cand_pos[k]);
     }
+    StreamTemps tmp(c);
     int *d_cc = nullptr, *d_cp = nullptr;
     double *d_out = nullptr;
-    if ((rc = dev_upload(c, &d_cc, cand_chunk, (size_t)n_cand))) return rc;
-    if ((rc = dev_upload(c, &d_cp, cand_pos, (size_t)n_cand))) { dev_free(d_cc); return rc; }
-    if ((rc = dev_alloc(&d_out, (size_t)3 * n_cand))) { dev_free(d_cc); dev_free(d_cp); return rc; }
+    if ((rc = tmp.upload(&d_cc, cand_chunk, (size_t)n_cand)) || (rc = tmp.upload(&d_cp, cand_pos, (size_t)n_cand)) ||
+        (rc = tmp.alloc(&d_out, (size_t)3 * n_cand)))
+        return rc;
     const ChunkTable ct = make_table(b);
     const VMatDev vm = make_vmat(c);
     natac_ctx::Ev ev;
@@ -1754,7 +1762,6 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
     if (e == hipSuccess) e = hipMemcpyAsync(var, d_out + n_cand, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(z, d_out + 2 * n_cand, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_cc); dev_free(d_cp); dev_free(d_out);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates: %s", hipGetErrorString(e));
     prof_collect(c);
     return NATAC_OK;
@@ -1782,56 +1789,53 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     const ChunkTable ct = make_table(b);
     const VMatDev vm = make_vmat(c);
     const int EW = c->W + ((c->vupper - 2) >> 1) + ((c->vupper - 1) >> 1);
-    int *d_cc = nullptr, *d_cp = nullptr;
-    double *d_p = nullptr, *d_out = nullptr;
     const int64_t slab = std::min<int64_t>(SLAB, n_cand);
-    if ((rc = dev_alloc(&d_cc, (size_t)slab)) || (rc = dev_alloc(&d_cp, (size_t)slab)) || (rc = dev_alloc(&d_p, (size_t)slab * N)) ||
-        (rc = dev_alloc(&d_out, (size_t)slab * NBLK))) {
-        dev_free(d_cc); dev_free(d_cp); dev_free(d_p); dev_free(d_out);
-        return rc;
-    }
     std::vector<double> part((size_t)slab * NBLK);
-    hipError_t e = hipSuccess;
-    for (int64_t k0 = 0; k0 < n_cand && e == hipSuccess; k0 += slab) {
-        const int64_t m = std::min<int64_t>(slab, n_cand - k0);
-        e = hipMemcpyAsync(d_cc, cand_chunk + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_cp, cand_pos + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(natac_cand_window_probs, dim3((unsigned)m), dim3(256), (size_t)(EW + 2) * sizeof(double), c->stream, ct, vm,
-                           d_cc, d_cp, d_p);
-        const int per = mode == 1 ? NBLK : 1;
-        if (mode == 1)
-            hipLaunchKernelGGL(natac_cov_literal_many, dim3(NBLK, (unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
-        else if (mode == 0)
-            hipLaunchKernelGGL((natac_cov_closed_many<double>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
-        else
-            hipLaunchKernelGGL((natac_cov_closed_many<float>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) break;
-        for (int64_t k = 0; k < m; ++k) {
-            double s = 0;
-            for (int j = 0; j < per; ++j) s += part[(size_t)k * per + j];
-            var[k0 + k] = s;
+    {
+        StreamTemps tmp(c);
+        int *d_cc = nullptr, *d_cp = nullptr;
+        double *d_p = nullptr, *d_out = nullptr;
+        if ((rc = tmp.alloc(&d_cc, (size_t)slab)) || (rc = tmp.alloc(&d_cp, (size_t)slab)) || (rc = tmp.alloc(&d_p, (size_t)slab * N)) ||
+            (rc = tmp.alloc(&d_out, (size_t)slab * NBLK)))
+            return rc;
+        for (int64_t k0 = 0; k0 < n_cand; k0 += slab) {
+            const int64_t m = std::min<int64_t>(slab, n_cand - k0);
+            hipError_t e = hipMemcpyAsync(d_cc, cand_chunk + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_cp, cand_pos + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
+            if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
+            hipLaunchKernelGGL(natac_cand_window_probs, dim3((unsigned)m), dim3(256), (size_t)(EW + 2) * sizeof(double), c->stream, ct, vm,
+                               d_cc, d_cp, d_p);
+            const int per = mode == 1 ? NBLK : 1;
+            if (mode == 1)
+                hipLaunchKernelGGL(natac_cov_literal_many, dim3(NBLK, (unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
+            else if (mode == 0)
+                hipLaunchKernelGGL((natac_cov_closed_many<double>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
+            else
+                hipLaunchKernelGGL((natac_cov_closed_many<float>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
+            for (int64_t k = 0; k < m; ++k) {
+                double s = 0;
+                for (int j = 0; j < per; ++j) s += part[(size_t)k * per + j];
+                var[k0 + k] = s;
+            }
         }
     }
-    dev_free(d_cc); dev_free(d_cp); dev_free(d_p); dev_free(d_out);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
     // r = int(nuc_cov[pos]) like the .pyx's `int r` (NucleosomeCalling.py:125): one gather of the coverage values
     std::vector<double> reads((size_t)n_cand);
     {
         std::vector<long long> idx((size_t)n_cand);
         for (int64_t k = 0; k < n_cand; ++k) idx[(size_t)k] = b->h_out_off[cand_chunk[k]] + cand_pos[k];
+        StreamTemps tmp(c);
         long long *d_idx = nullptr;
         double *d_r = nullptr;
-        if ((rc = dev_upload(c, &d_idx, idx.data(), (size_t)n_cand))) return rc;
-        if ((rc = dev_alloc(&d_r, (size_t)n_cand))) { dev_free(d_idx); return rc; }
+        if ((rc = tmp.upload(&d_idx, idx.data(), (size_t)n_cand)) || (rc = tmp.alloc(&d_r, (size_t)n_cand))) return rc;
         hipLaunchKernelGGL(natac_gather_f64, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, c->stream,
                            b->d_track[NATAC_T_NUC_COV], d_idx, (long long)n_cand, d_r);
-        e = hipMemcpyAsync(reads.data(), d_r, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipMemcpyAsync(reads.data(), d_r, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        dev_free(d_idx); dev_free(d_r);
         if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
     }
     for (int64_t k = 0; k < n_cand; ++k) var[k] = var[k] * (double)(int)reads[(size_t)k];
@@ -1850,9 +1854,7 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     HIPCHK(sync_all(c));
     int rc;
     if (!b->d_jitter || b->n_jitter < maxL) {
-        dev_free(b->d_jitter);
-        b->d_jitter = nullptr;
-        if ((rc = dev_upload(c, &b->d_jitter, jitter, (size_t)maxL))) return rc;
+        if ((rc = dev_upload(c, b->d_jitter, jitter, (size_t)maxL))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
         b->n_jitter = maxL;
     } else {
@@ -1863,15 +1865,14 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
         std::vector<long long> cap((size_t)b->nc + 1, 0);
         for (int i = 0; i < b->nc; ++i) cap[i + 1] = cap[i] + b->h_len[i] / (order + 1) + 2;
         b->slot_total = cap[b->nc];
-        dev_free(b->d_cap_off); dev_free(b->d_slot);
-        b->d_cap_off = nullptr; b->d_slot = nullptr;
-        if ((rc = dev_upload(c, &b->d_cap_off, cap.data(), (size_t)b->nc + 1))) return rc;
+        b->d_cap_off.reset(); b->d_slot.reset();
+        if ((rc = dev_upload(c, b->d_cap_off, cap.data(), (size_t)b->nc + 1))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
-        if ((rc = dev_alloc(&b->d_slot, (size_t)b->slot_total))) return rc;
+        if ((rc = dev_alloc(b->d_slot, (size_t)b->slot_total))) return rc;
         b->pk_order = order;
     }
-    if (!b->d_pk_count && (rc = dev_alloc(&b->d_pk_count, (size_t)b->nc))) return rc;
-    if (!b->d_pk_offs && (rc = dev_alloc(&b->d_pk_offs, (size_t)b->nc + 1))) return rc;
+    if (!b->d_pk_count && (rc = dev_alloc(b->d_pk_count, (size_t)b->nc))) return rc;
+    if (!b->d_pk_offs && (rc = dev_alloc(b->d_pk_offs, (size_t)b->nc + 1))) return rc;
     const ChunkTable ct = make_table(b);
     const double *norm = sig_a, *sm = sig_b;
     natac_ctx::Ev ev;
@@ -1910,14 +1911,9 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
             int *big_pos = nullptr;
             unsigned char *big_state = nullptr;
             if (maxL / (order + 1) + 2 > pk_cap) {      // some chunk can hold more maxima than the LDS lists: global lists for those
-                if (b->pk_big_slots < b->slot_total) {
-                    dev_free(b->d_pk_big);
-                    b->d_pk_big = nullptr;
-                    b->pk_big_slots = 0;
-                    // per slot: sig (8 bytes) + pos (4) + state (1), laid out as three arrays in one block
-                    if ((rc = dev_alloc(&b->d_pk_big, (size_t)b->slot_total * 2 + 2))) return rc;
-                    b->pk_big_slots = b->slot_total;
-                }
+                // per slot: sig (8 bytes) + pos (4) + state (1), laid out as three arrays in one block
+                if (b->d_pk_big.size() < (size_t)b->slot_total * 2 + 2 && (rc = dev_alloc(b->d_pk_big, (size_t)b->slot_total * 2 + 2)))
+                    return rc;
                 big_sig = b->d_pk_big;
                 big_pos = (int *)(b->d_pk_big + b->slot_total);
                 big_state = (unsigned char *)(big_pos + b->slot_total);
@@ -1933,13 +1929,16 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&total, b->d_pk_offs + b->nc, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (total > b->pk_cap) {
-        dev_free(b->d_pk_chunk); dev_free(b->d_pk_pos); dev_free(b->d_pk_out);
-        b->d_pk_chunk = b->d_pk_pos = nullptr; b->d_pk_out = nullptr;
-        b->pk_cap = total + total / 4 + 16;
-        if ((rc = dev_alloc(&b->d_pk_chunk, (size_t)b->pk_cap))) return rc;
-        if ((rc = dev_alloc(&b->d_pk_pos, (size_t)b->pk_cap))) return rc;
-        if ((rc = dev_alloc(&b->d_pk_out, (size_t)3 * b->pk_cap))) return rc;
+    if (total > b->pk_cap) {      // pk_cap is the stride of all three: set once they all exist, 0 while they do not
+        b->d_pk_chunk.reset(); b->d_pk_pos.reset(); b->d_pk_out.reset();
+        b->pk_cap = 0;
+        const long long cap = total + total / 4 + 16;
+        if ((rc = dev_alloc(b->d_pk_chunk, (size_t)cap)) || (rc = dev_alloc(b->d_pk_pos, (size_t)cap)) ||
+            (rc = dev_alloc(b->d_pk_out, (size_t)3 * cap))) {
+            b->d_pk_chunk.reset(); b->d_pk_pos.reset();
+            return rc;
+        }
+        b->pk_cap = cap;
     }
     if (total > 0) {
         hipLaunchKernelGGL(natac_compact_candidates, dim3((b->nc + 3) / 4), dim3(256), 0, c->stream, b->nc, b->d_pk_count, b->d_pk_offs,
@@ -1989,24 +1988,20 @@ int natac_run_occ_peaks(natac_batch *b, double min_occ, int sep, const double *j
     rc = run_peaks_impl(b, b->d_track[NATAC_T_OCC], nullptr, false, min_occ, sep, sep / 2, 1, jitter, n_jitter, n_peaks);
     if (rc) return rc;
     const long long n = *n_peaks;
-    if (n > b->opk_cap) {
-        HIPCHK(sync_all(c));
-        dev_free(b->d_opk_vals); dev_free(b->d_opk_keep);
-        b->d_opk_vals = nullptr; b->d_opk_keep = nullptr;
-        b->opk_cap = n + n / 4 + 16;
-        if ((rc = dev_alloc(&b->d_opk_vals, (size_t)4 * b->opk_cap))) return rc;
-        if ((rc = dev_alloc(&b->d_opk_keep, (size_t)b->opk_cap))) return rc;
-    }
-    if (!b->d_opk_vals) {
-        b->opk_cap = 16;
-        if ((rc = dev_alloc(&b->d_opk_vals, (size_t)4 * b->opk_cap))) return rc;
-        if ((rc = dev_alloc(&b->d_opk_keep, (size_t)b->opk_cap))) return rc;
+    if (n > b->opk_cap || !b->d_opk_vals) {     // opk_cap is the stride of both: set once both exist, 0 while they do not
+        if (n > b->opk_cap) HIPCHK(sync_all(c));
+        const long long cap = n > b->opk_cap ? n + n / 4 + 16 : 16;
+        b->d_opk_vals.reset(); b->d_opk_keep.reset();
+        b->opk_cap = 0;
+        if ((rc = dev_alloc(b->d_opk_vals, (size_t)4 * cap)) || (rc = dev_alloc(b->d_opk_keep, (size_t)cap))) {
+            b->d_opk_vals.reset();
+            return rc;
+        }
+        b->opk_cap = cap;
     }
     if (!b->d_nuc_dist || b->nd_upper != U) {
         HIPCHK(sync_all(c));
-        dev_free(b->d_nuc_dist);
-        b->d_nuc_dist = nullptr;
-        if ((rc = dev_alloc(&b->d_nuc_dist, (size_t)b->nc * U))) return rc;
+        if ((rc = dev_alloc(b->d_nuc_dist, (size_t)b->nc * U))) return rc;
         b->nd_upper = U;
     }
     const ChunkTable ct = make_table(b);
@@ -2148,11 +2143,12 @@ int natac_make_fragment_mat(natac_ctx *c, int64_t nf, const int64_t *l, const in
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     long long *d_l = nullptr; int *d_n = nullptr; double *d_m = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_l, (const long long *)l, (size_t)nf))) return rc;
-    if ((rc = dev_upload(c, &d_n, n, (size_t)nf))) { dev_free(d_l); return rc; }
-    if ((rc = dev_alloc(&d_m, (size_t)(nrow * ncol)))) { dev_free(d_l); dev_free(d_n); return rc; }
+    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
+        (rc = tmp.alloc(&d_m, (size_t)(nrow * ncol))))
+        return rc;
     hipError_t e = hipMemsetAsync(d_m, 0, (size_t)(nrow * ncol) * sizeof(double), c->stream);
     if (e == hipSuccess && nf > 0) {
         int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
@@ -2162,7 +2158,6 @@ int natac_make_fragment_mat(natac_ctx *c, int64_t nf, const int64_t *l, const in
     }
     if (e == hipSuccess) e = hipMemcpyAsync(mat, d_m, (size_t)(nrow * ncol) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_l); dev_free(d_n); dev_free(d_m);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "make_fragment_mat: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2174,12 +2169,12 @@ int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     const long long npos = end - start;
     if (npos > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     long long *d_l = nullptr; int *d_n = nullptr, *d_i = nullptr; double *d_o = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_l, (const long long *)l, (size_t)nf))) return rc;
-    if ((rc = dev_upload(c, &d_n, n, (size_t)nf))) { dev_free(d_l); return rc; }
-    if ((rc = dev_alloc(&d_i, (size_t)npos))) { dev_free(d_l); dev_free(d_n); return rc; }
-    if ((rc = dev_alloc(&d_o, (size_t)npos))) { dev_free(d_l); dev_free(d_n); dev_free(d_i); return rc; }
+    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
+        (rc = tmp.alloc(&d_i, (size_t)npos)) || (rc = tmp.alloc(&d_o, (size_t)npos)))
+        return rc;
     hipError_t e = hipMemsetAsync(d_i, 0, (size_t)npos * sizeof(int), c->stream);
     if (e == hipSuccess) {
         if (nf > 0) {
@@ -2193,7 +2188,6 @@ int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_l); dev_free(d_n); dev_free(d_i); dev_free(d_o);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "get_insertions: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2205,12 +2199,12 @@ int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, co
     const long long npos = end - start;
     if (npos > 0x3fffffffLL) return fail(NATAC_E_ARG, "region too long");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     long long *d_l = nullptr; int *d_n = nullptr, *d_i = nullptr; double *d_o = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_l, (const long long *)l, (size_t)nf))) return rc;
-    if ((rc = dev_upload(c, &d_n, n, (size_t)nf))) { dev_free(d_l); return rc; }
-    if ((rc = dev_alloc(&d_i, (size_t)2 * npos))) { dev_free(d_l); dev_free(d_n); return rc; }
-    if ((rc = dev_alloc(&d_o, (size_t)2 * npos))) { dev_free(d_l); dev_free(d_n); dev_free(d_i); return rc; }
+    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
+        (rc = tmp.alloc(&d_i, (size_t)2 * npos)) || (rc = tmp.alloc(&d_o, (size_t)2 * npos)))
+        return rc;
     hipError_t e = hipMemsetAsync(d_i, 0, (size_t)2 * npos * sizeof(int), c->stream);
     if (e == hipSuccess) {
         if (nf > 0) {
@@ -2225,7 +2219,6 @@ int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, co
     if (e == hipSuccess) e = hipMemcpyAsync(plus, d_o, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(minus, d_o + npos, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_l); dev_free(d_n); dev_free(d_i); dev_free(d_o);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "get_stranded_insertions: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2244,13 +2237,13 @@ int natac_fragment_sizes(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     for (int k = 0; k < nchunks; ++k) { hs[k] = cs[k]; he[k] = std::max<long long>(ce[k], cs[k]); }
     std::sort(hs.begin(), hs.end());
     std::sort(he.begin(), he.end());
+    StreamTemps tmp(c);
     long long *d_l = nullptr, *d_cs = nullptr, *d_ce = nullptr; int *d_n = nullptr; unsigned long long *d_h = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_l, (const long long *)l, (size_t)nf))) return rc;
-    if ((rc = dev_upload(c, &d_n, n, (size_t)nf))) { dev_free(d_l); return rc; }
-    if ((rc = dev_upload(c, &d_cs, hs.data(), (size_t)nchunks))) { dev_free(d_l); dev_free(d_n); return rc; }
-    if ((rc = dev_upload(c, &d_ce, he.data(), (size_t)nchunks))) { dev_free(d_l); dev_free(d_n); dev_free(d_cs); return rc; }
-    if ((rc = dev_alloc(&d_h, (size_t)nb))) { dev_free(d_l); dev_free(d_n); dev_free(d_cs); dev_free(d_ce); return rc; }
+    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
+        (rc = tmp.upload(&d_cs, hs.data(), (size_t)nchunks)) || (rc = tmp.upload(&d_ce, he.data(), (size_t)nchunks)) ||
+        (rc = tmp.alloc(&d_h, (size_t)nb)))
+        return rc;
     std::vector<unsigned long long> h((size_t)nb, 0);
     hipError_t e = hipMemsetAsync(d_h, 0, (size_t)nb * sizeof(unsigned long long), c->stream);
     natac_ctx::Ev ev;
@@ -2267,7 +2260,6 @@ int natac_fragment_sizes(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     prof_end(c, ev);
     if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_h, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_l); dev_free(d_n); dev_free(d_cs); dev_free(d_ce); dev_free(d_h);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "fragment_sizes: %s", hipGetErrorString(e));
     prof_collect(c);
     for (int i = 0; i < nb; ++i) sizes[i] = (double)h[i];
@@ -2279,12 +2271,13 @@ int natac_calculate_cov(natac_ctx *c, const double *p, const double *v, int64_t 
     if (n <= 0) return fail(NATAC_E_ARG, "p and v must be non-empty");
     if (mode != 0 && mode != 1) return fail(NATAC_E_ARG, "mode must be 0 (closed form) or 1 (literal)");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     double *d_p = nullptr, *d_v = nullptr, *d_part = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_p, p, (size_t)n))) return rc;
-    if ((rc = dev_upload(c, &d_v, v, (size_t)n))) { dev_free(d_p); return rc; }
+    if ((rc = tmp.upload(&d_p, p, (size_t)n)) || (rc = tmp.upload(&d_v, v, (size_t)n)))
+        return rc;
     const int blocks = mode == 0 ? (int)std::min<int64_t>((n + 255) / 256, 1024) : (int)std::min<int64_t>(n, 4096);
-    if ((rc = dev_alloc(&d_part, (size_t)2 * blocks))) { dev_free(d_p); dev_free(d_v); return rc; }
+    if ((rc = tmp.alloc(&d_part, (size_t)2 * blocks))) return rc;
     std::vector<double> part((size_t)2 * blocks);
     if (mode == 0)
         hipLaunchKernelGGL(natac_cov_closed, dim3(blocks), dim3(256), 0, c->stream, d_p, d_v, (long long)n, d_part);
@@ -2294,7 +2287,6 @@ int natac_calculate_cov(natac_ctx *c, const double *p, const double *v, int64_t 
     if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, (size_t)(mode == 0 ? 2 : 1) * blocks * sizeof(double),
                                             hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_p); dev_free(d_v); dev_free(d_part);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "calculate_cov: %s", hipGetErrorString(e));
     if (mode == 0) {
         double s1 = 0, s2 = 0;
@@ -2317,17 +2309,16 @@ int natac_smooth(natac_ctx *c, const double *x, int64_t n, const double *w, int 
     if (n < M) return fail(NATAC_E_ARG, "signal (%lld) shorter than the window (%d)", (long long)n, M);
     const long long nout = mode == 0 ? n - M + 1 : n;
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     double *d_x = nullptr, *d_w = nullptr, *d_y = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_x, x, (size_t)n))) return rc;
-    if ((rc = dev_upload(c, &d_w, w, (size_t)M))) { dev_free(d_x); return rc; }
-    if ((rc = dev_alloc(&d_y, (size_t)nout))) { dev_free(d_x); dev_free(d_w); return rc; }
+    if ((rc = tmp.upload(&d_x, x, (size_t)n)) || (rc = tmp.upload(&d_w, w, (size_t)M)) || (rc = tmp.alloc(&d_y, (size_t)nout)))
+        return rc;
     hipLaunchKernelGGL(natac_smooth1d, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_x, (long long)n, d_w, M, mode,
                        norm, d_y, nout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_y, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_x); dev_free(d_w); dev_free(d_y);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "smooth: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2339,12 +2330,12 @@ int natac_make_bias_mat(natac_ctx *c, const double *bias_log, int64_t nb, int64_
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     double *d_b = nullptr, *d_m = nullptr;
     int *d_oob = nullptr, oob = 0;
     int rc;
-    if ((rc = dev_upload(c, &d_b, bias_log, (size_t)nb))) return rc;
-    if ((rc = dev_alloc(&d_m, (size_t)(nrow * ncol)))) { dev_free(d_b); return rc; }
-    if ((rc = dev_alloc(&d_oob, 1))) { dev_free(d_b); dev_free(d_m); return rc; }
+    if ((rc = tmp.upload(&d_b, bias_log, (size_t)nb)) || (rc = tmp.alloc(&d_m, (size_t)(nrow * ncol))) || (rc = tmp.alloc(&d_oob, 1)))
+        return rc;
     hipError_t e = hipMemsetAsync(d_oob, 0, sizeof(int), c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(natac_bias_mat_dense, dim3((unsigned)((nrow * ncol + 255) / 256)), dim3(256), 0, c->stream, d_b, (long long)nb,
@@ -2354,7 +2345,6 @@ int natac_make_bias_mat(natac_ctx *c, const double *bias_log, int64_t nb, int64_
     if (e == hipSuccess) e = hipMemcpyAsync(mat, d_m, (size_t)(nrow * ncol) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&oob, d_oob, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_b); dev_free(d_m); dev_free(d_oob);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "make_bias_mat: %s", hipGetErrorString(e));
     if (oob) return fail(NATAC_E_ARG, "bias track does not cover [start - upper//2, end + upper//2)");
     return NATAC_OK;
@@ -2365,20 +2355,20 @@ int natac_pwm_bias(natac_ctx *c, const uint8_t *seq, int64_t n, const double *lo
     if (!c || !seq || !log_pwm || !nucleotides || !out) return fail(NATAC_E_ARG, "null argument");
     if (nrow < 1 || K < 1 || n < K) return fail(NATAC_E_ARG, "sequence shorter than the PWM");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     unsigned char *d_s = nullptr, *d_n = nullptr;
     double *d_p = nullptr, *d_o = nullptr;
     const long long nout = n - K + 1;
     int rc;
-    if ((rc = dev_upload(c, &d_s, (const unsigned char *)seq, (size_t)n))) return rc;
-    if ((rc = dev_upload(c, &d_n, (const unsigned char *)nucleotides, (size_t)nrow))) { dev_free(d_s); return rc; }
-    if ((rc = dev_upload(c, &d_p, log_pwm, (size_t)nrow * K))) { dev_free(d_s); dev_free(d_n); return rc; }
-    if ((rc = dev_alloc(&d_o, (size_t)nout))) { dev_free(d_s); dev_free(d_n); dev_free(d_p); return rc; }
+    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)n)) ||
+        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) || (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)) ||
+        (rc = tmp.alloc(&d_o, (size_t)nout)))
+        return rc;
     hipLaunchKernelGGL(natac_pwm_score, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)n, d_p, d_n, nrow, K,
                        d_o);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_s); dev_free(d_n); dev_free(d_p); dev_free(d_o);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "pwm_bias: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2412,19 +2402,17 @@ int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_le
     if (nf >= (1LL << 40)) return fail(NATAC_E_ARG, "too many fragments in one call");
     if (nf == 0) return NATAC_OK;
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     int *d_len = nullptr, *d_l = nullptr, *d_n = nullptr;
     long long *d_fo = nullptr, *d_so = nullptr;
     unsigned char *d_s = nullptr;
     unsigned long long *d_out = nullptr;
-    auto release = [&]() { dev_free(d_len); dev_free(d_l); dev_free(d_n); dev_free(d_fo); dev_free(d_so); dev_free(d_s); dev_free(d_out); };
     int rc;
-    if ((rc = dev_upload(c, &d_len, chunk_len, (size_t)nc)) || (rc = dev_upload(c, &d_fo, (const long long *)frag_off, (size_t)nc + 1)) ||
-        (rc = dev_upload(c, &d_so, (const long long *)seq_off, (size_t)nc + 1)) || (rc = dev_upload(c, &d_l, frag_lpos, (size_t)nf)) ||
-        (rc = dev_upload(c, &d_n, frag_ilen, (size_t)nf)) || (rc = dev_upload(c, &d_s, (const unsigned char *)seq, (size_t)ns)) ||
-        (rc = dev_alloc(&d_out, (size_t)4 * K + 1))) {
-        release();
+    if ((rc = tmp.upload(&d_len, chunk_len, (size_t)nc)) || (rc = tmp.upload(&d_fo, (const long long *)frag_off, (size_t)nc + 1)) ||
+        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)nc + 1)) || (rc = tmp.upload(&d_l, frag_lpos, (size_t)nf)) ||
+        (rc = tmp.upload(&d_n, frag_ilen, (size_t)nf)) || (rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)ns)) ||
+        (rc = tmp.alloc(&d_out, (size_t)4 * K + 1)))
         return rc;
-    }
     std::vector<unsigned long long> h((size_t)4 * K + 1);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipMemsetAsync(d_out, 0, h.size() * sizeof(unsigned long long), c->stream);
@@ -2451,7 +2439,6 @@ int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_le
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    release();
     if (e != hipSuccess) return fail(NATAC_E_HIP, "insertion_seq_counts: %s", hipGetErrorString(e));
     for (int i = 0; i < 4 * K; ++i) counts[i] = (int64_t)h[i];
     *n_ins = (int64_t)h[4 * K];
@@ -2476,16 +2463,14 @@ int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, c
     const long long bx = std::min<long long>((total + PF_SPAN - 1) / PF_SPAN, 8192);
     if ((total + bx - 1) / bx >= (1LL << 31)) return fail(NATAC_E_ARG, "ranges too long for one call");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     unsigned char *d_s = nullptr;
     long long *d_st = nullptr, *d_cum = nullptr;
     unsigned long long *d_out = nullptr;
-    auto release = [&]() { dev_free(d_s); dev_free(d_st); dev_free(d_cum); dev_free(d_out); };
     int rc;
-    if ((rc = dev_upload(c, &d_s, (const unsigned char *)seq, (size_t)n)) || (rc = dev_upload(c, &d_st, (const long long *)start, (size_t)nr)) ||
-        (rc = dev_upload(c, &d_cum, cum.data(), cum.size())) || (rc = dev_alloc(&d_out, 4))) {
-        release();
+    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)n)) || (rc = tmp.upload(&d_st, (const long long *)start, (size_t)nr)) ||
+        (rc = tmp.upload(&d_cum, cum.data(), cum.size())) || (rc = tmp.alloc(&d_out, 4)))
         return rc;
-    }
     unsigned long long h[4] = {0, 0, 0, 0};
     hipError_t e = hipMemsetAsync(d_out, 0, sizeof h, c->stream);
     if (e == hipSuccess) {
@@ -2494,7 +2479,6 @@ int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, c
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release();
     if (e != hipSuccess) return fail(NATAC_E_HIP, "base_counts: %s", hipGetErrorString(e));
     for (int i = 0; i < 4; ++i) counts[i] = (int64_t)h[i];
     return NATAC_OK;
@@ -2505,17 +2489,17 @@ int natac_correlate_valid(natac_ctx *c, const double *sub, int64_t ncol, const d
     if (R < 1 || W < 1 || ncol < W) return fail(NATAC_E_ARG, "matrix narrower than the template");
     const long long nout = ncol - W + 1;
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     double *d_s = nullptr, *d_v = nullptr, *d_o = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_s, sub, (size_t)R * ncol))) return rc;
-    if ((rc = dev_upload(c, &d_v, vmat, (size_t)R * W))) { dev_free(d_s); return rc; }
-    if ((rc = dev_alloc(&d_o, (size_t)nout))) { dev_free(d_s); dev_free(d_v); return rc; }
+    if ((rc = tmp.upload(&d_s, sub, (size_t)R * ncol)) || (rc = tmp.upload(&d_v, vmat, (size_t)R * W)) ||
+        (rc = tmp.alloc(&d_o, (size_t)nout)))
+        return rc;
     hipLaunchKernelGGL(natac_correlate_dense, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)ncol, d_v, R, W,
                        d_o, nout);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_s); dev_free(d_v); dev_free(d_o);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "correlate_valid: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
@@ -2524,19 +2508,18 @@ int natac_calculate_occupancy(natac_ctx *c, const double *inserts, const double 
     if (!c || !inserts || !bias || !out) return fail(NATAC_E_ARG, "null argument");
     if (!c->have_occ) return fail(NATAC_E_STATE, "natac_set_occ_model has not been called");
     HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
     double *d_i = nullptr, *d_b = nullptr, *d_o = nullptr;
     int *d_s = nullptr, st = 0;
     int rc;
-    if ((rc = dev_upload(c, &d_i, inserts, (size_t)c->occ_upper))) return rc;
-    if ((rc = dev_upload(c, &d_b, bias, (size_t)c->occ_upper))) { dev_free(d_i); return rc; }
-    if ((rc = dev_alloc(&d_o, 3))) { dev_free(d_i); dev_free(d_b); return rc; }
-    if ((rc = dev_alloc(&d_s, 1))) { dev_free(d_i); dev_free(d_b); dev_free(d_o); return rc; }
+    if ((rc = tmp.upload(&d_i, inserts, (size_t)c->occ_upper)) || (rc = tmp.upload(&d_b, bias, (size_t)c->occ_upper)) ||
+        (rc = tmp.alloc(&d_o, 3)) || (rc = tmp.alloc(&d_s, 1)))
+        return rc;
     hipLaunchKernelGGL(natac_occupancy_single, dim3(1), dim3(128), 0, c->stream, d_i, d_b, make_occ(c), d_o, d_s);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&st, d_s, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_i); dev_free(d_b); dev_free(d_o); dev_free(d_s);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "calculate_occupancy: %s", hipGetErrorString(e));
     if (st) return fail(NATAC_E_ARG, "no alpha passes the likelihood-ratio test");
     return NATAC_OK;
@@ -2558,13 +2541,13 @@ int natac_batch_format_track(natac_batch *b, int track, const int32_t *chrom_id,
     if (track != NATAC_T_INS)
         return format_values(b, b->d_track[track], chrom_id, names, n_names, chunk_start, write_zero, compress, n_bytes, n_text_bytes, n_lines,
                              n_hard);
+    StreamTemps tmp(c);
     double *d_tmp = nullptr;                   // insertion counts are int32 on the device; the writer takes float64 like the reference's track
-    if ((rc = dev_alloc(&d_tmp, (size_t)b->total_bp))) return rc;
+    if ((rc = tmp.alloc(&d_tmp, (size_t)b->total_bp))) return rc;
     const int blocks = (int)std::min<long long>((b->total_bp + 255) / 256, 65536);
-    hipLaunchKernelGGL(natac_i32_to_f64, dim3(blocks), dim3(256), 0, c->stream, (const int *)b->d_track[NATAC_T_INS], d_tmp, b->total_bp);
+    hipLaunchKernelGGL(natac_i32_to_f64, dim3(blocks), dim3(256), 0, c->stream, (const int *)b->d_track[NATAC_T_INS].get(), d_tmp, b->total_bp);
     rc = format_values(b, d_tmp, chrom_id, names, n_names, chunk_start, write_zero, compress, n_bytes, n_text_bytes, n_lines, n_hard);
     (void)hipStreamSynchronize(c->stream);
-    dev_free(d_tmp);
     return rc;
 }
 
@@ -2575,7 +2558,7 @@ static int fmt_pending_wait(natac_batch *b) {
         hipError_t e = hipEventSynchronize(p.second);
         if (e != hipSuccess && first == hipSuccess) first = e;
         (void)hipEventDestroy(p.second);
-        dev_free(p.first);
+        p.first.reset();
     }
     b->fmt_pending.clear();
     if (first != hipSuccess) return fail(NATAC_E_HIP, "format_fetch: %s", hipGetErrorString(first));
@@ -2597,8 +2580,8 @@ int natac_batch_format_fetch_begin(natac_batch *b, void *dst, size_t dst_bytes) 
     hipError_t e = hipMemcpyAsync(dst, b->d_fmt_out, (size_t)b->fmt_bytes, hipMemcpyDeviceToHost, c->copy_stream);
     if (e == hipSuccess) e = hipEventRecord(ev, c->copy_stream);
     if (e != hipSuccess) { (void)hipEventDestroy(ev); return fail(NATAC_E_HIP, "format_fetch_begin: %s", hipGetErrorString(e)); }
-    b->fmt_pending.emplace_back(b->d_fmt_out, ev);       // the buffer is the copy's until natac_batch_format_fetch_wait
-    b->d_fmt_out = nullptr;          // fmt_bytes stays: the result's tabix records are still to be fetched; a second fetch of the bytes is refused below
+    b->fmt_pending.emplace_back(std::move(b->d_fmt_out), ev);   // the buffer is the copy's until natac_batch_format_fetch_wait
+    // fmt_bytes stays: the result's tabix records are still to be fetched; a second fetch of the bytes finds d_fmt_out empty
     return NATAC_OK;
 }
 
@@ -2697,22 +2680,19 @@ int natac_format_doubles(natac_ctx *c, const double *vals, int64_t n, char *out,
     HIPCHK(hipSetDevice(c->device));
     int rc = ensure_text_tables(c);
     if (rc) return rc;
+    std::vector<int> len((size_t)n + 1);
+    std::vector<char> raw((size_t)n * natac_text::MAX_VALUE_CHARS);
+    StreamTemps tmp(c);
     double *d_v = nullptr;
     char *d_o = nullptr;
     int *d_len = nullptr, *d_hard = nullptr;
-    if ((rc = dev_upload(c, &d_v, vals, (size_t)n))) return rc;
-    TmpFree tmp;
-    tmp.keep(d_v);
-    if ((rc = dev_alloc(&d_o, (size_t)n * natac_text::MAX_VALUE_CHARS))) return rc;
-    tmp.keep(d_o);
-    if ((rc = dev_alloc(&d_len, (size_t)n + 1))) return rc;
-    tmp.keep(d_len);
+    if ((rc = tmp.upload(&d_v, vals, (size_t)n)) || (rc = tmp.alloc(&d_o, (size_t)n * natac_text::MAX_VALUE_CHARS)) ||
+        (rc = tmp.alloc(&d_len, (size_t)n + 1)))
+        return rc;
     HIPCHK(hipMemsetAsync(d_len + n, 0, sizeof(int), c->stream));
     d_hard = d_len + n;
     hipLaunchKernelGGL(natac_textz::tz_format_values, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_v, (long long)n, c->d_p10, d_o,
                        d_len, d_hard);
-    std::vector<int> len((size_t)n + 1);
-    std::vector<char> raw((size_t)n * natac_text::MAX_VALUE_CHARS);
     HIPCHK(hipMemcpyAsync(len.data(), d_len, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(raw.data(), d_o, raw.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -3174,7 +3154,7 @@ int natac_timer_stop(natac_ctx *c, double *ms) {
 /* ---------------- resident tracks between the stages of one process ---------------- */
 
 struct natac_store {
-    struct Seg { double *p[4]; int n_tracks; long long n; int device; };
+    struct Seg { PoolBuf<double> p[4]; int n_tracks; long long n; int device; };
     std::mutex mu;
     std::vector<Seg> segs;
     // HBM budget: the store is a convenience next to the files, it must never be what fills the device.  A segment is adopted only
@@ -3205,9 +3185,6 @@ int natac_store_set_budget(natac_store *s, int64_t max_bytes, int64_t min_free_b
 }
 
 void natac_store_free(natac_store *s) {
-    if (!s) return;
-    for (auto &g : s->segs)
-        for (int i = 0; i < g.n_tracks; ++i) dev_free(g.p[i]);
     delete s;
 }
 
@@ -3242,50 +3219,43 @@ int natac_store_adopt(natac_store *s, natac_batch *b, int32_t n_tracks, const in
     }
     if ((rc = ensure_text_tables(c))) return rc;
     HIPCHK(sync_all(c));
-    TmpFree tmp;
-    int *d_tc = nullptr, *d_C = nullptr, *d_hard = nullptr;
-    unsigned long long *d_tb = nullptr;
-    unsigned int *d_R = nullptr;
-    const int nt = b->n_tiles256;
-#define TRYS(x) do { if ((rc = (x)) != NATAC_OK) { for (int q_ = 0; q_ < 4; ++q_) dev_free(seg.p[q_]); dev_free(d_R); dev_free(d_C); return rc; } } while (0)
-    natac_store::Seg seg{{nullptr, nullptr, nullptr, nullptr}, n_tracks, b->total_bp, c->device};
-    TRYS(dev_alloc(&d_hard, 1)); tmp.keep(d_hard);
-    TRYS(dev_alloc(&d_tc, (size_t)nt)); tmp.keep(d_tc);
-    TRYS(dev_alloc(&d_tb, (size_t)nt + 1)); tmp.keep(d_tb);
-    hipError_t e = hipMemsetAsync(d_hard, 0, sizeof(int), c->stream);
+    // declared before the scope: an early exit drains the stream before the segment's tracks and the run tables go back
+    natac_store::Seg seg{{}, n_tracks, b->total_bp, c->device};
+    PoolBuf<unsigned int> d_R;
+    PoolBuf<int> d_C;
     int hard = 0;
+    StreamTemps tmp(c);
+    int *d_tc = nullptr, *d_hard = nullptr;
+    unsigned long long *d_tb = nullptr;
+    const int nt = b->n_tiles256;
+    if ((rc = tmp.alloc(&d_hard, 1)) || (rc = tmp.alloc(&d_tc, (size_t)nt)) || (rc = tmp.alloc(&d_tb, (size_t)nt + 1))) return rc;
+    hipError_t e = hipMemsetAsync(d_hard, 0, sizeof(int), c->stream);
     for (int i = 0; i < n_tracks && e == hipSuccess; ++i) {
         TextJob job;
         job.vals = b->d_track[tracks[i]]; job.out_off = b->d_out_off; job.chunk_len = b->d_len; job.tiles = b->d_tiles256; job.ntiles = nt;
         job.chrom_id = nullptr; job.chunk_start = nullptr; job.names = nullptr; job.name_off = nullptr; job.p10 = c->d_p10;
         job.write_zero = write_zero & 1; job.keep_before_nan = (write_zero >> 1) & 1;
         hipLaunchKernelGGL(tz_flags_count, dim3(nt), dim3(256), 0, c->stream, job, d_tc);
-        TRYS(dev_scan(c, d_tc, (long long)nt, d_tb, tmp));
+        if ((rc = dev_scan(c, d_tc, (long long)nt, d_tb, tmp))) return rc;
         unsigned long long nruns = 0;
         if ((e = hipMemcpyAsync(&nruns, d_tb + nt, sizeof nruns, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
-        dev_free(d_R); dev_free(d_C);
-        d_R = nullptr; d_C = nullptr;
-        TRYS(dev_alloc(&d_R, (size_t)nruns));
-        TRYS(dev_alloc(&d_C, (size_t)nruns));
+        d_R.reset(); d_C.reset();
+        if ((rc = dev_alloc(d_R, (size_t)nruns)) || (rc = dev_alloc(d_C, (size_t)nruns))) return rc;
         hipLaunchKernelGGL(tz_scatter_runs, dim3(nt), dim3(256), 0, c->stream, job, d_tb, d_R, d_C);
-        TRYS(dev_alloc(&seg.p[i], (size_t)b->total_bp));
+        if ((rc = dev_alloc(seg.p[i], (size_t)b->total_bp))) return rc;
         hipLaunchKernelGGL(tz_as_written, dim3((unsigned)((nruns + 255) / 256)), dim3(256), 0, c->stream, job, (long long)nruns, d_R, d_C,
                            seg.p[i], d_hard);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&hard, d_hard, sizeof hard, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_R); dev_free(d_C);
-    if (e != hipSuccess) { for (int q = 0; q < 4; ++q) dev_free(seg.p[q]); return fail(NATAC_E_HIP, "store_adopt: %s", hipGetErrorString(e)); }
-#undef TRYS
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "store_adopt: %s", hipGetErrorString(e));
     if (n_hard) *n_hard = hard;
-    if (hard) {      // a value the device cannot round like the text round trip would: nothing is adopted, the caller reads the file
-        for (int q = 0; q < 4; ++q) dev_free(seg.p[q]);
-        return NATAC_OK;
-    }
+    // a value the device cannot round like the text round trip would: nothing is adopted (the tracks go back), the caller reads the file
+    if (hard) return NATAC_OK;
     std::lock_guard<std::mutex> lk(s->mu);
-    s->segs.push_back(seg);
+    s->segs.push_back(std::move(seg));
     s->bytes += (long long)n_tracks * b->total_bp * (long long)sizeof(double);
     *segment = (int64_t)s->segs.size() - 1;
     return NATAC_OK;
@@ -3314,16 +3284,15 @@ int natac_store_read(natac_store *s, natac_ctx *c, int64_t n, const int64_t *seg
     }
     if ((size_t)total != out_values) return fail(NATAC_E_ARG, "destination holds %zu values, the regions %lld", out_values, total);
     if (total == 0) return NATAC_OK;
+    StreamTemps tmp(c);
     StoreRegion *d_reg = nullptr;
     double *d_out = nullptr;
     int rc;
-    if ((rc = dev_upload(c, &d_reg, reg.data(), reg.size()))) return rc;
-    if ((rc = dev_alloc(&d_out, (size_t)total))) { dev_free(d_reg); return rc; }
+    if ((rc = tmp.upload(&d_reg, reg.data(), reg.size())) || (rc = tmp.alloc(&d_out, (size_t)total))) return rc;
     hipLaunchKernelGGL(tz_store_gather, dim3((unsigned)n), dim3(256), 0, c->stream, d_reg, d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_reg); dev_free(d_out);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "store_read: %s", hipGetErrorString(e));
     return NATAC_OK;
 }
