@@ -13,6 +13,8 @@
  *         nucleoatac/multinomial_cov.pyx:20 calculateCov          -> natac_calculate_cov
  *   (3) `pyatac pwm`'s window counts (pyatac/get_pwm.py:21-40, tracks.py:179-201) -> natac_insertion_seq_counts
  *       and its background base counts (pyatac/seq.py:47-72)                   -> natac_base_counts
+ *   (4) `pyatac ins --smooth`'s smoothed insertions (pyatac/get_ins.py:20-32)  -> natac_run_ins_smooth
+ *       and `pyatac cov`'s fragment-centre coverage (pyatac/get_cov.py:21-37)   -> natac_run_center_cov
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -38,8 +40,9 @@ extern "C" {
 
 /* bumped whenever an entry point is added, removed or changes meaning (2: round 5 removed natac_run_nuc_occ, added natac_bg_tiling /
  * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
- * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`); the binding refuses another version */
-#define NATAC_ABI_VERSION 4
+ * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
+ * tracks and profile slots for `pyatac ins` / `cov`); the binding refuses another version */
+#define NATAC_ABI_VERSION 5
 
 enum {
     NATAC_OK = 0,
@@ -68,7 +71,9 @@ enum {
     NATAC_T_OCC_COV = 9,    /* OccChunk.getCov                       Occupancy.py:221-224 */
     NATAC_T_INS = 10,       /* int32 insertion counts, getInsertions pyatac/fragments.pyx:43-67 */
     NATAC_T_OCC_PREFILL = 11, /* smoothed_vals BEFORE the NaN fill (formed on the first download / track_ptr request) */
-    NATAC_T_COUNT = 12
+    NATAC_T_INS_SMOOTH = 12,  /* gaussian-smoothed insertions, `pyatac ins --smooth`   pyatac/get_ins.py:20-32 */
+    NATAC_T_CENTER_COV = 13,  /* fragment-centre coverage, `pyatac cov`               pyatac/get_cov.py:21-37 */
+    NATAC_T_COUNT = 14
 };
 
 /* per-grid-point arrays of the occupancy MLE (one value per `step` bases; chunk i occupies
@@ -87,7 +92,9 @@ enum {
     NATAC_K_INS = 6,
     NATAC_K_CAND = 7,
     NATAC_K_SIZE_HIST = 8,   /* insert-size histogram of natac_fragment_sizes */
-    NATAC_K_COUNT = 9
+    NATAC_K_INS_SMOOTH = 9,  /* natac_run_ins_smooth */
+    NATAC_K_CENTER_COV = 10, /* natac_run_center_cov */
+    NATAC_K_COUNT = 11
 };
 
 typedef struct natac_ctx natac_ctx;
@@ -150,6 +157,18 @@ int natac_run_nuc(natac_batch *b, double smooth_sd);
 int natac_run_occ(natac_batch *b);
 /* InsertionTrack.calculateInsertions (pyatac/tracks.py:164-168) for every chunk: fills INS. */
 int natac_run_ins(natac_batch *b, int lower, int upper);
+/* `pyatac ins --smooth S` for every chunk (_insHelperSmooth, pyatac/get_ins.py:20-32): the insertions of [start - h, end + h), h = M / 2,
+ * (both ends of every fragment with lower <= ilen < upper; ends outside the chromosome count like any other) smoothed by
+ * utils.smooth(..., window = "gaussian", mode = "valid", norm = True), pyatac/utils.py:23-52.  w[M] = scipy's gaussian(M, (M - 1) / 6.0)
+ * with M = S, or S + 1 when S is even (M odd, 1 <= M <= 4001); wsum = the window's 'valid' normaliser np.convolve(w, ones(M),
+ * 'valid')[0].  Every value is the fp64 sum of w[j] * count[x - h + j] divided by wsum.  The packing margin must hold every fragment
+ * with an end within h of a chunk.  Fills INS_SMOOTH.  Synchronous. */
+int natac_run_ins_smooth(natac_batch *b, int lower, int upper, const double *w, int M, double wsum);
+/* `pyatac cov` for every chunk (_covHelper, pyatac/get_cov.py:21-37, CoverageTrack.calculateCoverage, tracks.py:209-222): the number of
+ * fragment centres l + (ilen - 1) // 2 with lower <= ilen < upper within W / 2 of every base (the flat window of W taps, W + 1 when W is
+ * even), times mult = scale / float(W), one fp64 multiply of an exact count.  1 <= W <= 4001.  The packing margin must hold every
+ * fragment centred within W / 2 of a chunk.  Fills CENTER_COV.  Asynchronous. */
+int natac_run_center_cov(natac_batch *b, int lower, int upper, int W, double mult);
 /* Per-candidate statistics (needs natac_run_nuc first).  cand_chunk[k] = chunk index, cand_pos[k] = position
  * relative to the chunk start.  Outputs (host, length n_cand):
  *   lr   Nucleosome.getLR       NucleosomeCalling.py:110-122

@@ -20,6 +20,7 @@
 #include "natac_fuzzfit.hpp"
 #include "natac_bedtab.hpp"
 #include "natac_pwmfit.hpp"
+#include "natac_tracks.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -1462,7 +1463,7 @@ static int materialise_prefill(natac_batch *b) {
 // Every read of an output track goes through here: NATAC_E_STATE (before any HIP call) if it holds nothing, formed if pending.
 static int need_track(natac_batch *b, int t) {
     static const char *const names[NATAC_T_COUNT] = {"NUC_COV", "NFR_COV", "RAW", "BACKGROUND", "NORM", "SMOOTH", "OCC", "OCC_LOWER",
-                                                     "OCC_UPPER", "OCC_COV", "INS", "OCC_PREFILL"};
+                                                     "OCC_UPPER", "OCC_COV", "INS", "OCC_PREFILL", "INS_SMOOTH", "CENTER_COV"};
     if (t < 0 || t >= NATAC_T_COUNT) return fail(NATAC_E_ARG, "bad track id %d", t);
     if (b->out.track[t] == TS_EMPTY)
         return fail(NATAC_E_STATE, "track NATAC_T_%s holds nothing: no stage has written it and natac_batch_set_track has not", names[t]);
@@ -1716,6 +1717,59 @@ static int ins_launch(natac_batch *b, int lower, int upper) {
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
     b->out.track[NATAC_T_INS] = TS_RUN;
+    return NATAC_OK;
+}
+
+// the 1-kb tile table of the per-base track kernels (natac_tracks.hpp); the same table natac_smooth_same4 uses
+static int ensure_tiles1k(natac_batch *b) {
+    static_assert(natac_tracks::TR_TILE == 1024, "the track kernels share the 1-kb tile table");
+    if (b->d_tiles1k) return NATAC_OK;
+    return build_tiles(b, 1024, b->d_tiles1k, &b->n_tiles1k);
+}
+
+int natac_run_ins_smooth(natac_batch *b, int lower, int upper, const double *w, int M, double wsum) {
+    using namespace natac_tracks;
+    if (!b || !w) return fail(NATAC_E_ARG, "null argument");
+    if (M < 1 || M > TR_MAX_M || !(M & 1)) return fail(NATAC_E_ARG, "window needs an odd number of taps in [1, %d] (got %d)", TR_MAX_M, M);
+    for (int j = 0; j < M; ++j)
+        if (!std::isfinite(w[j])) return fail(NATAC_E_ARG, "window tap %d is not finite", j);
+    if (!(wsum > 0) || !std::isfinite(wsum)) return fail(NATAC_E_ARG, "window sum must be positive and finite (got %g)", wsum);
+    natac_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_track(b, NATAC_T_INS_SMOOTH)) || (rc = ensure_tiles1k(b))) return rc;
+    StreamTemps tmp(c);                // the window: on the device for this call only
+    double *d_w = nullptr;
+    if ((rc = tmp.upload(&d_w, w, (size_t)M))) return rc;
+    natac_ctx::Ev ev;
+    prof_begin(c, NATAC_K_INS_SMOOTH, ev, c->stream);
+    hipLaunchKernelGGL(natac_ins_smooth, dim3(b->n_tiles1k), dim3(TR_BLOCK), ins_smooth_lds(M), c->stream, b->d_tiles1k.get(), b->d_len.get(),
+                       b->d_frag_off.get(), b->d_lpos.get(), b->d_ilen.get(), b->d_centre.get(), b->d_out_off.get(), lower, upper, d_w, M, wsum,
+                       b->d_track[NATAC_T_INS_SMOOTH].get());
+    prof_end(c, ev);
+    HIPCHK(hipGetLastError());
+    b->out.track[NATAC_T_INS_SMOOTH] = TS_RUN;
+    return NATAC_OK;
+}
+
+int natac_run_center_cov(natac_batch *b, int lower, int upper, int W, double mult) {
+    using namespace natac_tracks;
+    if (!b) return fail(NATAC_E_ARG, "batch is NULL");
+    if (W < 1 || W > TR_MAX_W) return fail(NATAC_E_ARG, "window must be in [1, %d] (got %d)", TR_MAX_W, W);
+    if (!std::isfinite(mult)) return fail(NATAC_E_ARG, "multiplier must be finite");
+    natac_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_track(b, NATAC_T_CENTER_COV)) || (rc = ensure_tiles1k(b))) return rc;
+    const int h = W / 2;
+    natac_ctx::Ev ev;
+    prof_begin(c, NATAC_K_CENTER_COV, ev, c->stream);
+    hipLaunchKernelGGL(natac_center_cov, dim3(b->n_tiles1k), dim3(TR_BLOCK), center_cov_lds(h), c->stream, b->d_tiles1k.get(), b->d_len.get(),
+                       b->d_frag_off.get(), b->d_ilen.get(), b->d_centre.get(), b->d_out_off.get(), lower, upper, h, mult,
+                       b->d_track[NATAC_T_CENTER_COV].get());
+    prof_end(c, ev);
+    HIPCHK(hipGetLastError());
+    b->out.track[NATAC_T_CENTER_COV] = TS_RUN;
     return NATAC_OK;
 }
 

@@ -480,6 +480,20 @@ class DeviceBatch(object):
     def run_ins(self, lower=0, upper=2000):
         L.check(self._lib.natac_run_ins(self._h, int(lower), int(upper)))
 
+    def run_ins_smooth(self, w, lower=0, upper=2000, wsum=None):
+        """`pyatac ins --smooth` for every chunk (natac_run_ins_smooth): the insertions of [start - M//2, end + M//2) smoothed by the
+        odd-length window w and divided by wsum (default: np.convolve(w, ones(M), 'valid')[0], utils.smooth's norm=True).  The batch
+        must be packed with a margin that holds every fragment with an end within M//2 of a chunk.  Fills T_INS_SMOOTH."""
+        w = _f64(w)
+        if wsum is None:
+            wsum = float(np.convolve(w, np.ones(w.shape[0]), "valid")[0]) if w.shape[0] else 0.0
+        L.check(self._lib.natac_run_ins_smooth(self._h, int(lower), int(upper), _ptr(w), w.shape[0], float(wsum)))
+
+    def run_center_cov(self, window, mult, lower=0, upper=2000):
+        """`pyatac cov` for every chunk (natac_run_center_cov): fragment centres within window//2 of every base times mult
+        (scale / float(window)).  Fills T_CENTER_COV."""
+        L.check(self._lib.natac_run_center_cov(self._h, int(lower), int(upper), int(window), float(mult)))
+
     def run_candidates(self, cand_chunk, cand_pos):
         cc = np.ascontiguousarray(cand_chunk, dtype=np.int32)
         cp = np.ascontiguousarray(cand_pos, dtype=np.int32)

@@ -1,5 +1,6 @@
-"""`pyatac pwm | sizes` command line with the reference's flag names and defaults (pyatac/cli.py:111-173).  These are the two pyatac
-tools whose outputs feed `nucleoatac occ` / `nuc` (--pwm, --sizes); the other pyatac tools are not part of this package."""
+"""`pyatac pwm | sizes | ins | cov` command line with the reference's flag names and defaults (pyatac/cli.py:111-173, 310-352).  `pwm`
+and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov` write the per-base insertion and
+fragment-centre coverage tracks.  The other pyatac tools (bias, signal, counts, nucleotide, vplot) are not part of this package."""
 import argparse
 import sys
 
@@ -30,14 +31,44 @@ def add_sizes_parser(sub):
     p.add_argument("--no_plot", action="store_true", default=False, help="accepted for compatibility; plots are never made")
 
 
+def _add_track_options(p):
+    p.add_argument("--bam", metavar="bam_file", required=True, help="Accepts sorted BAM file (or a FragmentStore .npz)")
+    p.add_argument("--bed", metavar="bed_file", help="Regions in which to get insertions")
+    p.add_argument("--out", metavar="basename")
+    p.add_argument("--cores", metavar="int", default=1, type=int, help="accepted for compatibility; the GPU replaces the pool")
+    p.add_argument("--lower", metavar="int", default=0, type=int, help="lower limit on insert size")
+    p.add_argument("--upper", metavar="int", default=2000, type=int, help="upper limit on insert size")
+
+
+def add_ins_parser(sub):
+    p = sub.add_parser("ins", help="pyatac function-- get insertions")
+    _add_track_options(p)
+    p.add_argument("--smooth", metavar="int", type=int, help="smoothing window for guassian smoothing.  default is no smoothing")
+    p.add_argument("--not_atac", action="store_false", dest="atac", default=True, help="Don't use atac offsets")
+
+
+def add_cov_parser(sub):
+    p = sub.add_parser("cov", help="pyatac function-- get coverage")
+    _add_track_options(p)
+    p.add_argument("--window", metavar="int", type=int, default=121,
+                   help="window for flat smoothing of coverage.  default is 121, should be odd")
+    p.add_argument("--scale", metavar="float", type=float, default=10,
+                   help="scaling value.  default is 10, corresponding to signal corresponding to # of fragment centers per 10 bp. "
+                        "Use 1 for fragments per 1 bp.")
+    p.add_argument("--not_atac", action="store_false", dest="atac", default=True, help="Don't use atac offsets")
+
+
 def pyatac_parser():
     from .. import __version__
-    parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: fit the Tn5 PWM and the fragment-size distribution")
+    parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution and the per-base "
+                                                                "insertion and coverage tracks")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
     add_pwm_parser(sub)
     add_sizes_parser(sub)
+    add_ins_parser(sub)
+    add_cov_parser(sub)
     return parser
 
 
@@ -55,6 +86,19 @@ def pyatac_main(args):
         print("---------Getting fragment sizes---------------------------------------")
         print("plots are not produced: only the .fragmentsizes.txt file is written")
         get_sizes(args)
+    elif args.call in ("ins", "cov"):
+        from .trackfiles import MissingChromosomeError
+        print("---------Getting insertions to make track---------------------------------------")
+        try:
+            if args.call == "ins":
+                from .get_ins import get_ins
+                get_ins(args)
+            else:
+                from .get_cov import get_cov
+                get_cov(args)
+        except (MissingChromosomeError, ValueError) as e:
+            sys.stderr.write("pyatac %s: %s\n" % (args.call, e))
+            return 1
     return 0
 
 
