@@ -15,6 +15,7 @@
  *       and its background base counts (pyatac/seq.py:47-72)                   -> natac_base_counts
  *   (4) `pyatac ins --smooth`'s smoothed insertions (pyatac/get_ins.py:20-32)  -> natac_run_ins_smooth
  *       and `pyatac cov`'s fragment-centre coverage (pyatac/get_cov.py:21-37)   -> natac_run_center_cov
+ *   (5) `pyatac bias`'s Tn5 bias track (pyatac/make_bias_track.py, bias.py:85-92) -> natac_run_pwm_track
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -41,8 +42,9 @@ extern "C" {
 /* bumped whenever an entry point is added, removed or changes meaning (2: round 5 removed natac_run_nuc_occ, added natac_bg_tiling /
  * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
- * tracks and profile slots for `pyatac ins` / `cov`); the binding refuses another version */
-#define NATAC_ABI_VERSION 5
+ * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`); the binding
+ * refuses another version */
+#define NATAC_ABI_VERSION 6
 
 enum {
     NATAC_OK = 0,
@@ -73,7 +75,8 @@ enum {
     NATAC_T_OCC_PREFILL = 11, /* smoothed_vals BEFORE the NaN fill (formed on the first download / track_ptr request) */
     NATAC_T_INS_SMOOTH = 12,  /* gaussian-smoothed insertions, `pyatac ins --smooth`   pyatac/get_ins.py:20-32 */
     NATAC_T_CENTER_COV = 13,  /* fragment-centre coverage, `pyatac cov`               pyatac/get_cov.py:21-37 */
-    NATAC_T_COUNT = 14
+    NATAC_T_BIAS = 14,        /* log Tn5 bias of every base, `pyatac bias`            pyatac/bias.py:85-92 */
+    NATAC_T_COUNT = 15
 };
 
 /* per-grid-point arrays of the occupancy MLE (one value per `step` bases; chunk i occupies
@@ -94,7 +97,8 @@ enum {
     NATAC_K_SIZE_HIST = 8,   /* insert-size histogram of natac_fragment_sizes */
     NATAC_K_INS_SMOOTH = 9,  /* natac_run_ins_smooth */
     NATAC_K_CENTER_COV = 10, /* natac_run_center_cov */
-    NATAC_K_COUNT = 11
+    NATAC_K_PWM_TRACK = 11,  /* natac_run_pwm_track */
+    NATAC_K_COUNT = 12
 };
 
 typedef struct natac_ctx natac_ctx;
@@ -169,6 +173,15 @@ int natac_run_ins_smooth(natac_batch *b, int lower, int upper, const double *w, 
  * even), times mult = scale / float(W), one fp64 multiply of an exact count.  1 <= W <= 4001.  The packing margin must hold every
  * fragment centred within W / 2 of a chunk.  Fills CENTER_COV.  Asynchronous. */
 int natac_run_center_cov(natac_batch *b, int lower, int upper, int W, double mult);
+/* `pyatac bias` for every chunk (InsertionBiasTrack.computeBias, pyatac/bias.py:85-92, after its slop and before its trim): value x of
+ * chunk i is the sum over k < K of log_pwm[row(base x + k), k], where seq[seq_off[i] .. seq_off[i + 1]) holds the chunk_len[i] + K - 1
+ * bases under the chunk's track (host memory; raw FASTA bytes: lower case counts as upper case, a base that is none of the row letters
+ * adds 0).  log_pwm[nrow x K] = log(PWM.mat), nucleotides[nrow] its row letters, all different; nrow <= 255, nrow * K <= 4096.  Per row
+ * a running sum over k, rows added in order: bit-identical to natac_pwm_bias on the same (upper-case) bases.  The batch needs no
+ * fragments.  seq_off[0] != 0, a window of another length, K < 1, nrow < 1, a table entry that is not finite: NATAC_E_ARG and nothing
+ * is launched.  Fills BIAS.  Synchronous. */
+int natac_run_pwm_track(natac_batch *b, const int64_t *seq_off, const uint8_t *seq, const double *log_pwm, const uint8_t *nucleotides,
+                        int nrow, int K);
 /* Per-candidate statistics (needs natac_run_nuc first).  cand_chunk[k] = chunk index, cand_pos[k] = position
  * relative to the chunk start.  Outputs (host, length n_cand):
  *   lr   Nucleosome.getLR       NucleosomeCalling.py:110-122

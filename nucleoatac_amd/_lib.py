@@ -7,18 +7,18 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 5      # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 6      # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
 T_NUC_COV, T_NFR_COV, T_RAW, T_BACKGROUND, T_NORM, T_SMOOTH = 0, 1, 2, 3, 4, 5
 T_OCC, T_OCC_LOWER, T_OCC_UPPER, T_OCC_COV, T_INS, T_OCC_PREFILL = 6, 7, 8, 9, 10, 11
-T_INS_SMOOTH, T_CENTER_COV = 12, 13
+T_INS_SMOOTH, T_CENTER_COV, T_BIAS = 12, 13, 14
 G_OCC, G_LOWER, G_UPPER = 0, 1, 2
 K_FRAG_GATHER, K_BACKGROUND, K_SMOOTH_NUC, K_OCC_MLE, K_OCC_SMOOTH, K_OCC_FILL, K_INS, K_CAND, K_SIZE_HIST = range(9)
-K_INS_SMOOTH, K_CENTER_COV = 9, 10
+K_INS_SMOOTH, K_CENTER_COV, K_PWM_TRACK = 9, 10, 11
 KERNEL_NAMES = ["frag_gather", "background", "smooth_nuc", "occ_mle", "occ_smooth", "occ_fill", "insertions",
-                "candidates", "size_hist", "ins_smooth", "center_cov"]
+                "candidates", "size_hist", "ins_smooth", "center_cov", "pwm_track"]
 
 _vp, _i32, _i64, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_size_t
 _pp = C.POINTER(C.c_void_p)
@@ -47,6 +47,7 @@ SIGNATURES = {
     "natac_run_ins": (C.c_int, [_vp, C.c_int, C.c_int]),
     "natac_run_ins_smooth": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _f64]),
     "natac_run_center_cov": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64]),
+    "natac_run_pwm_track": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),
     "natac_store_create": (C.c_int, [_pp]),
     "natac_store_free": (None, [_vp]),
     "natac_store_adopt": (C.c_int, [_vp, _vp, _i32, _vp, C.c_int, C.POINTER(_i64), C.POINTER(_i32)]),

@@ -1463,7 +1463,7 @@ static int materialise_prefill(natac_batch *b) {
 // Every read of an output track goes through here: NATAC_E_STATE (before any HIP call) if it holds nothing, formed if pending.
 static int need_track(natac_batch *b, int t) {
     static const char *const names[NATAC_T_COUNT] = {"NUC_COV", "NFR_COV", "RAW", "BACKGROUND", "NORM", "SMOOTH", "OCC", "OCC_LOWER",
-                                                     "OCC_UPPER", "OCC_COV", "INS", "OCC_PREFILL", "INS_SMOOTH", "CENTER_COV"};
+                                                     "OCC_UPPER", "OCC_COV", "INS", "OCC_PREFILL", "INS_SMOOTH", "CENTER_COV", "BIAS"};
     if (t < 0 || t >= NATAC_T_COUNT) return fail(NATAC_E_ARG, "bad track id %d", t);
     if (b->out.track[t] == TS_EMPTY)
         return fail(NATAC_E_STATE, "track NATAC_T_%s holds nothing: no stage has written it and natac_batch_set_track has not", names[t]);
@@ -1770,6 +1770,44 @@ int natac_run_center_cov(natac_batch *b, int lower, int upper, int W, double mul
     prof_end(c, ev);
     HIPCHK(hipGetLastError());
     b->out.track[NATAC_T_CENTER_COV] = TS_RUN;
+    return NATAC_OK;
+}
+
+int natac_run_pwm_track(natac_batch *b, const int64_t *seq_off, const uint8_t *seq, const double *log_pwm, const uint8_t *nucleotides, int nrow,
+                        int K) {
+    using namespace natac_tracks;
+    if (!b || !seq_off || !seq || !log_pwm || !nucleotides) return fail(NATAC_E_ARG, "null argument");
+    if (K < 1 || nrow < 1 || nrow > PT_MAX_ROWS || (long long)nrow * K > PT_MAX_CELLS)
+        return fail(NATAC_E_ARG, "PWM needs 1 <= rows <= %d, 1 <= width and rows * width <= %d (got %d x %d)", PT_MAX_ROWS, PT_MAX_CELLS, nrow, K);
+    for (int j = 0; j < nrow * K; ++j)
+        if (!std::isfinite(log_pwm[j])) return fail(NATAC_E_ARG, "log PWM entry (%d, %d) is not finite", j / K, j % K);
+    for (int r = 1; r < nrow; ++r)
+        for (int q = 0; q < r; ++q)
+            if (nucleotides[q] == nucleotides[r]) return fail(NATAC_E_ARG, "PWM rows %d and %d have the same letter", q, r);
+    if (seq_off[0] != 0) return fail(NATAC_E_ARG, "seq_off[0] must be 0");
+    for (int i = 0; i < b->nc; ++i)
+        if (seq_off[i + 1] - seq_off[i] != (int64_t)b->h_len[i] + K - 1)
+            return fail(NATAC_E_ARG, "sequence window of chunk %d must hold %lld bases (its length + K - 1)", i, (long long)b->h_len[i] + K - 1);
+    natac_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_track(b, NATAC_T_BIAS)) || (rc = ensure_tiles1k(b))) return rc;
+    StreamTemps tmp(c);                // sequence, offsets, table and letters: on the device for this call only
+    unsigned char *d_s = nullptr, *d_n = nullptr;
+    long long *d_so = nullptr;
+    double *d_p = nullptr;
+    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)seq_off[b->nc])) ||
+        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)b->nc + 1)) ||
+        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) || (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)))
+        return rc;
+    natac_ctx::Ev ev;
+    prof_begin(c, NATAC_K_PWM_TRACK, ev, c->stream);
+    hipLaunchKernelGGL(natac_pwm_track, dim3(b->n_tiles1k), dim3(TR_BLOCK), pwm_track_lds(nrow, K), c->stream, b->d_tiles1k.get(), b->d_len.get(),
+                       d_so, d_s, b->d_out_off.get(), d_p, d_n, nrow, K, b->d_track[NATAC_T_BIAS].get());
+    prof_end(c, ev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));     // the host arrays may be released by the caller after return
+    b->out.track[NATAC_T_BIAS] = TS_RUN;
     return NATAC_OK;
 }
 

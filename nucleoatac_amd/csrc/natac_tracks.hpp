@@ -1,8 +1,11 @@
-// natac_tracks.hpp -- the two per-base tracks of `pyatac ins --smooth` and `pyatac cov` (pyatac/get_ins.py, get_cov.py of the reference):
+// natac_tracks.hpp -- the per-base tracks of `pyatac ins --smooth`, `pyatac cov` and `pyatac bias` (pyatac/get_ins.py, get_cov.py,
+// make_bias_track.py of the reference):
 //   natac_ins_smooth   utils.smooth(insertions of [start - h, end + h), M, window="gaussian", mode="valid", norm=True)
 //                      (get_ins.py:20-32, utils.py:23-52, fragments.pyx:43-67), h = M // 2
 //   natac_center_cov   the flat-window count of fragment centres within h of every base times scale / W
 //                      (get_cov.py:21-37, tracks.py:209-222, fragments.pyx:17-40), h = W // 2
+//   natac_pwm_track    InsertionBiasTrack.computeBias (bias.py:85-92, seq.py:37-45): the log PWM score of every K-base window of the
+//                      sequence under the chunk; it reads no fragments (see the kernel)
 // One workgroup per (chunk, tile of TR_TILE bases), the int2 tile table of the other tiled kernels.  The workgroup finds the fragments
 // that can reach its tile plus halo by a wave-wide search of the chunk's centre-sorted fragments, counts them into an int32 LDS
 // histogram of the tile and its halo (LDS integer atomics: exact, independent of fragment order), and every lane then forms its outputs
@@ -18,10 +21,16 @@ constexpr int TR_PER = TR_TILE / TR_BLOCK;
 constexpr int TR_MAX_M = 4001;          // longest gaussian window (taps); the LDS holds it and the tile + 2 * (M / 2) counts
 constexpr int TR_MAX_W = 4001;          // widest flat window (W + 1 taps when W is even)
 
+constexpr int PT_MAX_CELLS = 4096;      // nrow * K cells of the log PWM held in LDS (32 KiB of doubles); so K <= 4096
+constexpr int PT_MAX_ROWS = 255;        // a base's row index is one byte, and the value nrow means "no row"
+
 // LDS bytes of natac_ins_smooth for an M-tap window (the window's doubles first, 8-byte aligned)
 inline size_t ins_smooth_lds(int M) { return (size_t)M * sizeof(double) + (size_t)(TR_TILE + 2 * (M / 2)) * sizeof(int); }
 // LDS bytes of natac_center_cov for half-width h: the exclusive prefix of the tile + halo counts (one more slot) + 4 wave totals
 inline size_t center_cov_lds(int h) { return (size_t)(TR_TILE + 2 * h + 1 + 4) * sizeof(int); }
+
+// LDS bytes of natac_pwm_track: the nrow x K table (doubles first) + one row index per base of the tile and its K - 1 bases of overhang
+inline size_t pwm_track_lds(int nrow, int K) { return (size_t)nrow * K * sizeof(double) + (size_t)(TR_TILE + K - 1); }
 
 // first index i in [lo, hi) with a[i] >= key (a non-decreasing there), hi if none.  Every lane of the wave calls it with the same
 // arguments and gets the same answer: each round the 64 lanes probe 64 evenly spaced points, so a range of n shrinks to n / 65 + 1.
@@ -168,6 +177,63 @@ __global__ void __launch_bounds__(TR_BLOCK) natac_center_cov(const int2 *__restr
     block_exclusive_scan(s_p, span, s_tot);
     double *o = out + out_off[chunk] + x0;
     for (int x = threadIdx.x; x < n; x += TR_BLOCK) o[x] = (double)(s_p[x + 2 * h + 1] - s_p[x]) * mult;
+}
+
+// Tn5 bias track.  seq[seq_off[chunk] .. seq_off[chunk + 1]) holds the L + K - 1 bases under the chunk's L outputs (any case); output x
+// of the chunk scores bases x .. x + K - 1.  The tile's n + K - 1 bases are read from global memory once: upper-cased and mapped to the
+// index of the PWM row with that letter (nrow: no row, the base adds 0), one byte each in LDS, next to the whole nrow x K table.  Each
+// lane then forms its TR_PER outputs from LDS alone, with natac_pwm_score's association -- per row a running sum over k ascending, the
+// rows added in order -- so the values are that kernel's bit for bit (a row whose letter does not match adds nothing in either).  The
+// row letters must differ from one another (the host checks): a base then has one row at most.
+__global__ void __launch_bounds__(TR_BLOCK) natac_pwm_track(const int2 *__restrict__ tiles, const int *__restrict__ chunk_len,
+                                                            const long long *__restrict__ seq_off, const unsigned char *__restrict__ seq,
+                                                            const long long *__restrict__ out_off, const double *__restrict__ logpwm,
+                                                            const unsigned char *__restrict__ nucs, int nrow, int K,
+                                                            double *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tr_smem[];
+    double *s_tab = (double *)tr_smem;
+    unsigned char *s_row = tr_smem + (size_t)nrow * K * sizeof(double);   // [TR_TILE + K - 1]
+    const int2 t = tiles[blockIdx.x];
+    const int chunk = t.x, x0 = t.y;
+    const int L = chunk_len[chunk];
+    const int n = min(TR_TILE, L - x0);
+    const int span = n + K - 1;                      // x0 + span <= L + K - 1, the chunk's bases
+    const unsigned char *s = seq + seq_off[chunk] + x0;
+    for (int j = threadIdx.x; j < nrow * K; j += TR_BLOCK) s_tab[j] = logpwm[j];
+    for (int i = threadIdx.x; i < span; i += TR_BLOCK) {
+        unsigned char c = s[i];
+        if (c >= 'a' && c <= 'z') c -= 'a' - 'A';
+        int row = nrow;
+        for (int r = 0; r < nrow; ++r)
+            if (nucs[r] == c) row = r;
+        s_row[i] = (unsigned char)row;
+    }
+    __syncthreads();
+    // output x = threadIdx.x + 256 q reads rows x .. x + K - 1; past the tile's n outputs that stays inside the TR_TILE + K - 1 bytes and
+    // the sums are dropped
+    double acc[TR_PER];
+#pragma unroll
+    for (int q = 0; q < TR_PER; ++q) acc[q] = 0.0;
+    for (int r = 0; r < nrow; ++r) {
+        const double *tr = s_tab + r * K;
+        double rs[TR_PER];
+#pragma unroll
+        for (int q = 0; q < TR_PER; ++q) rs[q] = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const double v = tr[k];
+#pragma unroll
+            for (int q = 0; q < TR_PER; ++q)
+                if (s_row[threadIdx.x + q * TR_BLOCK + k] == r) rs[q] += v;
+        }
+#pragma unroll
+        for (int q = 0; q < TR_PER; ++q) acc[q] += rs[q];
+    }
+    double *o = out + out_off[chunk] + x0;
+#pragma unroll
+    for (int q = 0; q < TR_PER; ++q) {
+        const int x = threadIdx.x + q * TR_BLOCK;
+        if (x < n) o[x] = acc[q];
+    }
 }
 
 }  // namespace natac_tracks

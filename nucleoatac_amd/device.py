@@ -494,8 +494,26 @@ class DeviceBatch(object):
         (scale / float(window)).  Fills T_CENTER_COV."""
         L.check(self._lib.natac_run_center_cov(self._h, int(lower), int(upper), int(window), float(mult)))
 
+    def run_pwm_track(self, seq_off, seq, pwm_log, nucleotides):
+        """`pyatac bias` for every chunk (natac_run_pwm_track): seq[seq_off[i]:seq_off[i+1]] = the chunk_len[i] + K - 1 bases under
+        chunk i's track (uint8, any case), pwm_log = log(PWM.mat) of shape (nrow, K), nucleotides = its row letters (a uint8 array, or
+        the PWM's list of one-letter strings).  The batch needs no fragments.  Fills T_BIAS, bit-identical to Context.pwm_bias."""
+        so = np.ascontiguousarray(seq_off, dtype=np.int64)
+        sq = np.ascontiguousarray(seq, dtype=np.uint8)
+        logp = _f64(pwm_log)
+        if not isinstance(nucleotides, np.ndarray):
+            if set(len(x) for x in nucleotides) != {1}:
+                raise NotImplementedError("k-mer PWMs are not supported by natac_run_pwm_track: single-nucleotide PWMs only")
+            nucleotides = np.frombuffer("".join(nucleotides).encode("ascii"), dtype=np.uint8)
+        nucs = np.ascontiguousarray(nucleotides, dtype=np.uint8)
+        if logp.ndim != 2 or nucs.shape != (logp.shape[0],):
+            raise ValueError("pwm_log must be (nrow, K) with one letter per row")
+        if so.shape != (self.packed.n_chunks + 1,) or so[-1] != sq.shape[0]:
+            raise ValueError("seq_off needs n_chunks + 1 entries that end at len(seq)")
+        L.check(self._lib.natac_run_pwm_track(self._h, _ptr(so), _ptr(sq), _ptr(logp), _ptr(nucs), logp.shape[0], logp.shape[1]))
+
     def run_candidates(self, cand_chunk, cand_pos):
-        cc = np.ascontiguousarray(cand_chunk, dtype=np.int32)
+        cc =np.ascontiguousarray(cand_chunk, dtype=np.int32)
         cp = np.ascontiguousarray(cand_pos, dtype=np.int32)
         if cc.shape != cp.shape:
             raise ValueError("cand_chunk / cand_pos shape mismatch")

@@ -1,6 +1,7 @@
-"""`pyatac pwm | sizes | ins | cov` command line with the reference's flag names and defaults (pyatac/cli.py:111-173, 310-352).  `pwm`
-and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov` write the per-base insertion and
-fragment-centre coverage tracks.  The other pyatac tools (bias, signal, counts, nucleotide, vplot) are not part of this package."""
+"""`pyatac pwm | sizes | ins | cov | bias` command line with the reference's flag names and defaults (pyatac/cli.py:111-173, 310-352).
+`pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov` write the per-base insertion and
+fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM.  The other pyatac tools (signal,
+counts, nucleotide, vplot) are not part of this package."""
 import argparse
 import sys
 
@@ -58,10 +59,19 @@ def add_cov_parser(sub):
     p.add_argument("--not_atac", action="store_false", dest="atac", default=True, help="Don't use atac offsets")
 
 
+def add_bias_parser(sub):
+    p = sub.add_parser("bias", help="pyatac function-- compute Tn5 bias score")
+    p.add_argument("--fasta", metavar="fasta_file", required=True, help="Accepts fasta file (or a FastaStore .npz)")
+    p.add_argument("--pwm", metavar="Tn5_PWM", default="Human", help="PWM descriptor file or built-in name. Default is Human")
+    p.add_argument("--bed", metavar="bed_file", help="Find only bias for these regions of the genome")
+    p.add_argument("--out", metavar="output_basename", help="Basename for output")
+    p.add_argument("--cores", metavar="int", default=1, type=int, help="accepted for compatibility; the GPU replaces the pool")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution and the per-base "
-                                                                "insertion and coverage tracks")
+                                                                "insertion, coverage and Tn5 bias tracks")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -69,6 +79,7 @@ def pyatac_parser():
     add_sizes_parser(sub)
     add_ins_parser(sub)
     add_cov_parser(sub)
+    add_bias_parser(sub)
     return parser
 
 
@@ -98,6 +109,14 @@ def pyatac_main(args):
                 get_cov(args)
         except (MissingChromosomeError, ValueError) as e:
             sys.stderr.write("pyatac %s: %s\n" % (args.call, e))
+            return 1
+    elif args.call == "bias":
+        from .make_bias_track import BiasTrackError, make_bias_track
+        print("---------Making Tn5 Bias Track---------------------------------------")
+        try:
+            make_bias_track(args)
+        except BiasTrackError as e:
+            sys.stderr.write("pyatac bias: %s\n" % e)
             return 1
     return 0
 

@@ -1,4 +1,5 @@
-"""The driver behind `pyatac ins` and `pyatac cov`: regions -> packed sub-batches -> one track kernel per sub-batch -> bedGraph.gz + .tbi.
+"""The driver behind `pyatac ins`, `pyatac cov` and (write_packed_track_file) `pyatac bias`: regions -> packed sub-batches -> one track
+kernel per sub-batch -> bedGraph.gz + .tbi.
 
 The reference maps every 1-kb chunk (or merged BED region) on a process pool, re-reads the BAM per chunk and writes every region with
 its own Track.write_track into a text file that it then compresses and indexes (get_ins.py:49-85, get_cov.py:40-76).  Here the BAM is
@@ -72,12 +73,18 @@ def write_track_file(path, chunks, bam, run, halo, lower, upper, atac, max_chunk
     """run(batch) -> track id, for every sub-batch of `chunks`; writes `path` (BGZF) and `path`.tbi.  `halo`: how far past a region
     the kernel reads fragment ends or centres (the packing margin covers it).  timing (a dict) gets the seconds of packing, of the
     device calls and of the writer, and the sub-batch count."""
+    st = FragmentStore.open(bam)
+    margin = max(int(upper), 1) + max(0, -int(lower)) + int(halo) + 2
+    return write_packed_track_file(path, chunks, lambda sub: _pack(sub, st, margin, atac), run, max_chunks=max_chunks, timing=timing)
+
+
+def write_packed_track_file(path, chunks, pack_chunks, run, max_chunks=None, timing=None):
+    """write_track_file for any packer: pack_chunks(sub) -> the PackedChunks of a sub-batch (called on the prefetch threads), run(batch)
+    -> the id of the track it filled (the batch's PackedChunks is batch.packed)."""
     from .. import get_context
     from ..pipeline import prefetch_map, sub_batches
     from ..writer import BGZF_EOF, TbiBuilder, tabix_index, write_bedgraph
     ctx = get_context()
-    st = FragmentStore.open(bam)
-    margin = max(int(upper), 1) + max(0, -int(lower)) + int(halo) + 2
     t = timing if timing is not None else {}
     for k in ("pack_s", "device_s", "writer_s"):
         t.setdefault(k, 0.0)
@@ -85,7 +92,7 @@ def write_track_file(path, chunks, bam, run, halo, lower, upper, atac, max_chunk
 
     def pack(sub):
         t0 = time.perf_counter()
-        pk = _pack(sub, st, margin, atac)
+        pk = pack_chunks(sub)
         return pk, time.perf_counter() - t0
 
     tbi = TbiBuilder()
