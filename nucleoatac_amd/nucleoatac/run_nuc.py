@@ -6,7 +6,6 @@ statistics (LR, z) come from the device, the thresholds of `findAllNucs` (Nucleo
 sub-batches with numpy, `reduce_peaks` and the per-nucleosome L-BFGS fuzziness fit (NucleosomeCalling.py:137-194, host by
 SURVEY.md section 8f row 3) run per chunk, the fits on the `--cores` process pool while the GPU works on the next sub-batches."""
 import os
-import shutil
 
 import numpy as np
 
@@ -19,9 +18,9 @@ from ..pyatac.fragmentsizes import FragmentSizes
 from ..pyatac.utils import read_chrom_sizes_from_bam, read_chrom_sizes_from_fasta, reduce_peaks
 from ..pyatac.VMat import VMat
 from ..shard import balanced_ranges, barrier, broadcast_object, ensure_distributed, env_rank_world, shared_fragment_store
-from ..writer import bgzip_file, tabix_index, write_bed_rows, write_bedgraph
+from ..writer import TrackFile, bgzip_file, concat_parts, tabix_index, write_bed_rows, write_track_index
+from .driver import DEVICE_WRITER, Phases, TrackWriter, chrom_ids, finish_tracks, prefetch_inputs
 from .NucleosomeCalling import NucParameters, fit_fuzz_tasks, nuc_batch, read_occ_tracks_many
-from .run_occ import DEVICE_WRITER, _Phases, _Writer, finish_indexes
 
 LAST_TIMINGS = {}
 
@@ -32,7 +31,6 @@ BATCH_CHUNKS = int(os.environ.get("NATAC_BATCH_CHUNKS", "4096"))
 # look-ahead 21.5, with it 17.1; 18 Mbp 14.7; 9 Mbp 14.4; 4.5 Mbp 15.6 (2-kb windows: 4,096 chunks are 8.7 Mbp either way).
 NUC_SUB_BP = int(os.environ.get("NATAC_NUC_SUB_BP", "9000000"))
 N_CONTEXTS = int(os.environ.get("NATAC_CONTEXTS", "3"))
-COMPRESS_LEVEL = 4
 
 
 def _nucHelper(arg):
@@ -134,13 +132,8 @@ def batch_calls(r, params, pool=None, pool_workers=1):
 
 
 def run_nuc(args):
-    ph = _Phases(LAST_TIMINGS)
-    if env_rank_world()[2] == 0 and isinstance(args.bam, str):      # the node's publishing rank
-        from ..pyatac.fragments import FragmentStore
-        FragmentStore.prefetch(args.bam)       # it decodes (shard.shared_fragment_store): start now, next to the FASTA index / BED reads
-    if getattr(args, "fasta", None):
-        from ..pyatac.seq import FastaStore
-        FastaStore.prefetch(args.fasta)        # the genome loads on its own thread; the BED file only needs the record lengths
+    ph = Phases(LAST_TIMINGS)
+    prefetch_inputs(args)
     vmat = VMat.open(args.vmat)
     chrs = read_chrom_sizes_from_fasta(args.fasta) if args.fasta else read_chrom_sizes_from_bam(args.bam)
     pwm = PWM.open(args.pwm)
@@ -183,15 +176,12 @@ def run_nuc(args):
     track_of = {"nucleoatac_signal": L.T_NORM, "nucleoatac_signal.smooth": L.T_SMOOTH, "nucleoatac_background": L.T_BACKGROUND,
                 "nucleoatac_raw": L.T_RAW}
     track_of = {n: t for n, t in track_of.items() if n in outputs}
-    paths = {n: args.out + "." + n + ".bedgraph.gz" + suffix for n in track_of}
+    files = {n: TrackFile(args.out + "." + n + ".bedgraph.gz" + suffix, last=(rank == world - 1)) for n in track_of}
     call_paths = {n: args.out + "." + n + ".bed" + suffix for n in outputs if n.startswith("nucpos")}
     for p in call_paths.values():
         open(p, "w").close()
     # sub-batches: <= BATCH_CHUNKS chunks and NUC_SUB_BP bases (pipeline.sub_batches)
     parts = sub_batches(mine, BATCH_CHUNKS, NUC_SUB_BP if "NATAC_BATCH_CHUNKS" not in os.environ else 1 << 62)
-    if not parts:
-        for n in track_of:
-            write_bedgraph(paths[n], [], [], [0], np.zeros(0), append=False, compress=COMPRESS_LEVEL, finish=(rank == world - 1))
 
     calls_s = [0.0]
 
@@ -210,9 +200,7 @@ def run_nuc(args):
 
     def calls_finish(st):        # waits for the fits; rows in chunk / position order
         part = st["part"]
-        names = sorted(set(c.chrom for c in part))
-        idx = {c: i for i, c in enumerate(names)}
-        cid_of = np.array([idx[c.chrom] for c in part], dtype=np.int32)
+        names, cid_of = chrom_ids(part)
         start_of = np.array([c.start for c in part], dtype=np.int64)
         for name, (kc, kp, vals) in batch_calls_finish(st).items():
             if len(kc):
@@ -231,7 +219,7 @@ def run_nuc(args):
                         peaks=dict(min_signal=0, sep=params.redundant_sep, boundary=params.nonredundant_sep // 2,
                                    order=params.redundant_sep // 2), tracks=need,
                         text_tracks=tuple(track_of.values()) if DEVICE_WRITER else ())
-        writer = _Writer(paths, track_of, calls, len(parts), rank == world - 1)
+        writer = TrackWriter(files, track_of, calls)
         writer.start()
         fa_chrs = read_chrom_sizes_from_fasta(params.fasta) if params.fasta is not None else params.chrs
 
@@ -256,21 +244,17 @@ def run_nuc(args):
     finally:
         if pool is not None:             # also on a failure: the spawn workers of the fit pool must not outlive the run
             pool.shutdown()
-    to_index = finish_indexes(writer if parts else None, list(track_of), lambda n: args.out + "." + n + ".bedgraph.gz")
+    logs = finish_tracks(files)
     barrier()      # every rank has closed its part files (raises if WORLD_SIZE > 1 without a process group)
     if rank == 0:
         for n in outputs:
             base = args.out + "." + n + (".bed" if n.startswith("nucpos") else ".bedgraph.gz")
             if world > 1:
-                with open(base, "wb") as fo:
-                    for r in range(world):
-                        with open(base + ".rank%d" % r, "rb") as fi:
-                            shutil.copyfileobj(fi, fo)
-                        os.remove(base + ".rank%d" % r)
+                concat_parts(base, world)
             # bgzip + tabix of every output like the reference (run_nuc.py:195-201)
             if n.startswith("nucpos"):
-                bgzip_file(base, level=COMPRESS_LEVEL)
+                bgzip_file(base)
                 tabix_index(base + ".gz")
-            elif base in to_index:
-                tabix_index(base)
+            else:
+                write_track_index(base, logs[n])
     ph.mark("merge_bgzip_tabix")

@@ -5,7 +5,7 @@ The reference maps every 1-kb chunk (or merged BED region) on a process pool, re
 its own Track.write_track into a text file that it then compresses and indexes (get_ins.py:49-85, get_cov.py:40-76).  Here the BAM is
 decoded once (FragmentStore), the regions are packed in sub-batches (pipeline.sub_batches, natac_pack_chunks) on a small thread pool
 ahead of the device, and per sub-batch one kernel fills the track and the device writer turns it into BGZF members and tabix records
-(natac_batch_format_track, writer.TbiBuilder).  Each region stays a chunk of its own, so lines break at every region boundary like the
+(natac_batch_format_track, writer.TrackFile).  Each region stays a chunk of its own, so lines break at every region boundary like the
 reference's.
 """
 import os
@@ -17,7 +17,6 @@ from .chunk import ChunkList
 from .fragments import FragmentStore
 from .utils import read_chrom_sizes_from_bam
 
-COMPRESS_LEVEL = 4
 MAX_CHUNKS = 4096       # regions per sub-batch (pipeline.sub_batches also caps its bases)
 
 
@@ -83,7 +82,7 @@ def write_packed_track_file(path, chunks, pack_chunks, run, max_chunks=None, tim
     -> the id of the track it filled (the batch's PackedChunks is batch.packed)."""
     from .. import get_context
     from ..pipeline import prefetch_map, sub_batches
-    from ..writer import BGZF_EOF, TbiBuilder, tabix_index, write_bedgraph
+    from ..writer import TrackFile, write_track_index
     ctx = get_context()
     t = timing if timing is not None else {}
     for k in ("pack_s", "device_s", "writer_s"):
@@ -95,45 +94,28 @@ def write_packed_track_file(path, chunks, pack_chunks, run, max_chunks=None, tim
         pk = pack_chunks(sub)
         return pk, time.perf_counter() - t0
 
-    tbi = TbiBuilder()
-    host_written = False        # a sub-batch went through the host writer: the index is made from the file
-    nbytes = 0
-    try:
-        with open(path, "wb") as fh:
-            for pk, dt in prefetch_map(pack, sub_batches(chunks, max_chunks=max_chunks or MAX_CHUNKS)):
-                t["pack_s"] += dt
-                t0 = time.perf_counter()
-                b = ctx.upload(pk)
-                try:
-                    tid = run(b)
-                    ctx.sync()
-                    t1 = time.perf_counter()
-                    t["device_s"] += t1 - t0
-                    z, info = b.format_track(tid, pk.chroms, pk.chunk_start, compress=True)
-                    if info["hard"]:        # values the device formatter leaves to the host (e.g. a huge --scale)
-                        vals = b.track(tid).astype(np.float64)
-                        fh.flush()
-                        nbytes += write_bedgraph(path, pk.chroms, pk.chunk_start, pk.out_off, vals, append=True, compress=COMPRESS_LEVEL,
-                                                 finish=False)
-                        fh.seek(0, os.SEEK_END)
-                        host_written = True
-                    else:
-                        fh.write(memoryview(z))
-                        if not host_written:
-                            tbi.push(info["index"], nbytes)
-                        nbytes += len(z)
-                    t["writer_s"] += time.perf_counter() - t1
-                finally:
-                    b.free()
-                t["sub_batches"] += 1
-            fh.write(BGZF_EOF)
+    out = TrackFile(path)
+    for pk, dt in prefetch_map(pack, sub_batches(chunks, max_chunks=max_chunks or MAX_CHUNKS)):
+        t["pack_s"] += dt
         t0 = time.perf_counter()
-        if host_written:
-            tabix_index(path)
-        else:
-            tbi.write(path + ".tbi")
-        t["writer_s"] += time.perf_counter() - t0
-    finally:
-        tbi.close()
+        b = ctx.upload(pk)
+        try:
+            tid = run(b)
+            ctx.sync()
+            t1 = time.perf_counter()
+            t["device_s"] += t1 - t0
+            z, info = b.format_track(tid, pk.chroms, pk.chunk_start, compress=True)
+            if info["hard"]:        # values the device formatter leaves to the host (e.g. a huge --scale)
+                out.append_values(pk.chroms, pk.chunk_start, pk.out_off, b.track(tid).astype(np.float64))
+            else:
+                out.append_members(z, info["index"])
+            t["writer_s"] += time.perf_counter() - t1
+        finally:
+            b.free()
+        t["sub_batches"] += 1
+    t0 = time.perf_counter()
+    out.close()
+    write_track_index(path, [out.log()])
+    t["writer_s"] += time.perf_counter() - t0
     return path
 

@@ -1,9 +1,14 @@
-"""Native bedGraph writer (natac_write_bedgraph): all tracks of a batch in one multi-threaded call."""
+"""Native bedGraph writer (natac_write_bedgraph): all tracks of a batch in one multi-threaded call; TrackFile: one bedGraph.gz
+assembled from sub-batches, whoever formatted them."""
 import ctypes as C
+import os
+import shutil
 
 import numpy as np
 
 from . import _lib as L
+
+COMPRESS_LEVEL = 4     # BGZF deflate level of every file the host writes (tracks, bgzip of the .bed outputs)
 
 
 def write_bedgraph(path, chroms, chunk_start, out_off, vals, append=False, compress=0, finish=True, write_zero=True,
@@ -73,9 +78,8 @@ def read_bed_table(path, cols):
     return names, cid, start, end, vals
 
 
-def bgzip_file(src, dst=None, level=4, n_threads=0, remove=True):
+def bgzip_file(src, dst=None, level=COMPRESS_LEVEL, n_threads=0, remove=True):
     """BGZF-compress a text file (pysam.tabix_compress of the reference); returns the path of the .gz"""
-    import os
     lib = L.load()
     dst = dst or (str(src) + ".gz")
     L.check(lib.natac_bgzip_file(str(src).encode(), str(dst).encode(), int(level), int(n_threads)))
@@ -147,3 +151,65 @@ class TbiBuilder(object):
             self.close()
         except Exception:
             pass
+
+
+class TrackFile(object):
+    """one bedGraph.gz (or a rank's part of one) assembled from sub-batches in file order.  A sub-batch arrives as finished BGZF
+    members with their tabix records (DeviceBatch.format_track) or as values that the native host writer formats; the first append
+    creates the file, close() ends it -- with the BGZF EOF marker iff `last`: the final part of the file -- and creates it when
+    nothing was appended.  The records are logged with the byte they were written at, so that write_track_index needs no second
+    read of the file; a host-written sub-batch has no records, so the log of a file that holds one is useless."""
+
+    def __init__(self, path, last=True, compress=COMPRESS_LEVEL):
+        self.path, self.last, self.compress = str(path), last, compress
+        self.size = 0            # bytes of members written so far (without the EOF marker)
+        self.records = []        # (tabix records of a device-formatted sub-batch, byte offset of its first member)
+        self.host_appends = 0
+
+    def append_members(self, z, index):
+        with open(self.path, "ab" if self.size else "wb") as fh:
+            fh.write(memoryview(z))
+        self.records.append((index, self.size))
+        self.size += len(z)
+
+    def append_values(self, chroms, starts, out_off, vals):
+        """Track.write_track of every chunk (pyatac/tracks.py:37-74) through natac_write_bedgraph"""
+        self.size += write_bedgraph(self.path, chroms, starts, out_off, vals, append=self.size > 0, compress=self.compress, finish=False)
+        self.host_appends += 1
+
+    def close(self):
+        with open(self.path, "ab" if self.size else "wb") as fh:     # natac_write_bedgraph's `finish` writes these 28 bytes, no more
+            if self.last:
+                fh.write(BGZF_EOF)
+
+    def log(self):
+        """what write_track_index needs of this part (picklable): its records -- None when they do not cover the part -- and its size
+        without the EOF marker"""
+        return dict(records=None if self.host_appends else self.records, size=self.size)
+
+
+def write_track_index(path, logs):
+    """path + ".tbi" of a finished track file; logs: TrackFile.log() of its parts in file (= rank) order.  From the logged records,
+    shifted by the sizes of the parts in front, when every part has them; else from the file (natac_tabix_index)."""
+    if any(l["records"] is None for l in logs) or not any(l["records"] for l in logs):
+        return tabix_index(path)
+    tb = TbiBuilder()
+    try:
+        base = 0
+        for l in logs:
+            for index, off in l["records"]:
+                tb.push(index, base + off)
+            base += l["size"]
+        return tb.write(path + ".tbi")
+    finally:
+        tb.close()
+
+
+def concat_parts(base, world):
+    """base.rank0 .. base.rank<world-1> -> base, parts removed: BGZF members and text lines concatenate, rank order = chunk order"""
+    with open(base, "wb") as fo:
+        for r in range(world):
+            part = base + ".rank%d" % r
+            with open(part, "rb") as fi:
+                shutil.copyfileobj(fi, fo)
+            os.remove(part)

@@ -95,11 +95,10 @@ def test_writer_mixes_device_members_and_host_written_batches(tmp_path):
     writer instead; its members are appended between the device's, the file stays one valid BGZF stream with the same text, and
     the index falls back to the file-based indexer (the device's record log no longer covers the whole file)"""
     import gzip
-    import types
-    from nucleoatac_amd.nucleoatac.run_occ import _Writer, finish_indexes
+    from nucleoatac_amd.nucleoatac.driver import TrackWriter
     from nucleoatac_amd.pyatac.chunk import Chunk
     from nucleoatac_amd.pyatac.tracks import Track
-    from nucleoatac_amd.writer import tabix_index, write_bedgraph
+    from nucleoatac_amd.writer import TrackFile, tabix_index, write_bedgraph, write_track_index
     subs = _subs(5)
     for i, pk in enumerate(subs):                  # one sorted file: chromosome blocks contiguous, positions ascending
         pk.chroms = ["chr%d" % (1 + i // 2)] * pk.n_chunks
@@ -107,7 +106,8 @@ def test_writer_mixes_device_members_and_host_written_batches(tmp_path):
     path = str(tmp_path / "mixed.bedgraph.gz")
     ref_path = str(tmp_path / "host.bedgraph.gz")
     parts = [[Chunk(c, int(s), int(s) + int(n)) for c, s, n in zip(pk.chroms, pk.chunk_start, pk.chunk_len)] for pk in subs]
-    w = _Writer({"occ": path}, {"occ": L.T_OCC}, lambda r: None, len(subs), True)
+    tf = TrackFile(path)
+    w = TrackWriter({"occ": tf}, {"occ": L.T_OCC}, lambda r: None)
     w.start()
     with PipelinedExecutor(0, _configure, stages, n_contexts=2) as ex:
         for r in ex.map((pk, part) for pk, part in zip(subs, parts)):
@@ -117,10 +117,11 @@ def test_writer_mixes_device_members_and_host_written_batches(tmp_path):
                 r.text[L.T_OCC] = None
             w.put(r)
     w.finish()
-    assert not w.index_ok["occ"] and len(w.index_log["occ"]) == 3
-    ws = types.SimpleNamespace(index_log=w.index_log, index_ok=w.index_ok, offset=w.offset)
-    assert finish_indexes(ws, ["occ"], lambda n: path) == [path]
-    tabix_index(path)
+    assert len(tf.records) == 3 and tf.host_appends == 2 and tf.log()["records"] is None
+    tf.close()
+    write_track_index(path, [tf.log()])                           # falls back to the file: the same .tbi as the indexer's own
+    tabix_index(path, tbi_path=path + ".ref.tbi")
+    assert open(path + ".tbi", "rb").read() == open(path + ".ref.tbi", "rb").read()
     tabix_index(ref_path)
     assert gzip.open(path, "rt").read() == gzip.open(ref_path, "rt").read()
     pk = subs[3]

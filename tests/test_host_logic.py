@@ -313,9 +313,9 @@ def test_sub_batches_cut_by_bases_and_by_count():
 
 
 def test_writer_two_phase_lookahead_order():
-    """run_occ._Writer with a (start, finish) pair: start(k) runs before the result's buffers are released, finish(k) only after
+    """driver.TrackWriter with a (start, finish) pair: start(k) runs before the result's buffers are released, finish(k) only after
     start(k + 1), every finish in result order, the last one at finish(); a failing start surfaces on the caller's thread"""
-    from nucleoatac_amd.nucleoatac.run_occ import _Writer
+    from nucleoatac_amd.nucleoatac.driver import TrackWriter
     log = []
 
     class R(object):
@@ -335,7 +335,7 @@ def test_writer_two_phase_lookahead_order():
     def finish(k):
         log.append(("finish", k))
 
-    w = _Writer({}, {}, (start, finish), 4, True)
+    w = TrackWriter({}, {}, (start, finish))
     w.start()
     for k in range(4):
         w.put(R(k))
@@ -350,7 +350,7 @@ def test_writer_two_phase_lookahead_order():
     def bad(r):
         raise ValueError("boom %d" % r.seq)
 
-    w = _Writer({}, {}, (bad, finish), 2, True)
+    w = TrackWriter({}, {}, (bad, finish))
     w.start()
     w.put(R(0))
     with pytest.raises(ValueError, match="boom 0"):

@@ -17,6 +17,7 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
     base = sys.argv[2] if len(sys.argv) > 2 else None
     from nucleoatac_amd.nucleoatac import run_occ as ro
+    from nucleoatac_amd.nucleoatac.driver import DEVICE_WRITER
     from nucleoatac_amd.nucleoatac.cli import main as cli_main
     from nucleoatac_amd.synth import write_cli_dataset
     d = tempfile.mkdtemp(prefix="natac_e2e_", dir=base)
@@ -36,7 +37,7 @@ def main():
         size = sum(os.path.getsize(out + "." + x + ".bedgraph.gz") for x in ("occ", "occ.lower_bound", "occ.upper_bound"))
         print(json.dumps(dict(chunks=n, bp=n * 2120, occ_seconds=round(dt, 2), occ_mbp_s=round(n * 2120 / dt / 1e6, 2), phases_s=dict(ro.LAST_TIMINGS),
                               track_bytes=size, write_gb_s=round(size / dt / 1e9, 2), out_dir=d, generate_inputs_s=round(t_gen, 1),
-                              device_writer=ro.DEVICE_WRITER, inputs="real .bam (%.2f GB) + .fa" % (os.path.getsize(bam) / 1e9) if real else ".npz stand-ins")))
+                              device_writer=DEVICE_WRITER, inputs="real .bam (%.2f GB) + .fa" % (os.path.getsize(bam) / 1e9) if real else ".npz stand-ins")))
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
