@@ -3132,7 +3132,7 @@ int natac_bam_open_device(natac_ctx *c, const char *path, natac_bam **out, int *
 
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize) {
     if ((!src && csize) || (!out && isize) || csize > 0xffffffffull || isize > 0xffffffffull) return -1;
-    std::vector<unsigned char> padded(csize + 8, 0);         // the bit reader takes whole words: 8 readable bytes behind the payload
+    std::vector<unsigned char> padded(csize + 32, 0);        // the bit reader takes whole words: 32 readable bytes behind the payload
     if (csize) std::memcpy(padded.data(), src, csize);
     return natac_bamdev::inflate_member_host(padded.data(), (unsigned int)csize, (unsigned char *)out, (unsigned int)isize);
 }

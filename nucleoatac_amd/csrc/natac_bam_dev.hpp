@@ -46,7 +46,7 @@ struct Strided {
 };
 
 struct BitIn {
-    const unsigned char *p;      // at least 8 readable bytes behind p[n - 1]
+    const unsigned char *p;      // readable bytes behind p[n - 1]: see inflate_member
     unsigned int n, pos;
     unsigned long long buf;
     int cnt;
@@ -110,7 +110,9 @@ __host__ __device__ inline int decode_symbol(BitIn &in, const unsigned int (&lim
 }
 
 // inflate one member's payload into out[0, isize); 0 ok, otherwise an error code (1 bad block type, 2 stored length, 3 code
-// lengths, 4 bad symbol, 5 distance too far, 6 output overrun / short, 7 input overrun).  src needs 8 readable bytes of slack.
+// lengths, 4 bad symbol, 5 distance too far, 6 output overrun / short, 7 input overrun).  src needs 32 readable bytes of slack: a valid
+// stream reads at most 8 bytes behind its end, a stream that runs over is caught within one symbol (a dynamic header's fixed part and
+// first symbol: 11 bytes, plus the reader's 8).
 template <class L8, class T16>
 __host__ __device__ inline int inflate_member(const unsigned char *src, unsigned int csize, unsigned char *out, unsigned int isize, const L8 &lengths,
                                               const T16 &lsym, const T16 &ldelta, const T16 &lwork, const T16 &dsym, const T16 &ddelta, const T16 &dwork) {
@@ -169,16 +171,19 @@ __host__ __device__ inline int inflate_member(const unsigned char *src, unsigned
                         if (idx + rep > nlen + ndist) return 3;
                         while (rep--) lengths[idx++] = (unsigned char)val;
                     }
+                    if (in.consumed() > csize) return 7;          // a header that runs over must not be read to its end: the slack is 32 bytes
                 }
                 if (lengths[256] == 0) return 3;                  // no end-of-block code
+                // An incomplete set passes only under zlib's rule (inflate_table: its longest code has ONE bit, i.e. it is a single 1-bit
+                // code): the host decoder inflates with zlib, and both must refuse the same members.
                 int left = build_code(lengths, 0, nlen, llim, ldelta, lsym, lwork);
-                int zeros = 0;
-                for (int s = 0; s < nlen; ++s) zeros += lengths[s] == 0;
-                if (left < 0 || (left > 0 && nlen - zeros != 1)) return 3;         // incomplete only with a single code
+                int longer = 0;
+                for (int s = 0; s < nlen; ++s) longer += lengths[s] > 1;
+                if (left < 0 || (left > 0 && longer != 0)) return 3;
                 left = build_code(lengths, nlen, ndist, dlim, ddelta, dsym, dwork);
-                zeros = 0;
-                for (int s = 0; s < ndist; ++s) zeros += lengths[nlen + s] == 0;
-                if (left < 0 || (left > 0 && ndist - zeros != 1)) return 3;
+                longer = 0;
+                for (int s = 0; s < ndist; ++s) longer += lengths[nlen + s] > 1;
+                if (left < 0 || (left > 0 && longer != 0)) return 3;
             }
             for (;;) {
                 int sym = decode_symbol(in, llim, ldelta, lsym);
@@ -256,7 +261,8 @@ inline void crc32_slice8_tables(unsigned int *t8) {       // host: the tables ab
         for (unsigned int i = 0; i < 256; ++i) t8[s * 256 + i] = t8[(s - 1) * 256 + i] >> 8 ^ t8[t8[(s - 1) * 256 + i] & 0xff];
 }
 
-// error code 7: the member inflated to ISIZE bytes but its CRC-32 (the four bytes behind the payload, RFC 1952) does not match
+// error code 8 (inflate_member's own end at 7, input overrun): the member inflated to ISIZE bytes but its CRC-32 (the four bytes behind
+// the payload, RFC 1952) does not match
 __global__ void __launch_bounds__(64) bamdev_inflate(const unsigned char *__restrict__ raw, const Member *__restrict__ mem, int m_begin, int n_members,
                                                      unsigned char *__restrict__ data, int *__restrict__ status, int *__restrict__ queue,
                                                      const unsigned int *__restrict__ crc_t8) {
@@ -272,11 +278,11 @@ __global__ void __launch_bounds__(64) bamdev_inflate(const unsigned char *__rest
         const unsigned char *tr = raw + mb.coff + mb.csize;              // trailer: CRC-32, ISIZE
         const unsigned int want = (unsigned int)tr[0] | ((unsigned int)tr[1] << 8) | ((unsigned int)tr[2] << 16) | ((unsigned int)tr[3] << 24);
         int rc = 0;
-        if (mb.isize == 0) rc = want == 0 ? 0 : 7;
+        if (mb.isize == 0) rc = want == 0 ? 0 : 8;
         else {
             rc = inflate_member(raw + mb.coff, mb.csize, data + mb.uoff, mb.isize, L8{lengths}, T16{t}, T16{t + 288 * 64}, T16{t + 304 * 64},
                                 T16{t + 320 * 64}, T16{t + 352 * 64}, T16{t + 368 * 64});
-            if (rc == 0 && crc32_slice8(crc_t8, data + mb.uoff, mb.isize) != want) rc = 7;
+            if (rc == 0 && crc32_slice8(crc_t8, data + mb.uoff, mb.isize) != want) rc = 8;
         }
         if (rc != 0 && atomicCAS(&status[0], 0, rc) == 0) status[1] = m;
     }
@@ -628,7 +634,7 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
         int st[2] = {0, 0};
         BAMDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
         BAMDEV_HIP(hipStreamSynchronize(stream));
-        if (st[0] == 7) {      // the member's file offset: where the previous member of the chain ends
+        if (st[0] == 8) {      // the member's file offset: where the previous member of the chain ends
             unsigned long long at = 0;
             { std::lock_guard<std::mutex> lk(chain.mu); if (m0 + (size_t)st[1] > 0) at = chain.ends[m0 + (size_t)st[1] - 1]; }
             return fail("CRC-32 mismatch in the BGZF member at file offset " + std::to_string(at) + " (corrupt file)");

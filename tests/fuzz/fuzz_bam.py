@@ -1,6 +1,6 @@
 """Randomised sweep of the device BAM decoder (natac_bam_open_device) against the host decoder: random record mixes (names, cigars,
 sequences, aux data of every length, every flag combination, unmapped reads), member sizes from 64 bytes to 64 KiB, deflate levels and
-strategies (stored / fixed / dynamic blocks), device windows from a few kB up.   usage: python tests/fuzz/fuzz_bam.py [rounds] [seed]"""
+strategies (stored / fixed / dynamic blocks) or the hand-made streams of tests/deflate_craft.py, device windows from a few kB up.   usage: python tests/fuzz/fuzz_bam.py [rounds] [seed]"""
 import os
 import sys
 import tempfile
@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from nucleoatac_amd.pyatac.fragments import FragmentStore     # noqa: E402
+import deflate_craft as D                                      # noqa: E402
 import test_gpu_bam_device as T                                # noqa: E402
 
 
@@ -31,7 +32,13 @@ def run(rounds, seed):
         strategy = rng.choice([zlib.Z_DEFAULT_STRATEGY, zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE])
         if blk > 50000 and (level == 0 or strategy != zlib.Z_DEFAULT_STRATEGY):
             blk = 50000                      # random bytes do not shrink that way: the member must stay below 64 KiB
-        open(path, "wb").write(T._bgzf(raw, blk, level, int(strategy)))
+        if r % 3 == 2:
+            # every third file: members written by tests/deflate_craft.py (15-bit codes, single-code sets, far and distance-1 copies,
+            # many small blocks, ...: streams zlib's compressor never emits), member k by encoder k + r
+            blk = min(blk, 20000)            # the Python encoders are slow
+            open(path, "wb").write(T._file(raw, range(0, len(raw), blk), lambda k, chunk: D.encode_member(rng, chunk, k + r)))
+        else:
+            open(path, "wb").write(T._bgzf(raw, blk, level, int(strategy)))
         window = int(rng.choice([0, 3000, 70000, 1 << 20]))
         if window:
             os.environ["NATAC_BAM_DEV_WINDOW"] = str(window)
