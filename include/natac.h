@@ -16,6 +16,8 @@
  *   (4) `pyatac ins --smooth`'s smoothed insertions (pyatac/get_ins.py:20-32)  -> natac_run_ins_smooth
  *       and `pyatac cov`'s fragment-centre coverage (pyatac/get_cov.py:21-37)   -> natac_run_center_cov
  *   (5) `pyatac bias`'s Tn5 bias track (pyatac/make_bias_track.py, bias.py:85-92) -> natac_run_pwm_track
+ *   (6) `pyatac counts`'s per-region fragment counts (pyatac/get_counts.py:30-45) -> natac_region_counts
+ *       and `pyatac nucleotide`'s word counts around sites (pyatac/get_nucleotide.py:19-38) -> natac_site_seq_counts
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -42,9 +44,9 @@ extern "C" {
 /* bumped whenever an entry point is added, removed or changes meaning (2: round 5 removed natac_run_nuc_occ, added natac_bg_tiling /
  * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
- * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`); the binding
- * refuses another version */
-#define NATAC_ABI_VERSION 6
+ * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
+ * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`); the binding refuses another version */
+#define NATAC_ABI_VERSION 7
 
 enum {
     NATAC_OK = 0,
@@ -286,6 +288,26 @@ int natac_insertion_seq_counts(natac_ctx *ctx, int32_t n_chunks, const int32_t *
  * case) of seq[start[i] .. end[i]) summed over the n_ranges ranges, int64, overwritten; overlapping ranges count once per range. */
 int natac_base_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int32_t n_ranges, const int64_t *start, const int64_t *end,
                       int64_t *counts);
+/* get_counts, pyatac/get_counts.py:30-45, for the regions of one chromosome: pos[n_frags] (non-decreasing) and tlen[n_frags] are the
+ * chromosome's forward proper-pair records as the FragmentStore holds them.  A record is the fragment l = pos + 4, ilen = tlen - 8
+ * (atac != 0) or l = pos, ilen = tlen (atac == 0), r = l + ilen - 1, and counts for region i if lower <= ilen < upper and
+ * (start[i] <= l < end[i] or start[i] <= r < end[i]); ilen == 0 gives r = l - 1 and counts by the same rule.  EVERY record is a
+ * candidate: the reference's fetch(chrom, start - upper, end + upper) is a superset filter that only drops such a fragment when its
+ * read is shorter than 3 bases, and the store keeps no read lengths.  Regions may overlap, repeat and come in any order; each is
+ * counted on its own, end[i] >= start[i].  counts[n_regions] are exact int64, overwritten.  kernel_ms (may be NULL): device time of the
+ * range search and the counting kernels. */
+int natac_region_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, int64_t n_regions, const int64_t *start,
+                        const int64_t *end, int lower, int upper, int atac, int64_t *counts, double *kernel_ms);
+/* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
+ * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
+ * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows
+ * A C G T, word = 2 the 16 rows of itertools.product("CGAT", repeat=2); K = up + down + 1 columns.  A plus site reads the bases
+ * [center - up, center + down + word), a minus site [center - down - word + 1, center + up + 1) reversed, upper-case bases complemented
+ * and lower-case ones not (the reference translates before it upper-cases); then every letter is upper-cased and column j counts the
+ * word at j.  A site whose window leaves [0, n) is skipped whole.  counts[(4 or 16) x K] and n_used = the sites counted are exact
+ * int64, overwritten.  up, down in [0, 524288].  kernel_ms (may be NULL): device time of the counting kernel. */
+int natac_site_seq_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int64_t n_sites, const int64_t *center, const uint8_t *minus,
+                          int up, int down, int word, int64_t *counts, int64_t *n_used, double *kernel_ms);
 /* signal.correlate(sub, vmat, mode='valid')[0] as used by SignalTrack.calculateSignal / BiasTrack
  * (nucleoatac/NucleosomeCalling.py:34-36, 60-63): sub[R x ncol], vmat[R x W] row-major, out[ncol-W+1]. */
 int natac_correlate_valid(natac_ctx *ctx, const double *sub, int64_t ncol, const double *vmat, int R, int W, double *out);

@@ -20,6 +20,7 @@
 #include "natac_fuzzfit.hpp"
 #include "natac_bedtab.hpp"
 #include "natac_pwmfit.hpp"
+#include "natac_sites.hpp"
 #include "natac_tracks.hpp"
 
 #include <algorithm>
@@ -2573,6 +2574,144 @@ int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, c
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(NATAC_E_HIP, "base_counts: %s", hipGetErrorString(e));
     for (int i = 0; i < 4; ++i) counts[i] = (int64_t)h[i];
+    return NATAC_OK;
+}
+
+// device events around the counting kernels of a call (kernel_ms of natac_region_counts / natac_site_seq_counts)
+struct KernelTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool on;
+    explicit KernelTimer(bool enabled) : on(enabled) {}
+    ~KernelTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    hipError_t start(hipStream_t s) {
+        if (!on) return hipSuccess;
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e == hipSuccess) e = hipEventRecord(e0, s);
+        return e;
+    }
+    hipError_t stop(hipStream_t s) { return on ? hipEventRecord(e1, s) : hipSuccess; }
+    hipError_t read(double *ms) {       // after the stream has been synchronised
+        if (!on) return hipSuccess;
+        float f = 0;
+        hipError_t e = hipEventElapsedTime(&f, e0, e1);
+        *ms = f;
+        return e;
+    }
+};
+
+int natac_region_counts(natac_ctx *c, int64_t nf, const int64_t *pos, const int64_t *tlen, int64_t nr, const int64_t *start,
+                        const int64_t *end, int lower, int upper, int atac, int64_t *counts, double *kernel_ms) {
+    using namespace natac_sites;
+    if (!c) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0 || nr < 0) return fail(NATAC_E_ARG, "negative size");
+    if ((nf > 0 && (!pos || !tlen)) || (nr > 0 && (!start || !end || !counts))) return fail(NATAC_E_ARG, "null argument");
+    if (upper <= lower) return fail(NATAC_E_ARG, "upper (%d) <= lower (%d)", upper, lower);
+    if (nf >= (1LL << 40) || nr >= (1LL << 40)) return fail(NATAC_E_ARG, "too many records or regions in one call");
+    if (kernel_ms) *kernel_ms = 0;
+    const long long lim = 1LL << 60;     // coordinates far inside int64: start - upper, pos + tlen cannot overflow
+    for (int64_t i = 0; i < nr; ++i) {
+        if (end[i] < start[i]) return fail(NATAC_E_ARG, "region %lld: end %lld < start %lld", (long long)i, (long long)end[i], (long long)start[i]);
+        if (start[i] < -lim || end[i] > lim) return fail(NATAC_E_ARG, "region %lld: coordinates out of range", (long long)i);
+    }
+    // the kernels search pos: it must be sorted (the FragmentStore's order)
+    for (int64_t i = 0; i < nf; ++i) {
+        if (pos[i] < -lim || pos[i] > lim || tlen[i] < -lim || tlen[i] > lim)
+            return fail(NATAC_E_ARG, "record %lld: pos or tlen out of range", (long long)i);
+        if (i && pos[i] < pos[i - 1]) return fail(NATAC_E_ARG, "pos must be non-decreasing (record %lld)", (long long)i);
+    }
+    for (int64_t i = 0; i < nr; ++i) counts[i] = 0;
+    if (nr == 0 || nf == 0) return NATAC_OK;
+    HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
+    long long *d_pos = nullptr, *d_tlen = nullptr, *d_s = nullptr, *d_e = nullptr, *d_lo = nullptr, *d_n = nullptr, *d_long = nullptr;
+    unsigned long long *d_out = nullptr;      // counts[nr], then the number of long regions
+    int rc;
+    if ((rc = tmp.upload(&d_pos, (const long long *)pos, (size_t)nf)) || (rc = tmp.upload(&d_tlen, (const long long *)tlen, (size_t)nf)) ||
+        (rc = tmp.upload(&d_s, (const long long *)start, (size_t)nr)) || (rc = tmp.upload(&d_e, (const long long *)end, (size_t)nr)) ||
+        (rc = tmp.alloc(&d_lo, (size_t)nr)) || (rc = tmp.alloc(&d_n, (size_t)nr)) || (rc = tmp.alloc(&d_long, (size_t)nr)) ||
+        (rc = tmp.alloc(&d_out, (size_t)nr + 1)))
+        return rc;
+    const int shift = atac ? 4 : 0, trim = atac ? 8 : 0;
+    KernelTimer timer(kernel_ms != nullptr);
+    hipError_t e = hipMemsetAsync(d_out, 0, ((size_t)nr + 1) * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = timer.start(c->stream);
+    if (e == hipSuccess) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK - 1) / RC_BLOCK, 4096);
+        hipLaunchKernelGGL(natac_region_ranges, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, (long long)nf, (long long)nr, d_s, d_e, lower,
+                           upper, shift, d_lo, d_n, d_long, d_out + nr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK / 64 - 1) / (RC_BLOCK / 64), 8192);
+        hipLaunchKernelGGL(natac_region_count_short, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, (long long)nr, d_s, d_e, d_lo,
+                           d_n, lower, upper, shift, trim, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        // the number of long regions stays on the device: a fixed grid, idle when there is none
+        const unsigned bx = (unsigned)std::min<long long>(nr, 128);
+        hipLaunchKernelGGL(natac_region_count_long, dim3(bx, RC_LONG_Y), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, d_s, d_e, d_lo, d_n,
+                           d_long, d_out + nr, lower, upper, shift, trim, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = timer.stop(c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_out, (size_t)nr * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = timer.read(kernel_ms);
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "region_counts: %s", hipGetErrorString(e));
+    return NATAC_OK;
+}
+
+int natac_site_seq_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int64_t ns, const int64_t *center, const uint8_t *minus, int up,
+                          int down, int word, int64_t *counts, int64_t *n_used, double *kernel_ms) {
+    using namespace natac_sites;
+    if (!c || !counts || !n_used) return fail(NATAC_E_ARG, "null argument");
+    if (n < 0 || ns < 0) return fail(NATAC_E_ARG, "negative size");
+    if (word != 1 && word != 2) return fail(NATAC_E_ARG, "word length must be 1 or 2 (got %d)", word);
+    if (up < 0 || down < 0 || up > SS_MAX_FLANK || down > SS_MAX_FLANK)
+        return fail(NATAC_E_ARG, "up and down must be in [0, %d] (got %d, %d)", SS_MAX_FLANK, up, down);
+    if ((n > 0 && !seq) || (ns > 0 && !center)) return fail(NATAC_E_ARG, "null argument");
+    if (ns >= (1LL << 40)) return fail(NATAC_E_ARG, "too many sites in one call");
+    const int K = up + down + 1, R = word == 2 ? 16 : 4;
+    if (kernel_ms) *kernel_ms = 0;
+    // the kernel trusts the centres: every window it reads is checked against [0, n) from a centre inside it
+    for (int64_t i = 0; i < ns; ++i)
+        if (center[i] < 0 || center[i] >= n)
+            return fail(NATAC_E_ARG, "site %lld: centre %lld outside the sequence [0, %lld)", (long long)i, (long long)center[i], (long long)n);
+    for (long long i = 0; i < (long long)R * K; ++i) counts[i] = 0;
+    *n_used = 0;
+    if (ns == 0) return NATAC_OK;
+    HIPCHK(hipSetDevice(c->device));
+    StreamTemps tmp(c);
+    unsigned char *d_seq = nullptr, *d_m = nullptr;
+    long long *d_c = nullptr;
+    unsigned long long *d_out = nullptr;      // counts[R x K], then n_used
+    const size_t nout = (size_t)R * K + 1;
+    int rc;
+    if ((rc = tmp.upload(&d_seq, (const unsigned char *)seq, (size_t)n)) || (rc = tmp.upload(&d_c, (const long long *)center, (size_t)ns)) ||
+        (minus && (rc = tmp.upload(&d_m, (const unsigned char *)minus, (size_t)ns))) || (rc = tmp.alloc(&d_out, nout)))
+        return rc;
+    std::vector<unsigned long long> h(nout);
+    KernelTimer timer(kernel_ms != nullptr);
+    hipError_t e = hipMemsetAsync(d_out, 0, nout * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess) e = timer.start(c->stream);
+    if (e == hipSuccess) {
+        const unsigned bx = (unsigned)std::min<long long>((ns + SS_SEG - 1) / SS_SEG, 1024);
+        hipLaunchKernelGGL(natac_site_seq_count, dim3(bx, (unsigned)((K + SS_TILE - 1) / SS_TILE)), dim3(SS_BLOCK), 0, c->stream, d_seq,
+                           (long long)n, (long long)ns, d_c, d_m, up, down, word, d_out, d_out + (nout - 1));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = timer.stop(c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = timer.read(kernel_ms);
+    if (e != hipSuccess) return fail(NATAC_E_HIP, "site_seq_counts: %s", hipGetErrorString(e));
+    for (size_t i = 0; i + 1 < nout; ++i) counts[i] = (int64_t)h[i];
+    *n_used = (int64_t)h[nout - 1];
     return NATAC_OK;
 }
 

@@ -1,0 +1,205 @@
+// natac_sites.hpp -- the counting kernels behind `pyatac counts` and `pyatac nucleotide` (pyatac/get_counts.py and
+// pyatac/get_nucleotide.py of the reference):
+//   natac_region_ranges / natac_region_count_short / natac_region_count_long
+//                          fragments with an end inside each of a list of regions of one chromosome (get_counts.py:30-45)
+//   natac_site_seq_count   mono- or dinucleotide content of the window around every site of one chromosome (_nucleotideHelper,
+//                          get_nucleotide.py:19-38, with chunk.center / chunk.slop and seq.get_sequence / seq_to_mat)
+// Every count is an integer: lanes and waves add 32-bit partial counts, the results are 64-bit, and nothing depends on the order of
+// the records, the sites, the blocks or the waves.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "natac_pwmfit.hpp"
+
+namespace natac_sites {
+
+constexpr int RC_BLOCK = 256;           // 4 waves
+constexpr int RC_SLICE = 2048;          // candidate records per wave slice; a region with more candidates is a "long" region
+constexpr int RC_LONG_Y = 16;           // blocks that share the slices of one long region (x 4 waves)
+
+// ---- pyatac counts ---------------------------------------------------------------------------------------------------------------
+// A record (pos, tlen) of the chromosome, sorted by pos, is a fragment with left end l = pos + shift, insert size ilen = tlen - trim
+// (shift 4, trim 8 with the ATAC offsets; 0, 0 without) and right end r = l + ilen - 1.  It counts for the region [s, e) if
+// lower <= ilen < upper and (s <= l < e or s <= r < e).  Every record that can count has s - max(upper, 1) < l < e + max(0, 1 - lower)
+// (r >= s needs l >= s - ilen + 1 > s - upper; ilen <= 0 puts r left of l, so l may lie right of the region), and l is monotone in
+// pos: the candidates of a region are one contiguous range of records.
+
+// cand_lo[i] = the first candidate record of region i, cand_n[i] = how many follow.  Regions with more than RC_SLICE candidates are
+// appended to long_list (in no particular order; *n_long counts them), every other region is counted by natac_region_count_short.
+__global__ void __launch_bounds__(RC_BLOCK) natac_region_ranges(const long long *__restrict__ pos, long long nf, long long nr,
+                                                                const long long *__restrict__ start, const long long *__restrict__ end,
+                                                                int lower, int upper, int shift, long long *__restrict__ cand_lo,
+                                                                long long *__restrict__ cand_n, long long *__restrict__ long_list,
+                                                                unsigned long long *__restrict__ n_long) {
+    const long long below = (long long)(upper > 1 ? upper : 1);              // candidates have l > s - below
+    const long long above = lower < 1 ? 1LL - (long long)lower : 0LL;        // and l < e + above
+    for (long long i = (long long)blockIdx.x * RC_BLOCK + threadIdx.x; i < nr; i += (long long)gridDim.x * RC_BLOCK) {
+        const long long p0 = start[i] - below - shift;                       // pos > p0
+        const long long p1 = end[i] + above - shift;                         // pos < p1
+        long long lo = 0, hi = nf;                                           // first record with pos > p0
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (pos[mid] > p0) hi = mid; else lo = mid + 1;
+        }
+        const long long a = lo;
+        hi = nf;                                                             // first record with pos >= p1 (not before a)
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (pos[mid] >= p1) hi = mid; else lo = mid + 1;
+        }
+        const long long n = lo - a;
+        cand_lo[i] = a;
+        cand_n[i] = n;
+        if (n > RC_SLICE) long_list[atomicAdd(n_long, 1ULL)] = i;
+    }
+}
+
+// the records [f0, f1) that count for [s, e), over the lanes of one wave: every lane returns the wave's total
+__device__ __forceinline__ unsigned long long region_slice_count(const long long *__restrict__ pos, const long long *__restrict__ tlen,
+                                                                 long long f0, long long f1, long long s, long long e, int lower,
+                                                                 int upper, int shift, int trim, int lane) {
+    unsigned long long total = 0;
+    for (long long f = f0; f < f1; f += 64) {           // f0, f1 are wave-uniform: every lane takes part in every ballot
+        bool hit = false;
+        if (f + lane < f1) {
+            const long long n = tlen[f + lane] - trim;
+            const long long l = pos[f + lane] + shift;
+            const long long r = l + n - 1;
+            hit = n >= lower && n < upper && ((l >= s && l < e) || (r >= s && r < e));
+        }
+        total += (unsigned long long)__popcll(__ballot(hit));
+    }
+    return total;
+}
+
+// one wave per region with at most RC_SLICE candidates: counts[i] = its count.  Long regions are left alone.
+__global__ void __launch_bounds__(RC_BLOCK) natac_region_count_short(const long long *__restrict__ pos, const long long *__restrict__ tlen,
+                                                                     long long nr, const long long *__restrict__ start,
+                                                                     const long long *__restrict__ end,
+                                                                     const long long *__restrict__ cand_lo,
+                                                                     const long long *__restrict__ cand_n, int lower, int upper, int shift,
+                                                                     int trim, unsigned long long *__restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const long long nwaves = (long long)gridDim.x * (RC_BLOCK / 64);
+    for (long long i = (long long)blockIdx.x * (RC_BLOCK / 64) + (threadIdx.x >> 6); i < nr; i += nwaves) {
+        const long long n = cand_n[i];
+        if (n > RC_SLICE) continue;
+        const long long f0 = cand_lo[i];
+        const unsigned long long t = region_slice_count(pos, tlen, f0, f0 + n, start[i], end[i], lower, upper, shift, trim, lane);
+        if (lane == 0) counts[i] = t;
+    }
+}
+
+// the long regions: blockIdx.x strides over long_list, the 4 * gridDim.y waves of a row stride over the region's slices of RC_SLICE
+// candidates and each adds its slice totals to the region's counter (zero before the launch) with one 64-bit atomic.
+__global__ void __launch_bounds__(RC_BLOCK) natac_region_count_long(const long long *__restrict__ pos, const long long *__restrict__ tlen,
+                                                                    const long long *__restrict__ start, const long long *__restrict__ end,
+                                                                    const long long *__restrict__ cand_lo,
+                                                                    const long long *__restrict__ cand_n,
+                                                                    const long long *__restrict__ long_list,
+                                                                    const unsigned long long *__restrict__ n_long, int lower, int upper,
+                                                                    int shift, int trim, unsigned long long *__restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const long long nl = (long long)*n_long;
+    const long long wy = (long long)blockIdx.y * (RC_BLOCK / 64) + (threadIdx.x >> 6);
+    const long long ny = (long long)gridDim.y * (RC_BLOCK / 64);
+    for (long long k = blockIdx.x; k < nl; k += gridDim.x) {
+        const long long i = long_list[k];
+        const long long f0 = cand_lo[i], n = cand_n[i];
+        const long long s = start[i], e = end[i];
+        const long long nslice = (n + RC_SLICE - 1) / RC_SLICE;
+        unsigned long long t = 0;
+        for (long long sl = wy; sl < nslice; sl += ny) {
+            const long long a = f0 + sl * RC_SLICE;
+            const long long b = a + RC_SLICE < f0 + n ? a + RC_SLICE : f0 + n;
+            t += region_slice_count(pos, tlen, a, b, s, e, lower, upper, shift, trim, lane);
+        }
+        if (lane == 0 && t) atomicAdd(&counts[i], t);
+    }
+}
+
+// ---- pyatac nucleotide -----------------------------------------------------------------------------------------------------------
+constexpr int SS_BLOCK = 256;           // 4 waves
+constexpr int SS_TILE = 512;            // columns per block (blockIdx.y = the column tile): 16 rows x 512 x 4 B = 32 KB of LDS
+constexpr int SS_MAX_FLANK = 1 << 19;  // up, down <= 524288: at most 2^20 + 1 columns
+constexpr int SS_SEG = 4096;            // sites per block between two flushes: no 32-bit LDS counter passes SS_SEG
+
+// the letter of a window position as the reference sees it, 0..3 = A C G T, 4 = anything else.  On the minus strand the reference
+// complements with translate('ACGT' -> 'TGCA') BEFORE it upper-cases (pyatac/seq.py:19-22, 25-34): an upper-case base is complemented,
+// a lower-case (soft-masked) base is only upper-cased.
+__device__ __forceinline__ unsigned site_base(unsigned ch, bool minus) {
+    const unsigned b = natac_pwmfit::base_row(ch);
+    return (minus && b < 4u && !(ch & 0x20u)) ? 3u - b : b;
+}
+
+// counts[R][K] += the words of the windows of the sites of one chromosome, K = up + down + 1, R = 4 (word 1: rows A C G T) or 16
+// (word 2: rows in the order of itertools.product("CGAT", repeat=2)); *n_used += the sites whose window lies inside [0, n).
+// A plus site with centre c reads S[j] = seq[c - up + j]; a minus site reads S[j] = seq[c + up - j] (complemented, see site_base);
+// column j holds the word S[j .. j + word).  The window is [c - up, c + down + word) on plus, [c - down - word + 1, c + up + 1) on
+// minus; a site whose window leaves [0, n) is skipped whole (the reference's clipped window is shorter than K + word - 1 bases).
+// Lane layout: a wave is NG groups of CW lanes (CW = min(columns of the tile, 64), NG = 64 / CW); a group takes one site at a time
+// and its lanes run along the window, so the bases of a window are read from consecutive addresses and the lanes of a group add to
+// different LDS counters.  A block takes segments of SS_SEG sites and flushes its LDS tile into the 64-bit matrix after each.
+__global__ void __launch_bounds__(SS_BLOCK) natac_site_seq_count(const unsigned char *__restrict__ seq, long long n, long long ns,
+                                                                 const long long *__restrict__ center,
+                                                                 const unsigned char *__restrict__ minus, int up, int down, int word,
+                                                                 unsigned long long *__restrict__ counts,
+                                                                 unsigned long long *__restrict__ n_used) {
+    __shared__ unsigned s_cnt[16 * SS_TILE];
+    __shared__ unsigned s_n;
+    const int K = up + down + 1;
+    const int R = word == 2 ? 16 : 4;
+    const int col0 = blockIdx.y * SS_TILE;
+    const int tw = K - col0 < SS_TILE ? K - col0 : SS_TILE;       // columns of this tile
+    const int CW = tw < 64 ? tw : 64;
+    const int NG = 64 / CW;
+    const int lane = threadIdx.x & 63;
+    const int g = lane / CW, c = lane - g * CW;
+    const int slot = (threadIdx.x >> 6) * NG + g;                 // this group's first site of a segment
+    const int nslot = (SS_BLOCK / 64) * NG;
+    const long long d = word - 1;
+    for (int i = threadIdx.x; i < R * SS_TILE; i += SS_BLOCK) s_cnt[i] = 0;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    const long long nseg = (ns + SS_SEG - 1) / SS_SEG;
+    for (long long seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+        const long long i1 = (seg + 1) * SS_SEG < ns ? (seg + 1) * SS_SEG : ns;
+        if (g < NG) {
+            for (long long i = seg * SS_SEG + slot; i < i1; i += nslot) {
+                const long long ctr = center[i];
+                const bool rev = minus != nullptr && minus[i] != 0;
+                const long long w0 = rev ? ctr - down - d : ctr - up;
+                const long long w1 = rev ? ctr + up + 1 : ctr + down + 1 + d;
+                if (w0 < 0 || w1 > n) continue;
+                if (blockIdx.y == 0 && c == 0) atomicAdd(&s_n, 1u);
+                for (int j = c; j < tw; j += CW) {
+                    const long long col = col0 + j;
+                    const long long p = rev ? ctr + up - col : ctr - up + col;
+                    unsigned row = site_base(seq[p], rev);
+                    if (word == 2) {
+                        const unsigned b2 = site_base(seq[rev ? p - 1 : p + 1], rev);
+                        // A C G T -> its place in "CGAT": 2 0 1 3
+                        row = (row < 4u && b2 < 4u) ? 4u * ((0xD2u >> (2u * row)) & 3u) + ((0xD2u >> (2u * b2)) & 3u) : 16u;
+                    }
+                    if (row < (unsigned)R) atomicAdd(&s_cnt[row * SS_TILE + j], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < R * tw; i += SS_BLOCK) {
+            const int row = i / tw, j = i - row * tw;
+            const unsigned v = s_cnt[row * SS_TILE + j];
+            if (v) {
+                atomicAdd(&counts[(long long)row * K + col0 + j], (unsigned long long)v);
+                s_cnt[row * SS_TILE + j] = 0;
+            }
+        }
+        if (threadIdx.x == 0 && s_n) {
+            atomicAdd(n_used, (unsigned long long)s_n);
+            s_n = 0;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace natac_sites

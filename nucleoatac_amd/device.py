@@ -343,6 +343,40 @@ class Context(object):
         L.check(self._lib.natac_base_counts(self._h, _ptr(sq), sq.shape[0], st.shape[0], _ptr(st), _ptr(en), _ptr(out)))
         return out
 
+    def region_counts(self, pos, tlen, starts, ends, lower=0, upper=500, atac=True, with_kernel_ms=False):
+        """fragment counts of `pyatac counts` (pyatac/get_counts.py:30-45) for regions of one chromosome: int64[n_regions], exact.
+        pos (sorted) / tlen are the chromosome's records as the FragmentStore holds them; a record counts for [start, end) if
+        lower <= ilen < upper and its left or its right end lies in it.  with_kernel_ms: also return the kernels' device time."""
+        p = np.ascontiguousarray(pos, dtype=np.int64)
+        t = np.ascontiguousarray(tlen, dtype=np.int64)
+        st = np.ascontiguousarray(starts, dtype=np.int64)
+        en = np.ascontiguousarray(ends, dtype=np.int64)
+        if p.ndim != 1 or p.shape != t.shape or st.ndim != 1 or st.shape != en.shape:
+            raise ValueError("pos / tlen and starts / ends must be pairs of 1-d arrays of one length")
+        out = np.zeros(st.shape[0], dtype=np.int64)
+        ms = C.c_double(0)
+        L.check(self._lib.natac_region_counts(self._h, p.shape[0], _ptr(p), _ptr(t), st.shape[0], _ptr(st), _ptr(en), int(lower),
+                                              int(upper), 1 if atac else 0, _ptr(out), C.byref(ms)))
+        return (out, ms.value) if with_kernel_ms else out
+
+    def site_seq_counts(self, seq, centers, minus, up, down, word=1, with_kernel_ms=False):
+        """word counts of `pyatac nucleotide` (_nucleotideHelper, pyatac/get_nucleotide.py:19-38) around the sites of one chromosome:
+        (M int64[4 or 16, up + down + 1], n = the sites whose window lies inside the chromosome), exact.  seq: the chromosome's bytes,
+        case as in the FASTA; centers in [0, len(seq)); minus: per-site flags or None (all plus); word 1 (rows A C G T) or 2 (rows
+        itertools.product("CGAT", repeat=2)).  with_kernel_ms: also return the kernel's device time."""
+        sq = np.ascontiguousarray(seq, dtype=np.uint8)
+        ce = np.ascontiguousarray(centers, dtype=np.int64)
+        mi = None if minus is None else np.ascontiguousarray(minus, dtype=np.uint8)
+        if sq.ndim != 1 or ce.ndim != 1 or (mi is not None and mi.shape != ce.shape):
+            raise ValueError("seq and centers must be 1-d, minus as long as centers")
+        rows = 16 if int(word) == 2 else 4
+        counts = np.zeros((rows, max(int(up) + int(down) + 1, 1)), dtype=np.int64)
+        n = C.c_int64(0)
+        ms = C.c_double(0)
+        L.check(self._lib.natac_site_seq_counts(self._h, _ptr(sq), sq.shape[0], ce.shape[0], _ptr(ce), None if mi is None else _ptr(mi),
+                                                int(up), int(down), int(word), _ptr(counts), C.byref(n), C.byref(ms)))
+        return (counts, n.value, ms.value) if with_kernel_ms else (counts, n.value)
+
     def correlate_valid(self, sub, vmat):
         """signal.correlate(sub, vmat, mode='valid')[0] (nucleoatac/NucleosomeCalling.py:34-36)."""
         sub, vmat = _f64(sub), _f64(vmat)

@@ -7,6 +7,8 @@ import functools
 import gzip
 import warnings
 
+import numpy as np
+
 
 class Chunk(object):
     """one genomic interval (pyatac/chunk.py:11-54)"""
@@ -200,3 +202,36 @@ class ChunkList(list):
             self[:] = [x for x in self if x.chrom in chroms]
             warnings.warn("%d chromosome names in %s not included in %s:\n%s\n %s" % (
                 len(bad), chunklist_source, chrom_source, "\n".join(bad), warn))
+
+
+class BedColumnError(ValueError):
+    """a BED line has no field at the column it is asked for"""
+
+
+def read_bed_columns(bedfile, strand_col=None, min_length=1):
+    """the regions ChunkList.read(bedfile, strand_col=strand_col) keeps, in its order, as columns instead of a million Chunk objects:
+    (names, chrom, start, end, minus) with names the chromosome names in the order they first appear, chrom int32 indices into it,
+    start / end int64 and minus True where the strand field is "-" (every other value, and no strand column, is plus: Chunk.center
+    and Chunk.slop test for "-" only).  Raises BedColumnError, naming the line, when a line has fewer than strand_col fields."""
+    opener = gzip.open if bedfile[-3:] == ".gz" else open
+    names, index = [], {}
+    chrom, start, end, minus = [], [], [], []
+    with opener(bedfile, "rt") as fh:
+        for lineno, line in enumerate(fh, 1):
+            f = line.rstrip("\n").split("\t")
+            if len(f) < 3:
+                continue
+            if strand_col and not 1 <= strand_col <= len(f):
+                raise BedColumnError("%s line %d has %d fields: no strand in column %d" % (bedfile, lineno, len(f), strand_col))
+            s, e = int(f[1]), int(f[2])
+            if e - s < min_length:
+                continue
+            k = index.get(f[0])
+            if k is None:
+                k = index[f[0]] = len(names)
+                names.append(f[0])
+            chrom.append(k)
+            start.append(s)
+            end.append(e)
+            minus.append(bool(strand_col) and f[strand_col - 1] == "-")
+    return names, np.array(chrom, np.int32), np.array(start, np.int64), np.array(end, np.int64), np.array(minus, bool)

@@ -1,7 +1,8 @@
-"""`pyatac pwm | sizes | ins | cov | bias` command line with the reference's flag names and defaults (pyatac/cli.py:111-173, 310-352).
-`pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov` write the per-base insertion and
-fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM.  The other pyatac tools (signal,
-counts, nucleotide, vplot) are not part of this package."""
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide` command line with the reference's flag names and defaults
+(pyatac/cli.py:90-193, 310-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
+write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
+`counts` gives the fragment count of every BED window and `nucleotide` the mono- or dinucleotide frequency around a set of sites
+(for one, the nucpos.bed.gz of `nucleoatac nuc`).  The other pyatac tools (signal, vplot, bias_vplot) are not part of this package."""
 import argparse
 import sys
 
@@ -68,10 +69,35 @@ def add_bias_parser(sub):
     p.add_argument("--cores", metavar="int", default=1, type=int, help="accepted for compatibility; the GPU replaces the pool")
 
 
+def add_counts_parser(sub):
+    p = sub.add_parser("counts", help="pyatac function-- compute fragment counts within windows")
+    p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM or a FragmentStore .npz)")
+    p.add_argument("--bed", metavar="bed_file", required=True, help="Windows in which to compute counts")
+    p.add_argument("--out", metavar="output_basename", help="Basename for output")
+    p.add_argument("--not_atac", action="store_false", dest="atac", default=True, help="Don't use atac offsets")
+    p.add_argument("--lower", metavar="int", default=0, type=int, help="lower limit on insert size. Default is 0")
+    p.add_argument("--upper", metavar="int", default=500, type=int, help="upper limit on insert size.  Default is 500")
+
+
+def add_nucleotide_parser(sub):
+    p = sub.add_parser("nucleotide", help="pyatac function-- get nucleotide (or di-nucleotide) content around sites")
+    p.add_argument("--fasta", metavar="fasta_file", required=True, help="Accepts fasta file (or a FastaStore .npz)")
+    p.add_argument("--bed", metavar="bed_file", required=True, help="Positions around which to get nucleotide frequencies")
+    p.add_argument("--dinucleotide", action="store_true", default=False,
+                   help="Compute dinucleotide frequencies instead of single nucleotide")
+    p.add_argument("--up", metavar="int", default=250, type=int, help="Bases upstream of site to get frequencies for")
+    p.add_argument("--down", metavar="int", default=250, type=int, help="Bases downstream of site to get frequencies for")
+    p.add_argument("--strand", metavar="int", type=int, help="Column in bedfile with strand info (1-based)")
+    p.add_argument("--out", metavar="output_basename", help="Basename for output")
+    p.add_argument("--cores", metavar="int", default=1, type=int, help="accepted for compatibility; the GPU replaces the pool")
+    p.add_argument("--norm", action="store_true", default=False, help="Normalize by background frequencies")
+
+
 def pyatac_parser():
     from .. import __version__
-    parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution and the per-base "
-                                                                "insertion, coverage and Tn5 bias tracks")
+    parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
+                                                                "insertion, coverage and Tn5 bias tracks, fragment counts per window "
+                                                                "and nucleotide content around sites")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -80,6 +106,8 @@ def pyatac_parser():
     add_ins_parser(sub)
     add_cov_parser(sub)
     add_bias_parser(sub)
+    add_counts_parser(sub)
+    add_nucleotide_parser(sub)
     return parser
 
 
@@ -117,6 +145,24 @@ def pyatac_main(args):
             make_bias_track(args)
         except BiasTrackError as e:
             sys.stderr.write("pyatac bias: %s\n" % e)
+            return 1
+    elif args.call == "counts":
+        from .chunk import BedColumnError
+        from .get_counts import CountsError, get_counts
+        print("---------Getting fragment counts in windows---------------------------------------")
+        try:
+            get_counts(args)
+        except (CountsError, BedColumnError) as e:
+            sys.stderr.write("pyatac counts: %s\n" % e)
+            return 1
+    elif args.call == "nucleotide":
+        from .chunk import BedColumnError
+        from .get_nucleotide import NucleotideError, get_nucleotide
+        print("---------Getting nucleotide content around sites---------------------------------------")
+        try:
+            get_nucleotide(args)
+        except (NucleotideError, BedColumnError) as e:
+            sys.stderr.write("pyatac nucleotide: %s\n" % e)
             return 1
     return 0
 

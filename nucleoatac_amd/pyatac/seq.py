@@ -113,6 +113,36 @@ class FastaStore(object):
         return st
 
     @staticmethod
+    def open_cased(src):
+        """the store of `src` with every letter in the case the file has it (open() upper-cases on load): `pyatac nucleotide` needs the
+        soft-masking, because the reference complements a minus-strand window before it upper-cases it.  Cached apart from open()."""
+        if isinstance(src, FastaStore):
+            return src
+        key = ("cased", src)
+        if key not in _CACHE:
+            _CACHE[key] = FastaStore(FastaStore._load_cased(src))
+        return _CACHE[key]
+
+    @staticmethod
+    def _load_cased(src):
+        if src.endswith(".npz"):
+            d = np.load(src, allow_pickle=False)
+            return {str(c): np.ascontiguousarray(d["seq_" + str(c)]).view(np.uint8) for c in d["chrom_names"]}
+        with (gzip.open if src.endswith(".gz") else open)(src, "rb") as fh:
+            raw = fh.read()
+        data = np.frombuffer(raw, dtype=np.uint8)
+        starts = np.concatenate(([0], np.flatnonzero(data == 10) + 1))
+        starts = starts[starts < len(data)]
+        heads = starts[data[starts] == ord(">")]
+        seqs = {}
+        for k, h in enumerate(heads):
+            eol = raw.find(b"\n", h)
+            eol = len(raw) if eol < 0 else eol
+            body = data[eol + 1:heads[k + 1] if k + 1 < len(heads) else len(data)]
+            seqs[raw[h + 1:eol].split()[0].decode()] = body[(body != 10) & (body != 13) & (body != 32) & (body != 9)]
+        return seqs
+
+    @staticmethod
     def _native_ok():
         try:
             from .. import _lib as L
