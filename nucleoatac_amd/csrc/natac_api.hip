@@ -59,7 +59,7 @@ static void dev_free(void *p);
 
 // The owner of one pool block of n elements of T (move-only): the block goes back to the pool when the owner is reset or destroyed,
 // so whoever holds it must know the block's queued work has finished by then -- the context and the batch free theirs after draining
-// their stream, a call's temporaries live in a StreamTemps.  Converts to T * for launches and copies.
+// their stream, a call's temporaries live in a DeviceCall.  Converts to T * for launches and copies.
 template <class T>
 class PoolBuf {
   public:
@@ -341,35 +341,107 @@ static int dev_upload(natac_ctx *c, PoolBuf<T> &buf, const T *src, size_t n) {
     return NATAC_OK;
 }
 
-// The device temporaries of one call, freed when the scope ends.  The pool may hand a freed block to another context at once, so
-// a block may go back only once its stream has finished with it: on the normal path the call's last synchronisation has seen to
-// that; an early exit may leave kernels or copies queued, and the scope then drains the stream before it frees.
-class StreamTemps {
+// One per-call device operation on the context's stream, from selecting the device to reporting the result: the call's device
+// temporaries, its copies in and out, optional event timing of its kernels, and one finishing step.  The first HIP error is latched:
+// after it uploads, memsets and fetches do nothing, the caller asks ok() before it launches, and finish() reports "<name>: <error>"
+// (NATAC_E_NOMEM for a failed allocation, NATAC_E_HIP otherwise).
+// The temporaries go back to the pool when the scope ends.  The pool may hand a freed block to another context at once, so a block
+// may go back only once the stream has finished with it: finish() has seen to that; a scope left without it may have kernels or
+// copies queued, and then drains the stream before it frees.
+namespace {
+class DeviceCall {
   public:
-    explicit StreamTemps(natac_ctx *c) : c_(c) {}
-    ~StreamTemps() {
+    DeviceCall(natac_ctx *c, const char *name) : c_(c), name_(name) { note(hipSetDevice(c->device)); }
+    DeviceCall(const DeviceCall &) = delete;
+    DeviceCall &operator=(const DeviceCall &) = delete;
+    ~DeviceCall() {
         if (!bufs_.empty() && hipStreamQuery(c_->stream) != hipSuccess) (void)hipStreamSynchronize(c_->stream);
+        if (t0_) (void)hipEventDestroy(t0_);
+        if (t1_) (void)hipEventDestroy(t1_);
     }
-    // as dev_alloc / dev_upload, into a block the scope owns (n == 0 takes one element of T)
+    bool ok() const { return e_ == hipSuccess; }
+    void launched() { note(hipGetLastError()); }      // right after every launch
+    // device temporaries of n elements (n == 0 takes one element); nullptr once a step has failed
     template <class T>
-    int alloc(T **p, size_t n) {
+    T *alloc(size_t n) {
+        if (!ok()) return nullptr;
         bufs_.emplace_back();
-        int rc = dev_alloc(bufs_.back(), std::max<size_t>(n, 1) * sizeof(T));
-        *p = (T *)bufs_.back().get();
-        return rc;
+        note(bufs_.back().alloc(std::max<size_t>(n, 1) * sizeof(T)));
+        return (T *)bufs_.back().get();
     }
     template <class T>
-    int upload(T **p, const T *src, size_t n) {
-        int rc = alloc(p, n);
-        if (rc) return rc;
-        if (n) HIPCHK(hipMemcpyAsync(*p, src, n * sizeof(T), hipMemcpyHostToDevice, c_->stream));
-        return NATAC_OK;
+    T *zeroed(size_t n) {
+        T *p = alloc<T>(n);
+        zero(p, n);
+        return p;
+    }
+    template <class T>
+    T *upload(const T *src, size_t n) {
+        T *p = alloc<T>(n);
+        send(p, src, n);
+        return p;
+    }
+    // the stream's memset and copies, in elements of T
+    template <class T>
+    void zero(T *dst, size_t n) {
+        if (ok() && n) note(hipMemsetAsync(dst, 0, n * sizeof(T), c_->stream));
+    }
+    template <class T>
+    void send(T *dst, const T *src, size_t n) {
+        if (ok() && n) note(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, c_->stream));
+    }
+    template <class T>
+    void fetch(void *dst, const T *src, size_t n) {
+        if (ok() && n) note(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, c_->stream));
+    }
+    // device events around the kernels of the call: *ms (may be NULL: no timing) is written by finish()
+    void time_begin(double *ms) {
+        if (!ms || !ok()) return;
+        note(hipEventCreate(&t0_));
+        if (ok()) note(hipEventCreate(&t1_));
+        if (ok()) note(hipEventRecord(t0_, c_->stream));
+        ms_ = ms;
+    }
+    void time_end() {
+        if (ms_ && ok()) note(hipEventRecord(t1_, c_->stream));
+    }
+    // a profile event around the launches between the two (collected by finish())
+    void prof_begin(int k) { ::prof_begin(c_, k, ev_, c_->stream); profiled_ = true; }
+    void prof_end() { ::prof_end(c_, ev_); }
+    // waits for what has been queued -- also after a failure, so that nothing of the call is still running -- and reports the latch.
+    // For a call of several phases that needs a value on the host before it goes on; the last wait of a call is finish().
+    int sync() {
+        note(hipStreamSynchronize(c_->stream));
+        return report();
+    }
+    // the one finishing step of a call: wait, read the timer, collect the profile events, report
+    int finish() {
+        note(hipStreamSynchronize(c_->stream));
+        if (ms_ && ok()) {
+            float f = 0;
+            note(hipEventElapsedTime(&f, t0_, t1_));
+            *ms_ = f;
+        }
+        if (profiled_) prof_collect(c_);
+        return report();
     }
 
   private:
+    void note(hipError_t e) { if (e_ == hipSuccess) e_ = e; }
+    int report() const {
+        if (ok()) return NATAC_OK;
+        return fail(e_ == hipErrorOutOfMemory ? NATAC_E_NOMEM : NATAC_E_HIP, "%s: %s", name_, hipGetErrorString(e_));
+    }
     natac_ctx *c_;
+    const char *name_;
+    hipError_t e_ = hipSuccess;
     std::vector<PoolBuf<unsigned char>> bufs_;
+    hipEvent_t t0_ = nullptr, t1_ = nullptr;
+    double *ms_ = nullptr;
+    natac_ctx::Ev ev_;
+    bool profiled_ = false;
 };
+}  // namespace
 
 // pick the per-lane output count G of the background kernel: minimise idle lanes (sum of tile widths) with a small
 // penalty for the halo work of narrow tiles.
@@ -470,37 +542,31 @@ static int ensure_text_tables(natac_ctx *c) {
 }
 
 // exclusive scan of in[0..n) into out[0..n], out[n] = total (device arrays; n > 0).  The block sums are a temporary of the CALLER's scope
-// (`tmp`, freed after the caller's last synchronisation): freeing them here needed a stream synchronisation per scan -- six per formatted
-// track -- because the pool may hand a freed block to another context at once.
+// (`dc`, freed after the caller's last synchronisation): freeing them here needed a stream synchronisation per scan -- six per formatted
+// track -- because the pool may hand a freed block to another context at once.  A failure stays in the scope's latch.
 template <class T>
-static int dev_scan(natac_ctx *c, const T *in, long long n, unsigned long long *out, StreamTemps &tmp) {
+static void dev_scan(natac_ctx *c, const T *in, long long n, unsigned long long *out, DeviceCall &dc) {
     using namespace natac_textz;
     const long long nblk = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
-    unsigned long long *sums = nullptr;
-    int rc = tmp.alloc(&sums, (size_t)nblk + 1);
-    if (rc) return rc;
+    unsigned long long *sums = dc.alloc<unsigned long long>((size_t)nblk + 1);
+    if (!dc.ok()) return;
     hipLaunchKernelGGL((tz_scan_block_sums<T>), dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, sums);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nblk);
     hipLaunchKernelGGL((tz_scan_final<T>), dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, sums, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "scan: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.launched();
 }
 
 // the two scans over a track's runs (byte offsets and indices of its lines) in one pass over the length array (tz_scan2_*)
-static int dev_scan2(natac_ctx *c, const unsigned char *in, long long n, unsigned long long *out_sum, unsigned long long *out_cnt, StreamTemps &tmp) {
+static void dev_scan2(natac_ctx *c, const unsigned char *in, long long n, unsigned long long *out_sum, unsigned long long *out_cnt, DeviceCall &dc) {
     using namespace natac_textz;
     const long long nblk = (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK;
-    unsigned long long *sums = nullptr;
-    int rc = tmp.alloc(&sums, 2 * ((size_t)nblk + 1));
-    if (rc) return rc;
+    unsigned long long *sums = dc.alloc<unsigned long long>(2 * ((size_t)nblk + 1));
+    if (!dc.ok()) return;
     hipLaunchKernelGGL(tz_scan2_block_sums, dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, nblk, sums);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nblk);
     hipLaunchKernelGGL(tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums + nblk + 1, nblk);
     hipLaunchKernelGGL(tz_scan2_final, dim3((unsigned)nblk), dim3(256), 0, c->stream, in, n, nblk, sums, out_sum, out_cnt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "scan: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.launched();
 }
 
 // text / BGZF of a device array of per-base values laid out like the batch's tracks.  Result stays in b->d_fmt_out.
@@ -538,152 +604,145 @@ static int format_values(natac_batch *b, const double *d_vals, const int32_t *ch
     }
     const int line_cap = std::min<int>(MAX_LINE, (int)max_name + 2 * std::max(natac_text::digits_i64(max_coord), natac_text::digits_i64(min_coord)) + VTXT + 4);
     if (b->total_bp >= 0xffffffffLL) return fail(NATAC_E_ARG, "batch too long for the device writer (%lld bases)", b->total_bp);
-    StreamTemps tmp(c);
-    char *d_names = nullptr;
-    int *d_noff = nullptr, *d_cid = nullptr, *d_tc = nullptr, *d_C = nullptr, *d_hard = nullptr;
-    long long *d_cs = nullptr, *d_line_off = nullptr;
-    unsigned long long *d_tb = nullptr, *d_boff = nullptr, *d_lidx = nullptr;
-    unsigned int *d_R = nullptr;
-    unsigned char *d_len8 = nullptr, *d_text = nullptr;
-#define TRYF(x) do { if ((rc = (x)) != NATAC_OK) return rc; } while (0)
-    TRYF(tmp.upload(&d_names, cat.data(), cat.size()));
-    TRYF(tmp.upload(&d_noff, noff.data(), noff.size()));
-    TRYF(tmp.upload(&d_cid, chrom_id, (size_t)b->nc));
-    TRYF(tmp.upload(&d_cs, (const long long *)chunk_start, (size_t)b->nc));
-    TRYF(tmp.alloc(&d_hard, 1));
-    HIPCHK(hipMemsetAsync(d_hard, 0, sizeof(int), c->stream));
+    DeviceCall dc(c, "format_track");
+    char *d_names = dc.upload(cat.data(), cat.size());
+    int *d_noff = dc.upload(noff.data(), noff.size());
+    int *d_cid = dc.upload(chrom_id, (size_t)b->nc);
+    long long *d_cs = dc.upload((const long long *)chunk_start, (size_t)b->nc);
+    int *d_hard = dc.zeroed<int>(1);
     TextJob job;
     job.vals = d_vals; job.out_off = b->d_out_off; job.chunk_len = b->d_len; job.tiles = b->d_tiles256; job.ntiles = b->n_tiles256;
     job.chrom_id = d_cid; job.chunk_start = d_cs; job.names = d_names; job.name_off = d_noff; job.p10 = c->d_p10;
     job.write_zero = write_zero & 1; job.keep_before_nan = (write_zero >> 1) & 1;
     const int nt = b->n_tiles256;
-    TRYF(tmp.alloc(&d_tc, (size_t)nt));
-    TRYF(tmp.alloc(&d_tb, (size_t)nt + 1));
-    hipLaunchKernelGGL(tz_flags_count, dim3(nt), dim3(256), 0, c->stream, job, d_tc);
-    TRYF(dev_scan(c, d_tc, (long long)nt, d_tb, tmp));
+    int *d_tc = dc.alloc<int>((size_t)nt);
+    unsigned long long *d_tb = dc.alloc<unsigned long long>((size_t)nt + 1);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_flags_count, dim3(nt), dim3(256), 0, c->stream, job, d_tc);
+        dev_scan(c, d_tc, (long long)nt, d_tb, dc);
+    }
     unsigned long long nruns = 0;
-    HIPCHK(hipMemcpyAsync(&nruns, d_tb + nt, sizeof nruns, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    TRYF(tmp.alloc(&d_R, (size_t)nruns));
-    TRYF(tmp.alloc(&d_C, (size_t)nruns));
-    hipLaunchKernelGGL(tz_scatter_runs, dim3(nt), dim3(256), 0, c->stream, job, d_tb, d_R, d_C);
-    TRYF(tmp.alloc(&d_len8, (size_t)nruns));
+    dc.fetch(&nruns, d_tb + nt, 1);
+    if ((rc = dc.sync())) return rc;
+    unsigned int *d_R = dc.alloc<unsigned int>((size_t)nruns);
+    int *d_C = dc.alloc<int>((size_t)nruns);
+    unsigned char *d_len8 = dc.alloc<unsigned char>((size_t)nruns);
     const unsigned rb = (unsigned)((nruns + 255) / 256);
-    unsigned long long *d_vtxt = nullptr;             // text of every run's value (tz_line_len -> tz_write_lines)
-    TRYF(tmp.alloc(&d_vtxt, (size_t)nruns * (natac_textz::VTXT / 8)));
-    hipLaunchKernelGGL(tz_line_len, dim3(rb), dim3(256), 0, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_hard, d_vtxt);
-    TRYF(tmp.alloc(&d_boff, (size_t)nruns + 1));
-    TRYF(tmp.alloc(&d_lidx, (size_t)nruns + 1));
-    TRYF(dev_scan2(c, d_len8, (long long)nruns, d_boff, d_lidx, tmp));
+    unsigned long long *d_vtxt = dc.alloc<unsigned long long>((size_t)nruns * (natac_textz::VTXT / 8));   // text of every run's value (tz_line_len -> tz_write_lines)
+    unsigned long long *d_boff = dc.alloc<unsigned long long>((size_t)nruns + 1);
+    unsigned long long *d_lidx = dc.alloc<unsigned long long>((size_t)nruns + 1);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_scatter_runs, dim3(nt), dim3(256), 0, c->stream, job, d_tb, d_R, d_C);
+        hipLaunchKernelGGL(tz_line_len, dim3(rb), dim3(256), 0, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_hard, d_vtxt);
+        dev_scan2(c, d_len8, (long long)nruns, d_boff, d_lidx, dc);
+    }
     unsigned long long n_text = 0, nlines = 0;
     int hard = 0;
-    HIPCHK(hipMemcpyAsync(&n_text, d_boff + nruns, sizeof n_text, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&nlines, d_lidx + nruns, sizeof nlines, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(&hard, d_hard, sizeof hard, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    dc.fetch(&n_text, d_boff + nruns, 1);
+    dc.fetch(&nlines, d_lidx + nruns, 1);
+    dc.fetch(&hard, d_hard, 1);
+    if ((rc = dc.sync())) return rc;
     b->fmt_text_bytes = (long long)n_text;
     if (n_text_bytes) *n_text_bytes = (int64_t)n_text;
     if (n_lines) *n_lines = (int64_t)nlines;
     if (n_hard) *n_hard = hard;
     if (n_text == 0) { b->fmt_bytes = 0; if (n_bytes) *n_bytes = 0; return NATAC_OK; }
+    unsigned char *d_text = nullptr;
     if (compress) {
-        TRYF(tmp.alloc(&d_text, (size_t)n_text + 64));
+        d_text = dc.alloc<unsigned char>((size_t)n_text + 64);
     } else {           // the text is the result: written in place (a failed call leaves fmt_bytes at -1)
-        TRYF(dev_alloc(b->d_fmt_out, (size_t)n_text + 64));
+        if ((rc = dev_alloc(b->d_fmt_out, (size_t)n_text + 64))) return rc;
         d_text = b->d_fmt_out;
     }
-    TRYF(tmp.alloc(&d_line_off, (size_t)nlines + 1));
+    long long *d_line_off = dc.alloc<long long>((size_t)nlines + 1);
     int *d_lcid = nullptr;
     long long *d_lbeg = nullptr, *d_lend = nullptr;
     if (compress) {
-        TRYF(tmp.alloc(&d_lcid, (size_t)nlines));
-        TRYF(tmp.alloc(&d_lbeg, (size_t)nlines));
-        TRYF(tmp.alloc(&d_lend, (size_t)nlines));
+        d_lcid = dc.alloc<int>((size_t)nlines);
+        d_lbeg = dc.alloc<long long>((size_t)nlines);
+        d_lend = dc.alloc<long long>((size_t)nlines);
     }
-    hipLaunchKernelGGL(tz_write_lines, dim3(rb), dim3(256), (size_t)256 * line_cap + 32, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_boff, d_lidx, d_vtxt, d_text,
-                       d_line_off, d_lcid, d_lbeg, d_lend);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_write_lines, dim3(rb), dim3(256), (size_t)256 * line_cap + 32, c->stream, job, (long long)nruns, d_R, d_C, d_len8, d_boff, d_lidx, d_vtxt, d_text,
+                           d_line_off, d_lcid, d_lbeg, d_lend);
+        dc.launched();
+    }
     if (!compress) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e));
+        if ((rc = dc.finish())) return rc;
         b->fmt_bytes = (long long)n_text;
         if (n_bytes) *n_bytes = (int64_t)n_text;
         return NATAC_OK;
     }
     namespace nd = natac_deflate;
     const long long nblk = ((long long)n_text + nd::BLK - 1) / nd::BLK;
-    unsigned int *d_hist = nullptr, *d_sizes = nullptr;
-    nd::Codes *d_codes = nullptr;
-    unsigned char *d_regions = nullptr;
-    unsigned long long *d_pos = nullptr;
-    TRYF(tmp.alloc(&d_hist, (size_t)nd::NLL + nd::ND));
-    HIPCHK(hipMemsetAsync(d_hist, 0, (nd::NLL + nd::ND) * sizeof(unsigned int), c->stream));
+    unsigned int *d_hist = dc.zeroed<unsigned int>((size_t)nd::NLL + nd::ND);
     // line segments per member -> offsets of the per-segment records pass A of the emit kernel leaves for its pass B
-    unsigned int *d_nseg = nullptr;
-    unsigned long long *d_segbase = nullptr;
-    unsigned int *d_stage = nullptr;
-    unsigned short *d_segbits = nullptr;
-    long long *d_k0 = nullptr;
-    TRYF(tmp.alloc(&d_nseg, (size_t)nblk));
-    TRYF(tmp.alloc(&d_segbase, (size_t)nblk + 1));
-    TRYF(tmp.alloc(&d_k0, (size_t)nblk));
-    hipLaunchKernelGGL(tz_member_nseg, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, c->stream, d_line_off, (long long)nlines,
-                       (long long)n_text, nblk, d_nseg, d_k0);
-    TRYF(dev_scan(c, d_nseg, nblk, d_segbase, tmp));
-    TRYF(tmp.alloc(&d_segbits, (size_t)nlines + (size_t)nblk + 64));  // every line once + one more per straddled member border
-    TRYF(tmp.alloc(&d_stage, (size_t)nblk * STAGE_WORDS));             // the lines' finished bits between the emit kernel's two passes
+    unsigned int *d_nseg = dc.alloc<unsigned int>((size_t)nblk);
+    unsigned long long *d_segbase = dc.alloc<unsigned long long>((size_t)nblk + 1);
+    long long *d_k0 = dc.alloc<long long>((size_t)nblk);
+    unsigned short *d_segbits = dc.alloc<unsigned short>((size_t)nlines + (size_t)nblk + 64);  // every line once + one more per straddled member border
+    unsigned int *d_stage = dc.alloc<unsigned int>((size_t)nblk * STAGE_WORDS);                // the lines' finished bits between the emit kernel's two passes
     // token histogram of a sample of the members (every member of a small batch): natac_deflate.hpp, sample_stride
     const int stride = nd::sample_stride(nblk);
     const long long counted = (nblk + stride - 1) / stride;
     const size_t lds_count = 65536 + (nd::NLL + nd::ND) * sizeof(unsigned int);
-    hipLaunchKernelGGL(tz_count_tokens, dim3((unsigned)counted), dim3(TZ_THREADS), lds_count, c->stream, d_text, (long long)n_text, d_line_off,
-                       (long long)nlines, stride, d_nseg, d_k0, d_hist);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_member_nseg, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, c->stream, d_line_off, (long long)nlines,
+                           (long long)n_text, nblk, d_nseg, d_k0);
+        dev_scan(c, d_nseg, nblk, d_segbase, dc);
+    }
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_count_tokens, dim3((unsigned)counted), dim3(TZ_THREADS), lds_count, c->stream, d_text, (long long)n_text, d_line_off,
+                           (long long)nlines, stride, d_nseg, d_k0, d_hist);
+        dc.launched();
+    }
     unsigned int hist[nd::NLL + nd::ND];
-    HIPCHK(hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    dc.fetch(hist, d_hist, (size_t)nd::NLL + nd::ND);
+    if ((rc = dc.sync())) return rc;
     nd::finish_hist(hist, hist + nd::NLL, counted, stride);      // one end-of-block per counted member; a code for every symbol when sampled
     nd::Codes codes;
     if (!nd::build_codes(hist, hist + nd::NLL, codes)) return fail(NATAC_E_ARG, "format_track: Huffman table description too long");
-    TRYF(tmp.upload(&d_codes, &codes, 1));
-    TRYF(tmp.alloc(&d_regions, (size_t)nblk * nd::REGION));
-    HIPCHK(hipMemsetAsync(d_regions, 0, (size_t)nblk * nd::REGION, c->stream));
-    TRYF(tmp.alloc(&d_sizes, (size_t)nblk));
-    TRYF(tmp.alloc(&d_pos, (size_t)nblk + 1));
+    nd::Codes *d_codes = dc.upload(&codes, 1);
+    unsigned char *d_regions = dc.zeroed<unsigned char>((size_t)nblk * nd::REGION);
+    unsigned int *d_sizes = dc.alloc<unsigned int>((size_t)nblk);
+    unsigned long long *d_pos = dc.alloc<unsigned long long>((size_t)nblk + 1);
     const size_t lds_emit = 65536 + ((sizeof(nd::Codes) + 15) & ~(size_t)15);
-    hipLaunchKernelGGL(tz_emit_members, dim3((unsigned)nblk), dim3(TZ_THREADS), lds_emit, c->stream, d_text, (long long)n_text, d_line_off,
-                       (long long)nlines, d_nseg, d_k0, d_segbase, d_stage, d_segbits, d_codes, c->d_crc, d_regions, d_sizes);
-    HIPCHK(hipGetLastError());
-    TRYF(dev_scan(c, d_sizes, nblk, d_pos, tmp));
-    b->fmt_member_pos.resize((size_t)nblk + 1);
-    HIPCHK(hipMemcpyAsync(b->fmt_member_pos.data(), d_pos, ((size_t)nblk + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    {   // tabix records: runs of lines per leaf bin (tz_group_*)
-        unsigned char *d_gf = nullptr;
-        unsigned long long *d_gidx = nullptr;
-        long long *d_first = nullptr;
-        GroupRec *d_rec = nullptr;
-        const unsigned lb = (unsigned)((nlines + 255) / 256);
-        TRYF(tmp.alloc(&d_gf, (size_t)nlines));
-        TRYF(tmp.alloc(&d_gidx, (size_t)nlines + 1));
-        hipLaunchKernelGGL(tz_group_flags, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_lcid, d_lbeg, d_lend, d_gf);
-        TRYF(dev_scan(c, d_gf, (long long)nlines, d_gidx, tmp));
-        unsigned long long ngroups = 0;
-        HIPCHK(hipMemcpyAsync(&ngroups, d_gidx + nlines, sizeof ngroups, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        TRYF(tmp.alloc(&d_first, (size_t)ngroups));
-        TRYF(tmp.alloc(&d_rec, (size_t)ngroups));
-        hipLaunchKernelGGL(tz_group_starts, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_gf, d_gidx, d_first);
-        hipLaunchKernelGGL(tz_group_records, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, c->stream, (long long)ngroups, d_first,
-                           (long long)nlines, d_lcid, d_lbeg, d_lend, d_line_off, (long long)n_text, d_rec);
-        b->fmt_groups.resize((size_t)ngroups);
-        HIPCHK(hipMemcpyAsync(b->fmt_groups.data(), d_rec, (size_t)ngroups * sizeof(GroupRec), hipMemcpyDeviceToHost, c->stream));
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_emit_members, dim3((unsigned)nblk), dim3(TZ_THREADS), lds_emit, c->stream, d_text, (long long)n_text, d_line_off,
+                           (long long)nlines, d_nseg, d_k0, d_segbase, d_stage, d_segbits, d_codes, c->d_crc, d_regions, d_sizes);
+        dc.launched();
     }
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (dc.ok()) dev_scan(c, d_sizes, nblk, d_pos, dc);
+    b->fmt_member_pos.resize((size_t)nblk + 1);
+    dc.fetch(b->fmt_member_pos.data(), d_pos, (size_t)nblk + 1);
+    {   // tabix records: runs of lines per leaf bin (tz_group_*)
+        const unsigned lb = (unsigned)((nlines + 255) / 256);
+        unsigned char *d_gf = dc.alloc<unsigned char>((size_t)nlines);
+        unsigned long long *d_gidx = dc.alloc<unsigned long long>((size_t)nlines + 1);
+        if (dc.ok()) {
+            hipLaunchKernelGGL(tz_group_flags, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_lcid, d_lbeg, d_lend, d_gf);
+            dev_scan(c, d_gf, (long long)nlines, d_gidx, dc);
+        }
+        unsigned long long ngroups = 0;
+        dc.fetch(&ngroups, d_gidx + nlines, 1);
+        if ((rc = dc.sync())) return rc;
+        long long *d_first = dc.alloc<long long>((size_t)ngroups);
+        GroupRec *d_rec = dc.alloc<GroupRec>((size_t)ngroups);
+        if (dc.ok()) {
+            hipLaunchKernelGGL(tz_group_starts, dim3(lb), dim3(256), 0, c->stream, (long long)nlines, d_gf, d_gidx, d_first);
+            hipLaunchKernelGGL(tz_group_records, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, c->stream, (long long)ngroups, d_first,
+                               (long long)nlines, d_lcid, d_lbeg, d_lend, d_line_off, (long long)n_text, d_rec);
+            dc.launched();
+        }
+        b->fmt_groups.resize((size_t)ngroups);
+        dc.fetch(b->fmt_groups.data(), d_rec, (size_t)ngroups);
+    }
+    if ((rc = dc.sync())) return rc;
     const unsigned long long total = b->fmt_member_pos[(size_t)nblk];
-    TRYF(dev_alloc(b->d_fmt_out, (size_t)total + 64));
+    if ((rc = dev_alloc(b->d_fmt_out, (size_t)total + 64))) return rc;
     hipLaunchKernelGGL(tz_compact, dim3((unsigned)nblk), dim3(256), 0, c->stream, d_regions, d_sizes, d_pos, b->d_fmt_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "format_track: %s", hipGetErrorString(e));
-#undef TRYF
+    dc.launched();
+    if ((rc = dc.finish())) return rc;
     b->fmt_bytes = (long long)total;
     if (n_bytes) *n_bytes = (int64_t)total;
     return NATAC_OK;
@@ -1212,25 +1271,20 @@ int natac_batch_create_from_seq(natac_ctx *c, int32_t nc, const int32_t *chunk_l
     int rc = natac_batch_create(c, nc, chunk_len, frag_off, frag_lpos, frag_ilen, boff.data(), nullptr, bias_left, bias_right, out);
     if (rc) return rc;
     natac_batch *b = *out;
-    StreamTemps tmp(c);
-    unsigned char *d_s = nullptr, *d_n = nullptr;
-    long long *d_so = nullptr;
-    double *d_p = nullptr;
-    const size_t nseq = (size_t)seq_off[nc];
-    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, nseq)) == NATAC_OK &&
-        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)nc + 1)) == NATAC_OK &&
-        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) == NATAC_OK &&
-        (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)) == NATAC_OK) {
+    DeviceCall dc(c, "pwm score");
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)seq_off[nc]);
+    const long long *d_so = dc.upload((const long long *)seq_off, (size_t)nc + 1);
+    const unsigned char *d_n = dc.upload((const unsigned char *)nucleotides, (size_t)nrow);
+    const double *d_p = dc.upload(log_pwm, (size_t)nrow * K);
+    if (dc.ok()) {
         int maxlen = 0;
         for (int i = 0; i < nc; ++i) maxlen = std::max(maxlen, chunk_len[i] + bias_left + bias_right);
         const unsigned gx = (unsigned)std::min(16, (maxlen + 1023) / 1024);
         hipLaunchKernelGGL(natac_pwm_score_chunks, dim3(gx, (unsigned)nc), dim3(256), 0, c->stream, d_s, d_so, b->d_bias_off, d_p, d_n, nrow, K,
                            b->d_bias);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(NATAC_E_HIP, "pwm score: %s", hipGetErrorString(e));
+        dc.launched();
     }
-    if (rc) { natac_batch_free(b); *out = nullptr; }
+    if ((rc = dc.finish())) { natac_batch_free(b); *out = nullptr; }
     return rc;
 }
 
@@ -1736,19 +1790,20 @@ int natac_run_ins_smooth(natac_batch *b, int lower, int upper, const double *w, 
         if (!std::isfinite(w[j])) return fail(NATAC_E_ARG, "window tap %d is not finite", j);
     if (!(wsum > 0) || !std::isfinite(wsum)) return fail(NATAC_E_ARG, "window sum must be positive and finite (got %g)", wsum);
     natac_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "ins_smooth");
     int rc;
+    if (!dc.ok()) return dc.finish();
     if ((rc = ensure_track(b, NATAC_T_INS_SMOOTH)) || (rc = ensure_tiles1k(b))) return rc;
-    StreamTemps tmp(c);                // the window: on the device for this call only
-    double *d_w = nullptr;
-    if ((rc = tmp.upload(&d_w, w, (size_t)M))) return rc;
-    natac_ctx::Ev ev;
-    prof_begin(c, NATAC_K_INS_SMOOTH, ev, c->stream);
-    hipLaunchKernelGGL(natac_ins_smooth, dim3(b->n_tiles1k), dim3(TR_BLOCK), ins_smooth_lds(M), c->stream, b->d_tiles1k.get(), b->d_len.get(),
-                       b->d_frag_off.get(), b->d_lpos.get(), b->d_ilen.get(), b->d_centre.get(), b->d_out_off.get(), lower, upper, d_w, M, wsum,
-                       b->d_track[NATAC_T_INS_SMOOTH].get());
-    prof_end(c, ev);
-    HIPCHK(hipGetLastError());
+    const double *d_w = dc.upload(w, (size_t)M);     // the window: on the device for this call only
+    if (dc.ok()) {
+        dc.prof_begin(NATAC_K_INS_SMOOTH);
+        hipLaunchKernelGGL(natac_ins_smooth, dim3(b->n_tiles1k), dim3(TR_BLOCK), ins_smooth_lds(M), c->stream, b->d_tiles1k.get(), b->d_len.get(),
+                           b->d_frag_off.get(), b->d_lpos.get(), b->d_ilen.get(), b->d_centre.get(), b->d_out_off.get(), lower, upper, d_w, M, wsum,
+                           b->d_track[NATAC_T_INS_SMOOTH].get());
+        dc.prof_end();
+        dc.launched();
+    }
+    if ((rc = dc.finish())) return rc;          // the window must outlive the kernel
     b->out.track[NATAC_T_INS_SMOOTH] = TS_RUN;
     return NATAC_OK;
 }
@@ -1790,24 +1845,23 @@ int natac_run_pwm_track(natac_batch *b, const int64_t *seq_off, const uint8_t *s
         if (seq_off[i + 1] - seq_off[i] != (int64_t)b->h_len[i] + K - 1)
             return fail(NATAC_E_ARG, "sequence window of chunk %d must hold %lld bases (its length + K - 1)", i, (long long)b->h_len[i] + K - 1);
     natac_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "pwm_track");
     int rc;
+    if (!dc.ok()) return dc.finish();
     if ((rc = ensure_track(b, NATAC_T_BIAS)) || (rc = ensure_tiles1k(b))) return rc;
-    StreamTemps tmp(c);                // sequence, offsets, table and letters: on the device for this call only
-    unsigned char *d_s = nullptr, *d_n = nullptr;
-    long long *d_so = nullptr;
-    double *d_p = nullptr;
-    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)seq_off[b->nc])) ||
-        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)b->nc + 1)) ||
-        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) || (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)))
-        return rc;
-    natac_ctx::Ev ev;
-    prof_begin(c, NATAC_K_PWM_TRACK, ev, c->stream);
-    hipLaunchKernelGGL(natac_pwm_track, dim3(b->n_tiles1k), dim3(TR_BLOCK), pwm_track_lds(nrow, K), c->stream, b->d_tiles1k.get(), b->d_len.get(),
-                       d_so, d_s, b->d_out_off.get(), d_p, d_n, nrow, K, b->d_track[NATAC_T_BIAS].get());
-    prof_end(c, ev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));     // the host arrays may be released by the caller after return
+    // sequence, offsets, table and letters: on the device for this call only
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)seq_off[b->nc]);
+    const long long *d_so = dc.upload((const long long *)seq_off, (size_t)b->nc + 1);
+    const unsigned char *d_n = dc.upload((const unsigned char *)nucleotides, (size_t)nrow);
+    const double *d_p = dc.upload(log_pwm, (size_t)nrow * K);
+    if (dc.ok()) {
+        dc.prof_begin(NATAC_K_PWM_TRACK);
+        hipLaunchKernelGGL(natac_pwm_track, dim3(b->n_tiles1k), dim3(TR_BLOCK), pwm_track_lds(nrow, K), c->stream, b->d_tiles1k.get(), b->d_len.get(),
+                           d_so, d_s, b->d_out_off.get(), d_p, d_n, nrow, K, b->d_track[NATAC_T_BIAS].get());
+        dc.prof_end();
+        dc.launched();
+    }
+    if ((rc = dc.finish())) return rc;           // the host arrays may be released by the caller after return
     b->out.track[NATAC_T_BIAS] = TS_RUN;
     return NATAC_OK;
 }
@@ -1829,35 +1883,30 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !lr || !var || !z))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
     if (n_cand > 0x7fffffffLL) return fail(NATAC_E_ARG, "too many candidates");
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "candidates");
+    if (!dc.ok()) return dc.finish();
     for (int64_t k = 0; k < n_cand; ++k) {
         const int ci = cand_chunk[k];
         if (ci < 0 || ci >= b->nc || cand_pos[k] < 0 || cand_pos[k] >= b->h_len[ci])
             return fail(NATAC_E_ARG, "candidate %lld out of range (chunk %d pos %d)", (long long)k, ci, cand_pos[k]);
     }
-    StreamTemps tmp(c);
-    int *d_cc = nullptr, *d_cp = nullptr;
-    double *d_out = nullptr;
-    if ((rc = tmp.upload(&d_cc, cand_chunk, (size_t)n_cand)) || (rc = tmp.upload(&d_cp, cand_pos, (size_t)n_cand)) ||
-        (rc = tmp.alloc(&d_out, (size_t)3 * n_cand)))
-        return rc;
-    const ChunkTable ct = make_table(b);
-    const VMatDev vm = make_vmat(c);
-    natac_ctx::Ev ev;
-    prof_begin(c, NATAC_K_CAND, ev);
-    launch_candidates(c, ct, vm, d_cc, d_cp, n_cand, b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_NORM],
-                      b->out.bg_gen == c->model_gen ? b->d_bnum : nullptr, b->out.bg_gen == c->model_gen ? b->d_bcov : nullptr, d_out,
-                      d_out + n_cand,
-                      d_out + 2 * n_cand, b->ranges256_w == c->vw ? b->d_tile256_first : nullptr, b->ranges256_w == c->vw ? b->d_ranges256 : nullptr);
-    prof_end(c, ev);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(lr, d_out, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, d_out + n_cand, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(z, d_out + 2 * n_cand, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates: %s", hipGetErrorString(e));
-    prof_collect(c);
-    return NATAC_OK;
+    const int *d_cc = dc.upload(cand_chunk, (size_t)n_cand), *d_cp = dc.upload(cand_pos, (size_t)n_cand);
+    double *d_out = dc.alloc<double>((size_t)3 * n_cand);
+    if (dc.ok()) {
+        const ChunkTable ct = make_table(b);
+        const VMatDev vm = make_vmat(c);
+        dc.prof_begin(NATAC_K_CAND);
+        launch_candidates(c, ct, vm, d_cc, d_cp, n_cand, b->d_track[NATAC_T_NUC_COV], b->d_track[NATAC_T_NORM],
+                          b->out.bg_gen == c->model_gen ? b->d_bnum : nullptr, b->out.bg_gen == c->model_gen ? b->d_bcov : nullptr, d_out,
+                          d_out + n_cand,
+                          d_out + 2 * n_cand, b->ranges256_w == c->vw ? b->d_tile256_first : nullptr, b->ranges256_w == c->vw ? b->d_ranges256 : nullptr);
+        dc.prof_end();
+        dc.launched();
+    }
+    dc.fetch(lr, d_out, (size_t)n_cand);
+    dc.fetch(var, d_out + n_cand, (size_t)n_cand);
+    dc.fetch(z, d_out + 2 * n_cand, (size_t)n_cand);
+    return dc.finish();
 }
 
 int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand_chunk, const int32_t *cand_pos, int mode,
@@ -1869,7 +1918,8 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     if (mode < 0 || mode > 2) return fail(NATAC_E_ARG, "mode must be 0 (closed form), 1 (literal) or 2 (closed form in fp32)");
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !var))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "candidates_cov");
+    if (!dc.ok()) return dc.finish();
     if ((rc = ensure_srow(c))) return rc;
     for (int64_t k = 0; k < n_cand; ++k) {
         const int ci = cand_chunk[k];
@@ -1884,53 +1934,48 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     const int EW = c->W + ((c->vupper - 2) >> 1) + ((c->vupper - 1) >> 1);
     const int64_t slab = std::min<int64_t>(SLAB, n_cand);
     std::vector<double> part((size_t)slab * NBLK);
-    {
-        StreamTemps tmp(c);
-        int *d_cc = nullptr, *d_cp = nullptr;
-        double *d_p = nullptr, *d_out = nullptr;
-        if ((rc = tmp.alloc(&d_cc, (size_t)slab)) || (rc = tmp.alloc(&d_cp, (size_t)slab)) || (rc = tmp.alloc(&d_p, (size_t)slab * N)) ||
-            (rc = tmp.alloc(&d_out, (size_t)slab * NBLK)))
-            return rc;
-        for (int64_t k0 = 0; k0 < n_cand; k0 += slab) {
-            const int64_t m = std::min<int64_t>(slab, n_cand - k0);
-            hipError_t e = hipMemcpyAsync(d_cc, cand_chunk + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_cp, cand_pos + k0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
+    int *d_cc = dc.alloc<int>((size_t)slab), *d_cp = dc.alloc<int>((size_t)slab);
+    double *d_p = dc.alloc<double>((size_t)slab * N), *d_out = dc.alloc<double>((size_t)slab * NBLK);
+    for (int64_t k0 = 0; k0 < n_cand; k0 += slab) {
+        const int64_t m = std::min<int64_t>(slab, n_cand - k0);
+        const int per = mode == 1 ? NBLK : 1;
+        dc.send(d_cc, cand_chunk + k0, (size_t)m);
+        dc.send(d_cp, cand_pos + k0, (size_t)m);
+        if (dc.ok()) {
             hipLaunchKernelGGL(natac_cand_window_probs, dim3((unsigned)m), dim3(256), (size_t)(EW + 2) * sizeof(double), c->stream, ct, vm,
                                d_cc, d_cp, d_p);
-            const int per = mode == 1 ? NBLK : 1;
+            dc.launched();
+        }
+        if (dc.ok()) {
             if (mode == 1)
                 hipLaunchKernelGGL(natac_cov_literal_many, dim3(NBLK, (unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
             else if (mode == 0)
                 hipLaunchKernelGGL((natac_cov_closed_many<double>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
             else
                 hipLaunchKernelGGL((natac_cov_closed_many<float>), dim3((unsigned)m), dim3(256), 0, c->stream, d_p, c->d_vmat, N, d_out);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_out, (size_t)m * per * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
-            for (int64_t k = 0; k < m; ++k) {
-                double s = 0;
-                for (int j = 0; j < per; ++j) s += part[(size_t)k * per + j];
-                var[k0 + k] = s;
-            }
+            dc.launched();
+        }
+        dc.fetch(part.data(), d_out, (size_t)m * per);
+        if ((rc = dc.sync())) return rc;
+        for (int64_t k = 0; k < m; ++k) {
+            double s = 0;
+            for (int j = 0; j < per; ++j) s += part[(size_t)k * per + j];
+            var[k0 + k] = s;
         }
     }
     // r = int(nuc_cov[pos]) like the .pyx's `int r` (NucleosomeCalling.py:125): one gather of the coverage values
     std::vector<double> reads((size_t)n_cand);
-    {
-        std::vector<long long> idx((size_t)n_cand);
-        for (int64_t k = 0; k < n_cand; ++k) idx[(size_t)k] = b->h_out_off[cand_chunk[k]] + cand_pos[k];
-        StreamTemps tmp(c);
-        long long *d_idx = nullptr;
-        double *d_r = nullptr;
-        if ((rc = tmp.upload(&d_idx, idx.data(), (size_t)n_cand)) || (rc = tmp.alloc(&d_r, (size_t)n_cand))) return rc;
+    std::vector<long long> idx((size_t)n_cand);
+    for (int64_t k = 0; k < n_cand; ++k) idx[(size_t)k] = b->h_out_off[cand_chunk[k]] + cand_pos[k];
+    const long long *d_idx = dc.upload(idx.data(), (size_t)n_cand);
+    double *d_r = dc.alloc<double>((size_t)n_cand);
+    if (dc.ok()) {
         hipLaunchKernelGGL(natac_gather_f64, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, c->stream,
                            b->d_track[NATAC_T_NUC_COV], d_idx, (long long)n_cand, d_r);
-        hipError_t e = hipMemcpyAsync(reads.data(), d_r, (size_t)n_cand * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return fail(NATAC_E_HIP, "candidates_cov: %s", hipGetErrorString(e));
+        dc.launched();
     }
+    dc.fetch(reads.data(), d_r, (size_t)n_cand);
+    if ((rc = dc.finish())) return rc;
     for (int64_t k = 0; k < n_cand; ++k) var[k] = var[k] * (double)(int)reads[(size_t)k];
     return NATAC_OK;
 }
@@ -2235,24 +2280,18 @@ int natac_make_fragment_mat(natac_ctx *c, int64_t nf, const int64_t *l, const in
     if (end <= start || upper <= lower) return fail(NATAC_E_ARG, "empty matrix");
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    long long *d_l = nullptr; int *d_n = nullptr; double *d_m = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
-        (rc = tmp.alloc(&d_m, (size_t)(nrow * ncol))))
-        return rc;
-    hipError_t e = hipMemsetAsync(d_m, 0, (size_t)(nrow * ncol) * sizeof(double), c->stream);
-    if (e == hipSuccess && nf > 0) {
+    DeviceCall dc(c, "make_fragment_mat");
+    const long long *d_l = dc.upload((const long long *)l, (size_t)nf);
+    const int *d_n = dc.upload(n, (size_t)nf);
+    double *d_m = dc.zeroed<double>((size_t)(nrow * ncol));
+    if (dc.ok() && nf > 0) {
         int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
         hipLaunchKernelGGL(natac_fragment_mat, dim3(blocks), dim3(256), 0, c->stream, d_l, d_n, (long long)nf, (long long)start,
                            (int)ncol, lower, (int)nrow, d_m);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(mat, d_m, (size_t)(nrow * ncol) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "make_fragment_mat: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.fetch(mat, d_m, (size_t)(nrow * ncol));
+    return dc.finish();
 }
 
 int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32_t *n, int64_t start, int64_t end, int lower,
@@ -2261,15 +2300,12 @@ int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     if (end <= start) return fail(NATAC_E_ARG, "empty region");
     const long long npos = end - start;
     if (npos > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    long long *d_l = nullptr; int *d_n = nullptr, *d_i = nullptr; double *d_o = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
-        (rc = tmp.alloc(&d_i, (size_t)npos)) || (rc = tmp.alloc(&d_o, (size_t)npos)))
-        return rc;
-    hipError_t e = hipMemsetAsync(d_i, 0, (size_t)npos * sizeof(int), c->stream);
-    if (e == hipSuccess) {
+    DeviceCall dc(c, "get_insertions");
+    const long long *d_l = dc.upload((const long long *)l, (size_t)nf);
+    const int *d_n = dc.upload(n, (size_t)nf);
+    int *d_i = dc.zeroed<int>((size_t)npos);
+    double *d_o = dc.alloc<double>((size_t)npos);
+    if (dc.ok()) {
         if (nf > 0) {
             int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
             hipLaunchKernelGGL(natac_insertions_region, dim3(blocks), dim3(256), 0, c->stream, d_l, d_n, (long long)nf,
@@ -2277,12 +2313,10 @@ int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32
         }
         int blocks = (int)std::min<long long>((npos + 255) / 256, 4096);
         hipLaunchKernelGGL(natac_i32_to_f64, dim3(blocks), dim3(256), 0, c->stream, d_i, d_o, npos);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "get_insertions: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.fetch(out, d_o, (size_t)npos);
+    return dc.finish();
 }
 
 int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32_t *n, int64_t start, int64_t end, int lower,
@@ -2291,15 +2325,12 @@ int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, co
     if (end <= start) return fail(NATAC_E_ARG, "empty region");
     const long long npos = end - start;
     if (npos > 0x3fffffffLL) return fail(NATAC_E_ARG, "region too long");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    long long *d_l = nullptr; int *d_n = nullptr, *d_i = nullptr; double *d_o = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
-        (rc = tmp.alloc(&d_i, (size_t)2 * npos)) || (rc = tmp.alloc(&d_o, (size_t)2 * npos)))
-        return rc;
-    hipError_t e = hipMemsetAsync(d_i, 0, (size_t)2 * npos * sizeof(int), c->stream);
-    if (e == hipSuccess) {
+    DeviceCall dc(c, "get_stranded_insertions");
+    const long long *d_l = dc.upload((const long long *)l, (size_t)nf);
+    const int *d_n = dc.upload(n, (size_t)nf);
+    int *d_i = dc.zeroed<int>((size_t)2 * npos);
+    double *d_o = dc.alloc<double>((size_t)2 * npos);
+    if (dc.ok()) {
         if (nf > 0) {
             int blocks = (int)std::min<long long>((nf + 255) / 256, 4096);
             hipLaunchKernelGGL(natac_stranded_insertions_region, dim3(blocks), dim3(256), 0, c->stream, d_l, d_n, (long long)nf,
@@ -2307,13 +2338,11 @@ int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, co
         }
         int blocks = (int)std::min<long long>((2 * npos + 255) / 256, 4096);
         hipLaunchKernelGGL(natac_i32_to_f64, dim3(blocks), dim3(256), 0, c->stream, d_i, d_o, 2 * npos);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(plus, d_o, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(minus, d_o + npos, (size_t)npos * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "get_stranded_insertions: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.fetch(plus, d_o, (size_t)npos);
+    dc.fetch(minus, d_o + npos, (size_t)npos);
+    return dc.finish();
 }
 
 int natac_fragment_sizes(natac_ctx *c, int64_t nf, const int64_t *l, const int32_t *n, int32_t nchunks, const int64_t *cs,
@@ -2323,38 +2352,32 @@ int natac_fragment_sizes(natac_ctx *c, int64_t nf, const int64_t *l, const int32
     if (nf < 0 || nchunks < 0) return fail(NATAC_E_ARG, "negative size");
     const int nb = upper - lower;
     if (nb > (1 << 20)) return fail(NATAC_E_ARG, "size range too wide");
-    HIPCHK(hipSetDevice(c->device));
     // chunk starts and ends sorted independently: #{cs <= x} - #{ce <= x} chunks contain x (see natac_size_hist);
     // an inverted interval (end < start) contains nothing, like the reference's `center >= start and center < end`
     std::vector<long long> hs((size_t)nchunks), he((size_t)nchunks);
     for (int k = 0; k < nchunks; ++k) { hs[k] = cs[k]; he[k] = std::max<long long>(ce[k], cs[k]); }
     std::sort(hs.begin(), hs.end());
     std::sort(he.begin(), he.end());
-    StreamTemps tmp(c);
-    long long *d_l = nullptr, *d_cs = nullptr, *d_ce = nullptr; int *d_n = nullptr; unsigned long long *d_h = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_l, (const long long *)l, (size_t)nf)) || (rc = tmp.upload(&d_n, n, (size_t)nf)) ||
-        (rc = tmp.upload(&d_cs, hs.data(), (size_t)nchunks)) || (rc = tmp.upload(&d_ce, he.data(), (size_t)nchunks)) ||
-        (rc = tmp.alloc(&d_h, (size_t)nb)))
-        return rc;
+    DeviceCall dc(c, "fragment_sizes");
+    const long long *d_l = dc.upload((const long long *)l, (size_t)nf);
+    const int *d_n = dc.upload(n, (size_t)nf);
+    const long long *d_cs = dc.upload(hs.data(), (size_t)nchunks), *d_ce = dc.upload(he.data(), (size_t)nchunks);
+    unsigned long long *d_h = dc.zeroed<unsigned long long>((size_t)nb);
     std::vector<unsigned long long> h((size_t)nb, 0);
-    hipError_t e = hipMemsetAsync(d_h, 0, (size_t)nb * sizeof(unsigned long long), c->stream);
-    natac_ctx::Ev ev;
-    prof_begin(c, NATAC_K_SIZE_HIST, ev);
-    if (e == hipSuccess && nf > 0 && nchunks > 0) {
+    if (dc.ok() && nf > 0 && nchunks > 0) {
+        dc.prof_begin(NATAC_K_SIZE_HIST);
         const long long nseg = (nf + SIZE_SEG - 1) / SIZE_SEG;
         const int blocks = (int)std::min<long long>(nseg, 8192);
         const int use_lds = nb <= 8192 ? 1 : 0;
         const size_t lds = (size_t)2 * SIZE_STAGE * sizeof(long long) + (use_lds ? (size_t)nb * sizeof(unsigned) : 0);
         hipLaunchKernelGGL(natac_size_hist, dim3(blocks), dim3(256), lds, c->stream, d_l, d_n, (long long)nf, d_cs, d_ce, (int)nchunks,
                            lower, upper, use_lds, d_h);
-        e = hipGetLastError();
+        dc.prof_end();
+        dc.launched();
     }
-    prof_end(c, ev);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_h, (size_t)nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "fragment_sizes: %s", hipGetErrorString(e));
-    prof_collect(c);
+    dc.fetch(h.data(), d_h, (size_t)nb);
+    const int rc = dc.finish();
+    if (rc) return rc;
     for (int i = 0; i < nb; ++i) sizes[i] = (double)h[i];
     return NATAC_OK;
 }
@@ -2363,24 +2386,21 @@ int natac_calculate_cov(natac_ctx *c, const double *p, const double *v, int64_t 
     if (!c || !p || !v || !out) return fail(NATAC_E_ARG, "null argument");
     if (n <= 0) return fail(NATAC_E_ARG, "p and v must be non-empty");
     if (mode != 0 && mode != 1) return fail(NATAC_E_ARG, "mode must be 0 (closed form) or 1 (literal)");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    double *d_p = nullptr, *d_v = nullptr, *d_part = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_p, p, (size_t)n)) || (rc = tmp.upload(&d_v, v, (size_t)n)))
-        return rc;
+    DeviceCall dc(c, "calculate_cov");
+    const double *d_p = dc.upload(p, (size_t)n), *d_v = dc.upload(v, (size_t)n);
     const int blocks = mode == 0 ? (int)std::min<int64_t>((n + 255) / 256, 1024) : (int)std::min<int64_t>(n, 4096);
-    if ((rc = tmp.alloc(&d_part, (size_t)2 * blocks))) return rc;
+    double *d_part = dc.alloc<double>((size_t)2 * blocks);
     std::vector<double> part((size_t)2 * blocks);
-    if (mode == 0)
-        hipLaunchKernelGGL(natac_cov_closed, dim3(blocks), dim3(256), 0, c->stream, d_p, d_v, (long long)n, d_part);
-    else
-        hipLaunchKernelGGL(natac_cov_literal, dim3(blocks), dim3(256), 0, c->stream, d_p, d_v, (long long)n, d_part);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, (size_t)(mode == 0 ? 2 : 1) * blocks * sizeof(double),
-                                            hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "calculate_cov: %s", hipGetErrorString(e));
+    if (dc.ok()) {
+        if (mode == 0)
+            hipLaunchKernelGGL(natac_cov_closed, dim3(blocks), dim3(256), 0, c->stream, d_p, d_v, (long long)n, d_part);
+        else
+            hipLaunchKernelGGL(natac_cov_literal, dim3(blocks), dim3(256), 0, c->stream, d_p, d_v, (long long)n, d_part);
+        dc.launched();
+    }
+    dc.fetch(part.data(), d_part, (size_t)(mode == 0 ? 2 : 1) * blocks);
+    const int rc = dc.finish();
+    if (rc) return rc;
     if (mode == 0) {
         double s1 = 0, s2 = 0;
         for (int i = 0; i < blocks; ++i) { s1 += part[2 * i]; s2 += part[2 * i + 1]; }
@@ -2401,19 +2421,16 @@ int natac_smooth(natac_ctx *c, const double *x, int64_t n, const double *w, int 
     if (mode != 0 && mode != 1) return fail(NATAC_E_ARG, "mode must be 0 (valid) or 1 (same)");
     if (n < M) return fail(NATAC_E_ARG, "signal (%lld) shorter than the window (%d)", (long long)n, M);
     const long long nout = mode == 0 ? n - M + 1 : n;
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    double *d_x = nullptr, *d_w = nullptr, *d_y = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_x, x, (size_t)n)) || (rc = tmp.upload(&d_w, w, (size_t)M)) || (rc = tmp.alloc(&d_y, (size_t)nout)))
-        return rc;
-    hipLaunchKernelGGL(natac_smooth1d, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_x, (long long)n, d_w, M, mode,
-                       norm, d_y, nout);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_y, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "smooth: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    DeviceCall dc(c, "smooth");
+    const double *d_x = dc.upload(x, (size_t)n), *d_w = dc.upload(w, (size_t)M);
+    double *d_y = dc.alloc<double>((size_t)nout);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_smooth1d, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_x, (long long)n, d_w, M, mode,
+                           norm, d_y, nout);
+        dc.launched();
+    }
+    dc.fetch(out, d_y, (size_t)nout);
+    return dc.finish();
 }
 
 int natac_make_bias_mat(natac_ctx *c, const double *bias_log, int64_t nb, int64_t track_start, int64_t start, int64_t end,
@@ -2422,23 +2439,19 @@ int natac_make_bias_mat(natac_ctx *c, const double *bias_log, int64_t nb, int64_
     if (end <= start || upper <= lower || lower < 0) return fail(NATAC_E_ARG, "empty matrix");
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    double *d_b = nullptr, *d_m = nullptr;
-    int *d_oob = nullptr, oob = 0;
-    int rc;
-    if ((rc = tmp.upload(&d_b, bias_log, (size_t)nb)) || (rc = tmp.alloc(&d_m, (size_t)(nrow * ncol))) || (rc = tmp.alloc(&d_oob, 1)))
-        return rc;
-    hipError_t e = hipMemsetAsync(d_oob, 0, sizeof(int), c->stream);
-    if (e == hipSuccess) {
+    DeviceCall dc(c, "make_bias_mat");
+    const double *d_b = dc.upload(bias_log, (size_t)nb);
+    double *d_m = dc.alloc<double>((size_t)(nrow * ncol));
+    int *d_oob = dc.zeroed<int>(1), oob = 0;
+    if (dc.ok()) {
         hipLaunchKernelGGL(natac_bias_mat_dense, dim3((unsigned)((nrow * ncol + 255) / 256)), dim3(256), 0, c->stream, d_b, (long long)nb,
                            (long long)(start - track_start), (int)ncol, lower, (int)nrow, d_m, d_oob);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(mat, d_m, (size_t)(nrow * ncol) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&oob, d_oob, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "make_bias_mat: %s", hipGetErrorString(e));
+    dc.fetch(mat, d_m, (size_t)(nrow * ncol));
+    dc.fetch(&oob, d_oob, 1);
+    const int rc = dc.finish();
+    if (rc) return rc;
     if (oob) return fail(NATAC_E_ARG, "bias track does not cover [start - upper//2, end + upper//2)");
     return NATAC_OK;
 }
@@ -2447,23 +2460,19 @@ int natac_pwm_bias(natac_ctx *c, const uint8_t *seq, int64_t n, const double *lo
                    double *out) {
     if (!c || !seq || !log_pwm || !nucleotides || !out) return fail(NATAC_E_ARG, "null argument");
     if (nrow < 1 || K < 1 || n < K) return fail(NATAC_E_ARG, "sequence shorter than the PWM");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    unsigned char *d_s = nullptr, *d_n = nullptr;
-    double *d_p = nullptr, *d_o = nullptr;
     const long long nout = n - K + 1;
-    int rc;
-    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)n)) ||
-        (rc = tmp.upload(&d_n, (const unsigned char *)nucleotides, (size_t)nrow)) || (rc = tmp.upload(&d_p, log_pwm, (size_t)nrow * K)) ||
-        (rc = tmp.alloc(&d_o, (size_t)nout)))
-        return rc;
-    hipLaunchKernelGGL(natac_pwm_score, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)n, d_p, d_n, nrow, K,
-                       d_o);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "pwm_bias: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    DeviceCall dc(c, "pwm_bias");
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)n);
+    const unsigned char *d_n = dc.upload((const unsigned char *)nucleotides, (size_t)nrow);
+    const double *d_p = dc.upload(log_pwm, (size_t)nrow * K);
+    double *d_o = dc.alloc<double>((size_t)nout);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_pwm_score, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)n, d_p, d_n, nrow, K,
+                           d_o);
+        dc.launched();
+    }
+    dc.fetch(out, d_o, (size_t)nout);
+    return dc.finish();
 }
 
 int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_len, const int64_t *frag_off, const int32_t *frag_lpos,
@@ -2494,45 +2503,26 @@ int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_le
     if (ns > 0 && !seq) return fail(NATAC_E_ARG, "null argument");
     if (nf >= (1LL << 40)) return fail(NATAC_E_ARG, "too many fragments in one call");
     if (nf == 0) return NATAC_OK;
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    int *d_len = nullptr, *d_l = nullptr, *d_n = nullptr;
-    long long *d_fo = nullptr, *d_so = nullptr;
-    unsigned char *d_s = nullptr;
-    unsigned long long *d_out = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_len, chunk_len, (size_t)nc)) || (rc = tmp.upload(&d_fo, (const long long *)frag_off, (size_t)nc + 1)) ||
-        (rc = tmp.upload(&d_so, (const long long *)seq_off, (size_t)nc + 1)) || (rc = tmp.upload(&d_l, frag_lpos, (size_t)nf)) ||
-        (rc = tmp.upload(&d_n, frag_ilen, (size_t)nf)) || (rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)ns)) ||
-        (rc = tmp.alloc(&d_out, (size_t)4 * K + 1)))
-        return rc;
+    DeviceCall dc(c, "insertion_seq_counts");
+    const int *d_len = dc.upload(chunk_len, (size_t)nc);
+    const long long *d_fo = dc.upload((const long long *)frag_off, (size_t)nc + 1), *d_so = dc.upload((const long long *)seq_off, (size_t)nc + 1);
+    const int *d_l = dc.upload(frag_lpos, (size_t)nf), *d_n = dc.upload(frag_ilen, (size_t)nf);
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)ns);
     std::vector<unsigned long long> h((size_t)4 * K + 1);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMemsetAsync(d_out, 0, h.size() * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess && kernel_ms) {
-        e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipEventRecord(e0, c->stream);
-    }
-    if (e == hipSuccess) {
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(h.size());
+    dc.time_begin(kernel_ms);
+    if (dc.ok()) {
         const int CW = K < 64 ? K : 64;
         const long long nseg = (nf + PF_SEG - 1) / PF_SEG;
         const int bx = (int)std::min<long long>((nseg + PF_BLOCK / 64 - 1) / (PF_BLOCK / 64), 2048);
         hipLaunchKernelGGL(natac_ins_seq_counts, dim3(bx, (K + CW - 1) / CW), dim3(PF_BLOCK), 0, c->stream, d_fo, d_l, d_n, nf, (int)nc,
                            d_len, d_so, d_s, flank, lower, upper, sym ? 1 : 0, d_out, d_out + 4 * K);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess && kernel_ms) e = hipEventRecord(e1, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && kernel_ms) {
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, e0, e1);
-        *kernel_ms = ms;
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "insertion_seq_counts: %s", hipGetErrorString(e));
+    dc.time_end();
+    dc.fetch(h.data(), d_out, h.size());
+    const int rc = dc.finish();
+    if (rc) return rc;
     for (int i = 0; i < 4 * K; ++i) counts[i] = (int64_t)h[i];
     *n_ins = (int64_t)h[4 * K];
     return NATAC_OK;
@@ -2555,53 +2545,21 @@ int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, c
     // lane counters are 32-bit: a block adds at most ceil(total / blocks) bases
     const long long bx = std::min<long long>((total + PF_SPAN - 1) / PF_SPAN, 8192);
     if ((total + bx - 1) / bx >= (1LL << 31)) return fail(NATAC_E_ARG, "ranges too long for one call");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    unsigned char *d_s = nullptr;
-    long long *d_st = nullptr, *d_cum = nullptr;
-    unsigned long long *d_out = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_s, (const unsigned char *)seq, (size_t)n)) || (rc = tmp.upload(&d_st, (const long long *)start, (size_t)nr)) ||
-        (rc = tmp.upload(&d_cum, cum.data(), cum.size())) || (rc = tmp.alloc(&d_out, 4)))
-        return rc;
+    DeviceCall dc(c, "base_counts");
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)n);
+    const long long *d_st = dc.upload((const long long *)start, (size_t)nr), *d_cum = dc.upload(cum.data(), cum.size());
     unsigned long long h[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemsetAsync(d_out, 0, sizeof h, c->stream);
-    if (e == hipSuccess) {
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(4);
+    if (dc.ok()) {
         hipLaunchKernelGGL(natac_base_count, dim3((unsigned)bx), dim3(PF_BLOCK), 0, c->stream, d_s, (int)nr, d_st, d_cum, d_out);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "base_counts: %s", hipGetErrorString(e));
+    dc.fetch(h, d_out, 4);
+    const int rc = dc.finish();
+    if (rc) return rc;
     for (int i = 0; i < 4; ++i) counts[i] = (int64_t)h[i];
     return NATAC_OK;
 }
-
-// device events around the counting kernels of a call (kernel_ms of natac_region_counts / natac_site_seq_counts)
-struct KernelTimer {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool on;
-    explicit KernelTimer(bool enabled) : on(enabled) {}
-    ~KernelTimer() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    hipError_t start(hipStream_t s) {
-        if (!on) return hipSuccess;
-        hipError_t e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e == hipSuccess) e = hipEventRecord(e0, s);
-        return e;
-    }
-    hipError_t stop(hipStream_t s) { return on ? hipEventRecord(e1, s) : hipSuccess; }
-    hipError_t read(double *ms) {       // after the stream has been synchronised
-        if (!on) return hipSuccess;
-        float f = 0;
-        hipError_t e = hipEventElapsedTime(&f, e0, e1);
-        *ms = f;
-        return e;
-    }
-};
 
 int natac_region_counts(natac_ctx *c, int64_t nf, const int64_t *pos, const int64_t *tlen, int64_t nr, const int64_t *start,
                         const int64_t *end, int lower, int upper, int atac, int64_t *counts, double *kernel_ms) {
@@ -2625,45 +2583,35 @@ int natac_region_counts(natac_ctx *c, int64_t nf, const int64_t *pos, const int6
     }
     for (int64_t i = 0; i < nr; ++i) counts[i] = 0;
     if (nr == 0 || nf == 0) return NATAC_OK;
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    long long *d_pos = nullptr, *d_tlen = nullptr, *d_s = nullptr, *d_e = nullptr, *d_lo = nullptr, *d_n = nullptr, *d_long = nullptr;
-    unsigned long long *d_out = nullptr;      // counts[nr], then the number of long regions
-    int rc;
-    if ((rc = tmp.upload(&d_pos, (const long long *)pos, (size_t)nf)) || (rc = tmp.upload(&d_tlen, (const long long *)tlen, (size_t)nf)) ||
-        (rc = tmp.upload(&d_s, (const long long *)start, (size_t)nr)) || (rc = tmp.upload(&d_e, (const long long *)end, (size_t)nr)) ||
-        (rc = tmp.alloc(&d_lo, (size_t)nr)) || (rc = tmp.alloc(&d_n, (size_t)nr)) || (rc = tmp.alloc(&d_long, (size_t)nr)) ||
-        (rc = tmp.alloc(&d_out, (size_t)nr + 1)))
-        return rc;
+    DeviceCall dc(c, "region_counts");
+    const long long *d_pos = dc.upload((const long long *)pos, (size_t)nf), *d_tlen = dc.upload((const long long *)tlen, (size_t)nf);
+    const long long *d_s = dc.upload((const long long *)start, (size_t)nr), *d_e = dc.upload((const long long *)end, (size_t)nr);
+    long long *d_lo = dc.alloc<long long>((size_t)nr), *d_n = dc.alloc<long long>((size_t)nr), *d_long = dc.alloc<long long>((size_t)nr);
+    unsigned long long *d_out = dc.zeroed<unsigned long long>((size_t)nr + 1);      // counts[nr], then the number of long regions
     const int shift = atac ? 4 : 0, trim = atac ? 8 : 0;
-    KernelTimer timer(kernel_ms != nullptr);
-    hipError_t e = hipMemsetAsync(d_out, 0, ((size_t)nr + 1) * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = timer.start(c->stream);
-    if (e == hipSuccess) {
+    dc.time_begin(kernel_ms);
+    if (dc.ok()) {
         const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK - 1) / RC_BLOCK, 4096);
         hipLaunchKernelGGL(natac_region_ranges, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, (long long)nf, (long long)nr, d_s, d_e, lower,
                            upper, shift, d_lo, d_n, d_long, d_out + nr);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) {
+    if (dc.ok()) {
         const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK / 64 - 1) / (RC_BLOCK / 64), 8192);
         hipLaunchKernelGGL(natac_region_count_short, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, (long long)nr, d_s, d_e, d_lo,
                            d_n, lower, upper, shift, trim, d_out);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) {
+    if (dc.ok()) {
         // the number of long regions stays on the device: a fixed grid, idle when there is none
         const unsigned bx = (unsigned)std::min<long long>(nr, 128);
         hipLaunchKernelGGL(natac_region_count_long, dim3(bx, RC_LONG_Y), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, d_s, d_e, d_lo, d_n,
                            d_long, d_out + nr, lower, upper, shift, trim, d_out);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = timer.stop(c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_out, (size_t)nr * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = timer.read(kernel_ms);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "region_counts: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    dc.time_end();
+    dc.fetch(counts, d_out, (size_t)nr);
+    return dc.finish();
 }
 
 int natac_site_seq_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int64_t ns, const int64_t *center, const uint8_t *minus, int up,
@@ -2685,31 +2633,24 @@ int natac_site_seq_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int64_t n
     for (long long i = 0; i < (long long)R * K; ++i) counts[i] = 0;
     *n_used = 0;
     if (ns == 0) return NATAC_OK;
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    unsigned char *d_seq = nullptr, *d_m = nullptr;
-    long long *d_c = nullptr;
-    unsigned long long *d_out = nullptr;      // counts[R x K], then n_used
-    const size_t nout = (size_t)R * K + 1;
-    int rc;
-    if ((rc = tmp.upload(&d_seq, (const unsigned char *)seq, (size_t)n)) || (rc = tmp.upload(&d_c, (const long long *)center, (size_t)ns)) ||
-        (minus && (rc = tmp.upload(&d_m, (const unsigned char *)minus, (size_t)ns))) || (rc = tmp.alloc(&d_out, nout)))
-        return rc;
+    DeviceCall dc(c, "site_seq_counts");
+    const size_t nout = (size_t)R * K + 1;      // counts[R x K], then n_used
+    const unsigned char *d_seq = dc.upload((const unsigned char *)seq, (size_t)n);
+    const long long *d_c = dc.upload((const long long *)center, (size_t)ns);
+    const unsigned char *d_m = minus ? dc.upload((const unsigned char *)minus, (size_t)ns) : nullptr;
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(nout);
     std::vector<unsigned long long> h(nout);
-    KernelTimer timer(kernel_ms != nullptr);
-    hipError_t e = hipMemsetAsync(d_out, 0, nout * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) e = timer.start(c->stream);
-    if (e == hipSuccess) {
+    dc.time_begin(kernel_ms);
+    if (dc.ok()) {
         const unsigned bx = (unsigned)std::min<long long>((ns + SS_SEG - 1) / SS_SEG, 1024);
         hipLaunchKernelGGL(natac_site_seq_count, dim3(bx, (unsigned)((K + SS_TILE - 1) / SS_TILE)), dim3(SS_BLOCK), 0, c->stream, d_seq,
                            (long long)n, (long long)ns, d_c, d_m, up, down, word, d_out, d_out + (nout - 1));
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = timer.stop(c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_out, nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = timer.read(kernel_ms);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "site_seq_counts: %s", hipGetErrorString(e));
+    dc.time_end();
+    dc.fetch(h.data(), d_out, nout);
+    const int rc = dc.finish();
+    if (rc) return rc;
     for (size_t i = 0; i + 1 < nout; ++i) counts[i] = (int64_t)h[i];
     *n_used = (int64_t)h[nout - 1];
     return NATAC_OK;
@@ -2719,39 +2660,33 @@ int natac_correlate_valid(natac_ctx *c, const double *sub, int64_t ncol, const d
     if (!c || !sub || !vmat || !out) return fail(NATAC_E_ARG, "null argument");
     if (R < 1 || W < 1 || ncol < W) return fail(NATAC_E_ARG, "matrix narrower than the template");
     const long long nout = ncol - W + 1;
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    double *d_s = nullptr, *d_v = nullptr, *d_o = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_s, sub, (size_t)R * ncol)) || (rc = tmp.upload(&d_v, vmat, (size_t)R * W)) ||
-        (rc = tmp.alloc(&d_o, (size_t)nout)))
-        return rc;
-    hipLaunchKernelGGL(natac_correlate_dense, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)ncol, d_v, R, W,
-                       d_o, nout);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "correlate_valid: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    DeviceCall dc(c, "correlate_valid");
+    const double *d_s = dc.upload(sub, (size_t)R * ncol), *d_v = dc.upload(vmat, (size_t)R * W);
+    double *d_o = dc.alloc<double>((size_t)nout);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_correlate_dense, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, c->stream, d_s, (long long)ncol, d_v, R, W,
+                           d_o, nout);
+        dc.launched();
+    }
+    dc.fetch(out, d_o, (size_t)nout);
+    return dc.finish();
 }
 
 int natac_calculate_occupancy(natac_ctx *c, const double *inserts, const double *bias, double *out) {
     if (!c || !inserts || !bias || !out) return fail(NATAC_E_ARG, "null argument");
     if (!c->have_occ) return fail(NATAC_E_STATE, "natac_set_occ_model has not been called");
-    HIPCHK(hipSetDevice(c->device));
-    StreamTemps tmp(c);
-    double *d_i = nullptr, *d_b = nullptr, *d_o = nullptr;
-    int *d_s = nullptr, st = 0;
-    int rc;
-    if ((rc = tmp.upload(&d_i, inserts, (size_t)c->occ_upper)) || (rc = tmp.upload(&d_b, bias, (size_t)c->occ_upper)) ||
-        (rc = tmp.alloc(&d_o, 3)) || (rc = tmp.alloc(&d_s, 1)))
-        return rc;
-    hipLaunchKernelGGL(natac_occupancy_single, dim3(1), dim3(128), 0, c->stream, d_i, d_b, make_occ(c), d_o, d_s);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&st, d_s, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "calculate_occupancy: %s", hipGetErrorString(e));
+    DeviceCall dc(c, "calculate_occupancy");
+    const double *d_i = dc.upload(inserts, (size_t)c->occ_upper), *d_b = dc.upload(bias, (size_t)c->occ_upper);
+    double *d_o = dc.alloc<double>(3);
+    int *d_s = dc.alloc<int>(1), st = 0;
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_occupancy_single, dim3(1), dim3(128), 0, c->stream, d_i, d_b, make_occ(c), d_o, d_s);
+        dc.launched();
+    }
+    dc.fetch(out, d_o, 3);
+    dc.fetch(&st, d_s, 1);
+    const int rc = dc.finish();
+    if (rc) return rc;
     if (st) return fail(NATAC_E_ARG, "no alpha passes the likelihood-ratio test");
     return NATAC_OK;
 }
@@ -2772,14 +2707,15 @@ int natac_batch_format_track(natac_batch *b, int track, const int32_t *chrom_id,
     if (track != NATAC_T_INS)
         return format_values(b, b->d_track[track], chrom_id, names, n_names, chunk_start, write_zero, compress, n_bytes, n_text_bytes, n_lines,
                              n_hard);
-    StreamTemps tmp(c);
-    double *d_tmp = nullptr;                   // insertion counts are int32 on the device; the writer takes float64 like the reference's track
-    if ((rc = tmp.alloc(&d_tmp, (size_t)b->total_bp))) return rc;
+    DeviceCall dc(c, "format_track");
+    double *d_tmp = dc.alloc<double>((size_t)b->total_bp);   // insertion counts are int32 on the device; the writer takes float64 like the reference's track
+    if (!dc.ok()) return dc.finish();
     const int blocks = (int)std::min<long long>((b->total_bp + 255) / 256, 65536);
     hipLaunchKernelGGL(natac_i32_to_f64, dim3(blocks), dim3(256), 0, c->stream, (const int *)b->d_track[NATAC_T_INS].get(), d_tmp, b->total_bp);
+    dc.launched();
     rc = format_values(b, d_tmp, chrom_id, names, n_names, chunk_start, write_zero, compress, n_bytes, n_text_bytes, n_lines, n_hard);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
+    const int rc_end = dc.finish();
+    return rc ? rc : rc_end;
 }
 
 // results handed to natac_batch_format_fetch_begin: wait for their copies, give the device buffers back
@@ -2908,25 +2844,24 @@ int natac_tbi_write(natac_tbi *t, const char *tbi_path, int64_t *n_records) {
 int natac_format_doubles(natac_ctx *c, const double *vals, int64_t n, char *out, size_t out_cap, int64_t *out_off, int32_t *n_hard) {
     if (!c || !vals || !out || !out_off || n <= 0) return fail(NATAC_E_ARG, "bad argument");
     if (out_cap < (size_t)n * natac_text::MAX_VALUE_CHARS) return fail(NATAC_E_ARG, "out must hold %d bytes per value", natac_text::MAX_VALUE_CHARS);
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "format_doubles");
+    if (!dc.ok()) return dc.finish();
     int rc = ensure_text_tables(c);
     if (rc) return rc;
     std::vector<int> len((size_t)n + 1);
     std::vector<char> raw((size_t)n * natac_text::MAX_VALUE_CHARS);
-    StreamTemps tmp(c);
-    double *d_v = nullptr;
-    char *d_o = nullptr;
-    int *d_len = nullptr, *d_hard = nullptr;
-    if ((rc = tmp.upload(&d_v, vals, (size_t)n)) || (rc = tmp.alloc(&d_o, (size_t)n * natac_text::MAX_VALUE_CHARS)) ||
-        (rc = tmp.alloc(&d_len, (size_t)n + 1)))
-        return rc;
-    HIPCHK(hipMemsetAsync(d_len + n, 0, sizeof(int), c->stream));
-    d_hard = d_len + n;
-    hipLaunchKernelGGL(natac_textz::tz_format_values, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_v, (long long)n, c->d_p10, d_o,
-                       d_len, d_hard);
-    HIPCHK(hipMemcpyAsync(len.data(), d_len, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(raw.data(), d_o, raw.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const double *d_v = dc.upload(vals, (size_t)n);
+    char *d_o = dc.alloc<char>(raw.size());
+    int *d_len = dc.alloc<int>((size_t)n + 1), *d_hard = d_len + n;      // the lengths, then the count of undecidable values
+    dc.zero(d_hard, 1);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_textz::tz_format_values, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_v, (long long)n, c->d_p10, d_o,
+                           d_len, d_hard);
+        dc.launched();
+    }
+    dc.fetch(len.data(), d_len, (size_t)n + 1);
+    dc.fetch(raw.data(), d_o, raw.size());
+    if ((rc = dc.finish())) return rc;
     long long o = 0;
     for (int64_t i = 0; i < n; ++i) {
         out_off[i] = o;
@@ -3455,33 +3390,30 @@ int natac_store_adopt(natac_store *s, natac_batch *b, int32_t n_tracks, const in
     PoolBuf<unsigned int> d_R;
     PoolBuf<int> d_C;
     int hard = 0;
-    StreamTemps tmp(c);
-    int *d_tc = nullptr, *d_hard = nullptr;
-    unsigned long long *d_tb = nullptr;
+    DeviceCall dc(c, "store_adopt");
     const int nt = b->n_tiles256;
-    if ((rc = tmp.alloc(&d_hard, 1)) || (rc = tmp.alloc(&d_tc, (size_t)nt)) || (rc = tmp.alloc(&d_tb, (size_t)nt + 1))) return rc;
-    hipError_t e = hipMemsetAsync(d_hard, 0, sizeof(int), c->stream);
-    for (int i = 0; i < n_tracks && e == hipSuccess; ++i) {
+    int *d_hard = dc.zeroed<int>(1), *d_tc = dc.alloc<int>((size_t)nt);
+    unsigned long long *d_tb = dc.alloc<unsigned long long>((size_t)nt + 1);
+    for (int i = 0; i < n_tracks && dc.ok(); ++i) {
         TextJob job;
         job.vals = b->d_track[tracks[i]]; job.out_off = b->d_out_off; job.chunk_len = b->d_len; job.tiles = b->d_tiles256; job.ntiles = nt;
         job.chrom_id = nullptr; job.chunk_start = nullptr; job.names = nullptr; job.name_off = nullptr; job.p10 = c->d_p10;
         job.write_zero = write_zero & 1; job.keep_before_nan = (write_zero >> 1) & 1;
         hipLaunchKernelGGL(tz_flags_count, dim3(nt), dim3(256), 0, c->stream, job, d_tc);
-        if ((rc = dev_scan(c, d_tc, (long long)nt, d_tb, tmp))) return rc;
+        dev_scan(c, d_tc, (long long)nt, d_tb, dc);
         unsigned long long nruns = 0;
-        if ((e = hipMemcpyAsync(&nruns, d_tb + nt, sizeof nruns, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
-        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) break;
+        dc.fetch(&nruns, d_tb + nt, 1);
+        if ((rc = dc.sync())) return rc;
         d_R.reset(); d_C.reset();
         if ((rc = dev_alloc(d_R, (size_t)nruns)) || (rc = dev_alloc(d_C, (size_t)nruns))) return rc;
         hipLaunchKernelGGL(tz_scatter_runs, dim3(nt), dim3(256), 0, c->stream, job, d_tb, d_R, d_C);
         if ((rc = dev_alloc(seg.p[i], (size_t)b->total_bp))) return rc;
         hipLaunchKernelGGL(tz_as_written, dim3((unsigned)((nruns + 255) / 256)), dim3(256), 0, c->stream, job, (long long)nruns, d_R, d_C,
                            seg.p[i], d_hard);
-        e = hipGetLastError();
+        dc.launched();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&hard, d_hard, sizeof hard, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "store_adopt: %s", hipGetErrorString(e));
+    dc.fetch(&hard, d_hard, 1);
+    if ((rc = dc.finish())) return rc;
     if (n_hard) *n_hard = hard;
     // a value the device cannot round like the text round trip would: nothing is adopted (the tracks go back), the caller reads the file
     if (hard) return NATAC_OK;
@@ -3497,7 +3429,8 @@ int natac_store_read(natac_store *s, natac_ctx *c, int64_t n, const int64_t *seg
     using namespace natac_textz;
     if (!s || !c || n < 0 || (n > 0 && (!segment || !offset || !length || !out))) return fail(NATAC_E_ARG, "null argument");
     if (n == 0) return NATAC_OK;
-    HIPCHK(hipSetDevice(c->device));
+    DeviceCall dc(c, "store_read");
+    if (!dc.ok()) return dc.finish();
     std::vector<StoreRegion> reg((size_t)n);
     long long total = 0;
     {
@@ -3515,17 +3448,14 @@ int natac_store_read(natac_store *s, natac_ctx *c, int64_t n, const int64_t *seg
     }
     if ((size_t)total != out_values) return fail(NATAC_E_ARG, "destination holds %zu values, the regions %lld", out_values, total);
     if (total == 0) return NATAC_OK;
-    StreamTemps tmp(c);
-    StoreRegion *d_reg = nullptr;
-    double *d_out = nullptr;
-    int rc;
-    if ((rc = tmp.upload(&d_reg, reg.data(), reg.size())) || (rc = tmp.alloc(&d_out, (size_t)total))) return rc;
-    hipLaunchKernelGGL(tz_store_gather, dim3((unsigned)n), dim3(256), 0, c->stream, d_reg, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(NATAC_E_HIP, "store_read: %s", hipGetErrorString(e));
-    return NATAC_OK;
+    const StoreRegion *d_reg = dc.upload(reg.data(), reg.size());
+    double *d_out = dc.alloc<double>((size_t)total);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(tz_store_gather, dim3((unsigned)n), dim3(256), 0, c->stream, d_reg, d_out);
+        dc.launched();
+    }
+    dc.fetch(out, d_out, (size_t)total);
+    return dc.finish();
 }
 
 int natac_store_info(natac_store *s, int64_t *n_segments, int64_t *bytes) {
