@@ -1,6 +1,7 @@
 """CPU: the host restatement of the device BGZF encoder (natac_bgzf_lines_host, csrc/natac_deflate.hpp) -- the kernels must
 produce exactly its bytes (tests/test_gpu_textz.py), so here it is pinned against zlib's inflate: every member it emits must
-decompress to the text, for float tracks, integer tracks, long names, single lines, members that fall back to `stored`."""
+decompress to the text, for float tracks, integer tracks, long names, single lines, members that fall back to `stored` -- among
+them the crafted track text (tests/writer_cases.py) that takes the DEVICE encoder into its stored arm in tests/test_gpu_writer_edges.py."""
 import gzip
 import io
 import zlib
@@ -73,3 +74,35 @@ def test_edge_cases():
     z = bgzf_lines_host(noise)
     assert _inflate(z) == noise
     assert bgzf_lines_host(b"") == b""
+
+
+def test_crafted_track_text_reaches_the_stored_arm(tmp_path):
+    """writer_cases.stored_member_case written by the native host writer: from 64 members on the Huffman code comes from members 0, 8,
+    16, ...; the members between them are full of characters those never show, so their payload passes 64 KiB.  Shown here
+    without a device: this input takes the encoder into its stored arm (63 of 73 members; with the tabix-indexable layout
+    exactly the members the builder fills that way), and every member, stored or dynamic, inflates to its slice of the text."""
+    import struct
+    import writer_cases as W
+    from nucleoatac_amd.writer import write_bedgraph
+    for indexable in (False, True):
+        pk, chroms, v = W.stored_member_case(indexable=indexable)
+        path = str(tmp_path / "crafted.bedgraph")
+        write_bedgraph(path, chroms, pk.chunk_start, pk.out_off, v, compress=0)
+        text = open(path, "rb").read()
+        z = bgzf_lines_host(text)
+        ms = W.members(z)
+        assert len(ms) == (len(text) + W.BLK - 1) // W.BLK >= 72
+        stored = dynamic = 0
+        for i, (o, size, first, crc, isz) in enumerate(ms):
+            part = text[i * W.BLK:(i + 1) * W.BLK]
+            assert zlib.decompress(z[o + 18:o + size - 8], -15) == part and isz == len(part) and crc == zlib.crc32(part), i
+            if first == 0x01:                                  # BFINAL = 1, BTYPE = 00
+                assert size == 18 + 5 + isz + 8 and struct.unpack_from("<HH", z, o + 19) == (isz, isz ^ 0xffff)
+                assert i % 8 != 0 and (not indexable or i in W.INDEXABLE_ODD)
+                stored += 1
+            else:
+                assert first & 7 == 5                          # BFINAL = 1, BTYPE = 10
+                dynamic += 1
+        print("indexable=%s: %d members, %d stored, %d dynamic" % (indexable, len(ms), stored, dynamic))
+        assert (stored == len(W.INDEXABLE_ODD)) if indexable else (stored >= 40 and dynamic >= 8)
+        assert _inflate(z) == text
