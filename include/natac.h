@@ -18,6 +18,7 @@
  *   (5) `pyatac bias`'s Tn5 bias track (pyatac/make_bias_track.py, bias.py:85-92) -> natac_run_pwm_track
  *   (6) `pyatac counts`'s per-region fragment counts (pyatac/get_counts.py:30-45) -> natac_region_counts
  *       and `pyatac nucleotide`'s word counts around sites (pyatac/get_nucleotide.py:19-38) -> natac_site_seq_counts
+ *   (7) `pyatac signal`'s per-site rows and their aggregate (pyatac/signal_around_sites.py:24-74) -> natac_site_signal
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -45,8 +46,9 @@ extern "C" {
  * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
  * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
- * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`); the binding refuses another version */
-#define NATAC_ABI_VERSION 7
+ * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`);
+ * the binding refuses another version */
+#define NATAC_ABI_VERSION 8
 
 enum {
     NATAC_OK = 0,
@@ -308,6 +310,21 @@ int natac_region_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, con
  * int64, overwritten.  up, down in [0, 524288].  kernel_ms (may be NULL): device time of the counting kernel. */
 int natac_site_seq_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int64_t n_sites, const int64_t *center, const uint8_t *minus,
                           int up, int down, int word, int64_t *counts, int64_t *n_used, double *kernel_ms);
+/* sites per partial sum of natac_site_signal's aggregate: part of its documented summation order */
+#define NATAC_SIGNAL_SEG 64
+/* _signalHelper, pyatac/signal_around_sites.py:24-74, after the track has been read (pyatac/bedgraph.py:6-14): vals[n_vals] holds the
+ * per-base values the sites need, NaN where no record covers a base.  Site i has K columns; in genomic orientation they are lead[i]
+ * zeros, the len[i] values vals[src[i] ..], and zeros up to K (the reference pads a window clipped by a chromosome end with zeros,
+ * signal_around_sites.py:42-47); minus[i] != 0 reverses the row (minus == NULL: all plus).  Then, by flags: 1 (--exp) v = exp(v), so a
+ * padding zero becomes 1 and NaN stays; 2 (--positive) v < 0 becomes 0, NaN and -0.0 stay; 4 (--scale) NaN becomes 0 and the row is
+ * divided by S + (S == 0), S = the sum of its absolute values.  mat (may be NULL) [n_sites x K] gets the rows; agg[K], overwritten,
+ * their column sums with NaN as 0.  Both are deterministic: a column is added in site order from 0 over every segment of
+ * NATAC_SIGNAL_SEG consecutive sites, the segment sums are added in segment order from 0, and S is added in an order that depends on
+ * K alone; no floating-point atomics.  The operands are checked on the host (NATAC_E_ARG names the site): K in [1, 1048577],
+ * len, lead >= 0, lead + len <= K, 0 <= src, src + len <= n_vals.  n_sites == 0 gives zeros and launches nothing.  kernel_ms (may be
+ * NULL): device time of the kernels. */
+int natac_site_signal(natac_ctx *ctx, const double *vals, int64_t n_vals, int64_t n_sites, const int64_t *src, const int32_t *len,
+                      const int32_t *lead, const uint8_t *minus, int K, int flags, double *mat, double *agg, double *kernel_ms);
 /* signal.correlate(sub, vmat, mode='valid')[0] as used by SignalTrack.calculateSignal / BiasTrack
  * (nucleoatac/NucleosomeCalling.py:34-36, 60-63): sub[R x ncol], vmat[R x W] row-major, out[ncol-W+1]. */
 int natac_correlate_valid(natac_ctx *ctx, const double *sub, int64_t ncol, const double *vmat, int R, int W, double *out);

@@ -2656,6 +2656,65 @@ int natac_site_seq_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int64_t n
     return NATAC_OK;
 }
 
+int natac_site_signal(natac_ctx *c, const double *vals, int64_t n_vals, int64_t ns, const int64_t *src, const int32_t *len,
+                      const int32_t *lead, const uint8_t *minus, int K, int flags, double *mat, double *agg, double *kernel_ms) {
+    using namespace natac_sites;
+    static_assert(SG_SEG == NATAC_SIGNAL_SEG, "the segment length is part of the documented summation order");
+    if (!c || !agg) return fail(NATAC_E_ARG, "null argument");
+    if (n_vals < 0 || ns < 0) return fail(NATAC_E_ARG, "negative size");
+    if (K < 1 || K > 2 * SS_MAX_FLANK + 1) return fail(NATAC_E_ARG, "K must be in [1, %d] (got %d)", 2 * SS_MAX_FLANK + 1, K);
+    if (flags & ~(SG_EXP | SG_POSITIVE | SG_SCALE)) return fail(NATAC_E_ARG, "flags must be a sum of 1 (exp), 2 (positive), 4 (scale) (got %d)", flags);
+    if ((n_vals > 0 && !vals) || (ns > 0 && (!src || !len || !lead))) return fail(NATAC_E_ARG, "null argument");
+    if (ns >= (1LL << 40)) return fail(NATAC_E_ARG, "too many sites in one call");
+    if (kernel_ms) *kernel_ms = 0;
+    // the kernels trust their operands: every read is vals[src + r] with 0 <= r < len
+    for (int64_t i = 0; i < ns; ++i) {
+        if (len[i] < 0 || lead[i] < 0) return fail(NATAC_E_ARG, "site %lld: negative len (%d) or lead (%d)", (long long)i, len[i], lead[i]);
+        if ((int64_t)lead[i] + len[i] > K)
+            return fail(NATAC_E_ARG, "site %lld: lead %d + len %d exceed the %d columns", (long long)i, lead[i], len[i], K);
+        if (src[i] < 0 || src[i] > n_vals || len[i] > n_vals - src[i])
+            return fail(NATAC_E_ARG, "site %lld: values [%lld, %lld + %d) outside [0, %lld)", (long long)i, (long long)src[i], (long long)src[i],
+                        len[i], (long long)n_vals);
+    }
+    for (int j = 0; j < K; ++j) agg[j] = 0;
+    if (ns == 0) return NATAC_OK;
+    const long long nseg = (ns + SG_SEG - 1) / SG_SEG;
+    DeviceCall dc(c, "site_signal");
+    const double *d_v = dc.upload(vals, (size_t)n_vals);
+    const long long *d_src = dc.upload((const long long *)src, (size_t)ns);
+    const int *d_len = dc.upload(len, (size_t)ns), *d_lead = dc.upload(lead, (size_t)ns);
+    const unsigned char *d_m = minus ? dc.upload((const unsigned char *)minus, (size_t)ns) : nullptr;
+    double *d_div = (flags & SG_SCALE) ? dc.alloc<double>((size_t)ns) : nullptr;
+    double *d_mat = mat ? dc.alloc<double>((size_t)ns * K) : nullptr;
+    double *d_part = dc.alloc<double>((size_t)nseg * K), *d_agg = dc.alloc<double>((size_t)K);
+    dc.time_begin(kernel_ms);
+    if (dc.ok() && (flags & SG_SCALE)) {
+        int W = 1;                          // the kernel's group width: 64 / W sites per wave
+        while (W < K && W < 64) W <<= 1;
+        const long long per_block = (SG_BLOCK / 64) * (64 / W);
+        const unsigned bx = (unsigned)std::min<long long>((ns + per_block - 1) / per_block, 8192);
+        hipLaunchKernelGGL(natac_site_signal_div, dim3(bx), dim3(SG_BLOCK), 0, c->stream, d_v, (long long)ns, d_src, d_len, d_lead, d_m, K,
+                           flags, d_div);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        const int ng = SG_BLOCK / std::min(K, SG_TILE);      // segments per block in the widest tile
+        const unsigned bx = (unsigned)std::min<long long>((nseg + ng - 1) / ng, 65535);
+        hipLaunchKernelGGL(natac_site_signal_rows, dim3(bx, (unsigned)((K + SG_TILE - 1) / SG_TILE)), dim3(SG_BLOCK), 0, c->stream, d_v,
+                           (long long)ns, d_src, d_len, d_lead, d_m, K, flags, d_div, d_mat, d_part);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_site_signal_agg, dim3((unsigned)((K + SG_BLOCK - 1) / SG_BLOCK)), dim3(SG_BLOCK), 0, c->stream, d_part, nseg,
+                           K, d_agg);
+        dc.launched();
+    }
+    dc.time_end();
+    if (mat) dc.fetch(mat, d_mat, (size_t)ns * K);
+    dc.fetch(agg, d_agg, (size_t)K);
+    return dc.finish();
+}
+
 int natac_correlate_valid(natac_ctx *c, const double *sub, int64_t ncol, const double *vmat, int R, int W, double *out) {
     if (!c || !sub || !vmat || !out) return fail(NATAC_E_ARG, "null argument");
     if (R < 1 || W < 1 || ncol < W) return fail(NATAC_E_ARG, "matrix narrower than the template");

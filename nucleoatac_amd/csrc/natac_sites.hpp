@@ -1,11 +1,14 @@
-// natac_sites.hpp -- the counting kernels behind `pyatac counts` and `pyatac nucleotide` (pyatac/get_counts.py and
-// pyatac/get_nucleotide.py of the reference):
+// natac_sites.hpp -- the kernels behind `pyatac counts`, `pyatac nucleotide` and `pyatac signal` (pyatac/get_counts.py,
+// pyatac/get_nucleotide.py and pyatac/signal_around_sites.py of the reference):
 //   natac_region_ranges / natac_region_count_short / natac_region_count_long
 //                          fragments with an end inside each of a list of regions of one chromosome (get_counts.py:30-45)
 //   natac_site_seq_count   mono- or dinucleotide content of the window around every site of one chromosome (_nucleotideHelper,
 //                          get_nucleotide.py:19-38, with chunk.center / chunk.slop and seq.get_sequence / seq_to_mat)
+//   natac_site_signal_div / natac_site_signal_rows / natac_site_signal_agg
+//                          the track values of the window around every site, transformed per site, and their column sums
+//                          (_signalHelper, signal_around_sites.py:24-74)
 // Every count is an integer: lanes and waves add 32-bit partial counts, the results are 64-bit, and nothing depends on the order of
-// the records, the sites, the blocks or the waves.
+// the records, the sites, the blocks or the waves.  The signal sums are float64 and are added in one fixed order, without atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -200,6 +203,93 @@ __global__ void __launch_bounds__(SS_BLOCK) natac_site_seq_count(const unsigned 
         }
         __syncthreads();
     }
+}
+
+// ---- pyatac signal ---------------------------------------------------------------------------------------------------------------
+constexpr int SG_BLOCK = 256;           // 4 waves
+constexpr int SG_TILE = 256;            // columns per block (blockIdx.y = the column tile): one column per thread
+constexpr int SG_SEG = 64;              // consecutive sites whose column sums make one partial (NATAC_SIGNAL_SEG of natac.h): the
+                                        // order of every sum depends on this constant alone, never on the grid
+constexpr int SG_EXP = 1, SG_POSITIVE = 2, SG_SCALE = 4;
+
+// column `col` of site i before --scale (_signalHelper, pyatac/signal_around_sites.py:41-56): the row in genomic orientation is `lead`
+// zeros, the `len` values from vals[src], zeros up to K; a minus site reads it backwards.  --exp turns the padding into 1 and leaves
+// NaN; --positive replaces what compares below 0 (not NaN, not -0.0); under --scale NaN becomes 0 in the row itself.
+__device__ __forceinline__ double signal_value(const double *__restrict__ vals, long long src, int len, int lead, bool rev, int K,
+                                               int col, int flags) {
+    const int rel = (rev ? K - 1 - col : col) - lead;
+    double v = (rel >= 0 && rel < len) ? vals[src + rel] : 0.0;
+    if (flags & SG_EXP) v = exp(v);
+    if ((flags & SG_POSITIVE) && v < 0.0) v = 0.0;
+    if ((flags & SG_SCALE) && v != v) v = 0.0;
+    return v;
+}
+
+// --scale's divisor per site: div[i] = S + (S == 0), S = the sum of |row| (signal_around_sites.py:54-57).  A wave is NG groups of W
+// lanes (W = the power of two >= min(K, 64), NG = 64 / W), a group takes one site: lane c adds the columns c, c + W, c + 2W, ... in
+// that order, then the group's lanes are added by a butterfly over the lane distances W/2 .. 1.  The order depends on K alone.
+__global__ void __launch_bounds__(SG_BLOCK) natac_site_signal_div(const double *__restrict__ vals, long long ns,
+                                                                  const long long *__restrict__ src, const int *__restrict__ len,
+                                                                  const int *__restrict__ lead, const unsigned char *__restrict__ minus,
+                                                                  int K, int flags, double *__restrict__ div) {
+    int W = 1;
+    while (W < K && W < 64) W <<= 1;
+    const int NG = 64 / W;
+    const int lane = threadIdx.x & 63;
+    const int g = lane / W, c = lane - g * W;
+    const long long nwaves = (long long)gridDim.x * (SG_BLOCK / 64);
+    const long long wave = (long long)blockIdx.x * (SG_BLOCK / 64) + (threadIdx.x >> 6);
+    for (long long i0 = wave * NG; i0 < ns; i0 += nwaves * NG) {       // i0 is wave-uniform: every lane takes part in the butterfly
+        const long long i = i0 + g;
+        double s = 0.0;
+        if (i < ns) {
+            const long long so = src[i];
+            const int ln = len[i], ld = lead[i];
+            const bool rev = minus != nullptr && minus[i] != 0;
+            for (int col = c; col < K; col += W) s += fabs(signal_value(vals, so, ln, ld, rev, K, col, flags));
+        }
+        for (int d = W >> 1; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+        if (i < ns && c == 0) div[i] = s + (s == 0.0 ? 1.0 : 0.0);
+    }
+}
+
+// mat[i][col] (when mat != NULL) = the transformed row of site i, and part[seg][col] = the sum over the sites of segment seg, NaN as
+// 0, added in site order starting from 0.  Segment seg holds the sites [seg * SG_SEG, (seg + 1) * SG_SEG).  Lane layout: a block is NG
+// groups of CW threads (CW = the columns of its tile, at most SG_TILE; NG = SG_BLOCK / CW); a group takes one segment and its threads
+// run along the window, so every row is read and written at consecutive addresses and a column's sum stays in one register.
+__global__ void __launch_bounds__(SG_BLOCK) natac_site_signal_rows(const double *__restrict__ vals, long long ns,
+                                                                   const long long *__restrict__ src, const int *__restrict__ len,
+                                                                   const int *__restrict__ lead, const unsigned char *__restrict__ minus,
+                                                                   int K, int flags, const double *__restrict__ div,
+                                                                   double *__restrict__ mat, double *__restrict__ part) {
+    const int col0 = blockIdx.y * SG_TILE;
+    const int tw = K - col0 < SG_TILE ? K - col0 : SG_TILE;       // columns of this tile
+    const int NG = SG_BLOCK / tw;
+    const int g = threadIdx.x / tw, col = col0 + (threadIdx.x - g * tw);
+    if (g >= NG) return;
+    const long long nseg = (ns + SG_SEG - 1) / SG_SEG;
+    for (long long seg = (long long)blockIdx.x * NG + g; seg < nseg; seg += (long long)gridDim.x * NG) {
+        const long long i1 = (seg + 1) * SG_SEG < ns ? (seg + 1) * SG_SEG : ns;
+        double acc = 0.0;
+#pragma unroll 4
+        for (long long i = seg * SG_SEG; i < i1; ++i) {
+            double v = signal_value(vals, src[i], len[i], lead[i], minus != nullptr && minus[i] != 0, K, col, flags);
+            if (flags & SG_SCALE) v = v / div[i];
+            if (mat != nullptr) mat[i * K + col] = v;
+            acc += v != v ? 0.0 : v;
+        }
+        part[seg * K + col] = acc;
+    }
+}
+
+// agg[col] = part[0][col] + part[1][col] + ... in segment order, starting from 0
+__global__ void __launch_bounds__(SG_BLOCK) natac_site_signal_agg(const double *__restrict__ part, long long nseg, int K,
+                                                                  double *__restrict__ agg) {
+    const int col = blockIdx.x * SG_BLOCK + threadIdx.x;
+    if (col >= K) return;
+    double acc = 0.0;
+    for (long long seg = 0; seg < nseg; ++seg) acc += part[seg * K + col];
+    agg[col] = acc;
 }
 
 }  // namespace natac_sites

@@ -377,6 +377,29 @@ class Context(object):
                                                 int(up), int(down), int(word), _ptr(counts), C.byref(n), C.byref(ms)))
         return (counts, n.value, ms.value) if with_kernel_ms else (counts, n.value)
 
+    def site_signal(self, vals, src, length, lead, minus, K, exp=False, positive=False, scale=False, want_matrix=False, with_kernel_ms=False):
+        """rows and aggregate of `pyatac signal` (_signalHelper, pyatac/signal_around_sites.py:24-74): (agg float64[K], mat float64[n, K]
+        or None).  vals: the per-base track values the sites need, NaN where there is no record; site i is lead[i] zeros, the length[i]
+        values from vals[src[i]], zeros up to K, reversed where minus[i] (None: all plus); then exp, positive (negatives to 0) and scale
+        (NaN to 0, row / (sum |row| or 1)).  agg is the column sum with NaN as 0, added in the fixed order of natac.h (segments of
+        _lib.SIGNAL_SEG sites): two calls give the same bits.  with_kernel_ms: also return the kernels' device time."""
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        sr = np.ascontiguousarray(src, dtype=np.int64)
+        ln = np.ascontiguousarray(length, dtype=np.int32)
+        ld = np.ascontiguousarray(lead, dtype=np.int32)
+        mi = None if minus is None else np.ascontiguousarray(minus, dtype=np.uint8)
+        if v.ndim != 1 or sr.ndim != 1 or ln.shape != sr.shape or ld.shape != sr.shape or (mi is not None and mi.shape != sr.shape):
+            raise ValueError("vals and src must be 1-d; length, lead and minus as long as src")
+        K = int(K)
+        agg = np.zeros(max(K, 1), dtype=np.float64)
+        mat = np.empty((sr.shape[0], max(K, 1)), dtype=np.float64) if want_matrix else None
+        ms = C.c_double(0)
+        flags = (1 if exp else 0) | (2 if positive else 0) | (4 if scale else 0)
+        L.check(self._lib.natac_site_signal(self._h, _ptr(v), v.shape[0], sr.shape[0], _ptr(sr), _ptr(ln), _ptr(ld),
+                                            None if mi is None else _ptr(mi), K, flags, None if mat is None else _ptr(mat), _ptr(agg),
+                                            C.byref(ms)))
+        return (agg, mat, ms.value) if with_kernel_ms else (agg, mat)
+
     def correlate_valid(self, sub, vmat):
         """signal.correlate(sub, vmat, mode='valid')[0] (nucleoatac/NucleosomeCalling.py:34-36)."""
         sub, vmat = _f64(sub), _f64(vmat)

@@ -1,8 +1,9 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide` command line with the reference's flag names and defaults
-(pyatac/cli.py:90-193, 310-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal` command line with the reference's flag names and defaults
+(pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
-`counts` gives the fragment count of every BED window and `nucleotide` the mono- or dinucleotide frequency around a set of sites
-(for one, the nucpos.bed.gz of `nucleoatac nuc`).  The other pyatac tools (signal, vplot, bias_vplot) are not part of this package."""
+`counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
+(for one, the nucpos.bed.gz of `nucleoatac nuc`) and `signal` the values of an indexed bedGraph track (any of the tracks written here)
+around such sites, per site and summed.  The other pyatac tools (vplot, bias_vplot) are not part of this package."""
 import argparse
 import sys
 
@@ -93,11 +94,31 @@ def add_nucleotide_parser(sub):
     p.add_argument("--norm", action="store_true", default=False, help="Normalize by background frequencies")
 
 
+def add_signal_parser(sub):
+    p = sub.add_parser("signal", help="pyatac function-- get signal around sites")
+    p.add_argument("--bed", metavar="bed_file", required=True, help="Positions around which to get the signal")
+    p.add_argument("--bg", metavar="bg_file", required=True, help="Accepts bedgraph file that is tabix indexed")
+    p.add_argument("--sizes", metavar="genome_sizes_file", required=True, help="File with chromosome names in 1st col, sizes in 2nd")
+    p.add_argument("--out", metavar="basename", help="basename for output")
+    p.add_argument("--cores", metavar="int", type=int, default=1, help="accepted for compatibility; the GPU replaces the pool")
+    p.add_argument("--all", action="store_true", default=False, help="output csv file (gzipped) with signal track around all sites")
+    p.add_argument("--no_agg", action="store_true", default=False, help="Don't write the aggregate")
+    p.add_argument("--up", metavar="int", type=int, default=250, help="bases upstream of site to look")
+    p.add_argument("--down", metavar="int", type=int, default=250, help="bases downstream of site to look")
+    p.add_argument("--weight", metavar="int", type=int, default=None, help="accepted for compatibility; ignored, like the reference")
+    p.add_argument("--strand", metavar="int", type=int, default=None,
+                   help="Column in which strand information is included if strand is to be used")
+    p.add_argument("--exp", action="store_true", default=False, help="take exponent of value")
+    p.add_argument("--positive", action="store_true", default=False, help="Only include positive signal")
+    p.add_argument("--scale", action="store_true", default=False, help="scale each individual track by total signal value")
+    p.add_argument("--norm", action="store_true", default=False, help="normalize aggregate track by number of intervals")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
-                                                                "insertion, coverage and Tn5 bias tracks, fragment counts per window "
-                                                                "and nucleotide content around sites")
+                                                                "insertion, coverage and Tn5 bias tracks, fragment counts per window, "
+                                                                "nucleotide content and track signal around sites")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -108,6 +129,7 @@ def pyatac_parser():
     add_bias_parser(sub)
     add_counts_parser(sub)
     add_nucleotide_parser(sub)
+    add_signal_parser(sub)
     return parser
 
 
@@ -163,6 +185,16 @@ def pyatac_main(args):
             get_nucleotide(args)
         except (NucleotideError, BedColumnError) as e:
             sys.stderr.write("pyatac nucleotide: %s\n" % e)
+            return 1
+    elif args.call == "signal":
+        from .chunk import BedColumnError
+        from .signal_around_sites import SignalError, get_signal
+        print("---------Getting signal around sites---------------------------------------")
+        print("plots are not produced: only the .agg.track.txt and .tracks.txt.gz files are written")
+        try:
+            get_signal(args)
+        except (SignalError, BedColumnError) as e:
+            sys.stderr.write("pyatac signal: %s\n" % e)
             return 1
     return 0
 

@@ -1,6 +1,6 @@
-"""Wall time by phase of `pyatac counts` and `pyatac nucleotide` (nucleoatac_amd/pyatac/get_counts.py, get_nucleotide.py) end to end on a
-synthetic workload, kernel milliseconds against wall time, and the NumPy restatement of tests/sites_ref.py on the same inputs as the
-point of comparison.  Prints one JSON line per tool.
+"""Wall time by phase of `pyatac counts`, `pyatac nucleotide` and `pyatac signal` (nucleoatac_amd/pyatac/get_counts.py, get_nucleotide.py,
+signal_around_sites.py) end to end on a synthetic workload, kernel milliseconds against wall time, and the NumPy restatement of
+tests/sites_ref.py / tests/signal_ref.py on the same inputs as the point of comparison.  Prints one JSON line per tool.
 
 The workload: a fragment store at the density of the configs[2] benchmark (50 M fragments over --refs x --ref-len bases, 500 per
 2,120 bases), registered in memory (the BAM decode is tools/bench_bam.py's number); --windows windows of 500 bases for `counts`; a
@@ -13,8 +13,15 @@ random genome of the same size, saved as a FastaStore .npz, and --sites sites wi
                            text_s     formatting and gzip of the .counts.txt.gz (host)
                            wall_s     the command end to end; numpy_s the restatement's counting alone (no BED, no text)
   tool = bench_nucleotide  bed_s, fasta_s (the .npz load), device_s, kernel_ms, text_s, wall_s and numpy_s likewise, for word = 1 and 2
-usage: python tools/bench_sites.py [--fragments 50000000] [--windows 1000000] [--sites 1000000] [--refs 4] [--ref-len 53000000]
-                                   [--no-numpy] [--out DIR]"""
+  tool = bench_signal      (mode `signal`) `pyatac signal` on a synthetic bedGraph of --refs x --signal-ref-len bases in records of
+                           1 to 19 bases with holes, bgzipped and indexed by the package's writers, and --signal-sites stranded sites
+                           at +-250: bed_s, read_s (span merging and natac_tbx_read_regions), device_s (the natac_site_signal calls:
+                           upload, kernels, download), kernel_ms, text_s and wall_s of get_signal without --all, for no transform and
+                           for --exp --positive --scale; kernel_ms_matrix, the kernels of one natac_site_signal call over all sites
+                           with the matrix written; floor_ms, n x K x 8 bytes read (and written, with the matrix) at 8 TB/s;
+                           numpy_s, the restatement of tests/signal_ref.py on the same value buffer (rows and aggregate, no read)
+usage: python tools/bench_sites.py [sites|signal] [--fragments 50000000] [--windows 1000000] [--sites 1000000] [--refs 4]
+                                   [--ref-len 53000000] [--signal-sites 100000] [--signal-ref-len 2500000] [--no-numpy] [--out DIR]"""
 import argparse
 import json
 import os
@@ -29,8 +36,89 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def bench_signal(a):
+    import signal_ref as R
+    from nucleoatac_amd import get_context
+    from nucleoatac_amd.pyatac.chunk import read_bed_columns
+    from nucleoatac_amd.pyatac.signal_around_sites import get_signal, merge_spans, site_windows
+    from nucleoatac_amd.tabix import NativeTabix
+    from nucleoatac_amd.writer import bgzip_file, tabix_index
+    d = a.out or tempfile.mkdtemp(prefix="bench_signal_")
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(2)
+    names = ["chr%d" % (r + 1) for r in range(a.refs)]
+    L, K = a.signal_ref_len, 501
+    t0 = time.perf_counter()
+    plain = os.path.join(d, "track.bedgraph")
+    n_records = 0
+    with open(plain, "w") as f:
+        for c in names:
+            edges = np.cumsum(rng.integers(1, 20, size=L // 9))
+            edges = edges[edges < L]
+            b, e = edges[:-1], edges[1:]
+            keep = rng.random(len(b)) > 0.03                        # holes: NaN
+            v = np.round(rng.normal(0.2, 1.0, len(b)), 4)
+            f.write("".join("%s\t%d\t%d\t%s\n" % (c, x, y, repr(z)) for x, y, z in zip(b[keep].tolist(), e[keep].tolist(), v[keep].tolist())))
+            n_records += int(keep.sum())
+    bg = bgzip_file(plain)
+    tabix_index(bg)
+    sizes = os.path.join(d, "genome.sizes")
+    with open(sizes, "w") as f:
+        f.write("".join("%s\t%d\n" % (c, L) for c in names))
+    sites = os.path.join(d, "signal_sites.bed")
+    with open(sites, "w") as f:
+        c = rng.integers(0, a.refs, size=a.signal_sites)
+        s = rng.integers(0, L - 147, size=a.signal_sites)
+        m = rng.random(a.signal_sites) < 0.5
+        f.write("".join("%s\t%d\t%d\tn\t0\t%s\n" % (names[k], x, x + 147, "-" if y else "+") for k, x, y in zip(c.tolist(), s.tolist(), m.tolist())))
+    t_gen = time.perf_counter() - t0
+    ctx = get_context()
+    dev = ctx.device_info()["name"]
+    for flags in (0, 7):                                            # warm-up: code objects
+        ctx.site_signal(np.zeros(600), [0, 50], [501, 501], [0, 0], [0, 1], K, exp=bool(flags & 1), positive=bool(flags & 2),
+                        scale=bool(flags & 4), want_matrix=True)
+    cn, cc, cs, ce, cm = read_bed_columns(sites, strand_col=6)
+    ws, we, lead, _ = site_windows(cn, cc, cs, ce, cm, {c: L for c in names}, 250, 250)
+    sc, ss, se, off, src = merge_spans(cc, ws, we)
+    tbx = NativeTabix(bg)
+    vals, _ = tbx.read_regions([cn[k] for k in sc.tolist()], ss, se, empty=np.nan, value_col=4)
+    tbx.close()
+    length = (we - ws).astype(np.int32)
+    n = len(cs)
+    for flags in (0, 7):
+        kw = dict(exp=bool(flags & 1), positive=bool(flags & 2), scale=bool(flags & 4))
+        tm = {}
+        args = argparse.Namespace(bed=sites, bg=bg, sizes=sizes, out=os.path.join(d, "bench_signal%d" % flags), cores=1, all=False,
+                                  no_agg=False, up=250, down=250, weight=None, strand=6, norm=False, **kw)
+        t0 = time.perf_counter()
+        agg, _ = get_signal(args, timing=tm)
+        wall = time.perf_counter() - t0
+        ms_mat = min(ctx.site_signal(vals, src, length, lead, cm, K, want_matrix=True, with_kernel_ms=True, **kw)[2] for _ in range(3))
+        ms_agg = min(ctx.site_signal(vals, src, length, lead, cm, K, want_matrix=False, with_kernel_ms=True, **kw)[2] for _ in range(3))
+        numpy_s = None
+        if not a.no_numpy:
+            t0 = time.perf_counter()
+            want, mag = np.zeros(K), np.zeros(K)
+            for i in range(0, n, 8192):
+                m = R.rows_ref_fast(vals, src[i:i + 8192], length[i:i + 8192], lead[i:i + 8192], cm[i:i + 8192], K, flags)
+                want += R.aggregate(m)
+                mag += np.nansum(np.abs(m), axis=0)
+            numpy_s = round(time.perf_counter() - t0, 2)
+            assert np.all(np.abs(agg - want) <= (2 * n + K + 4) * 2.0 ** -52 * mag)
+        print(json.dumps(dict(tool="bench_signal", device=dev, flags=flags, sites=n, columns=K, track_records=n_records,
+                              values_read=int(off[-1]), generate_inputs_s=round(t_gen, 1), bed_s=round(tm["bed_s"], 3),
+                              read_s=round(tm["read_s"], 3), device_s=round(tm["device_s"], 3), kernel_ms=round(tm["kernel_ms"], 3),
+                              kernel_ms_aggregate_only=round(ms_agg, 3), kernel_ms_matrix=round(ms_mat, 3),
+                              floor_ms_aggregate_only=round(n * K * 8 / 8e12 * 1e3, 4), floor_ms_matrix=round(2 * n * K * 8 / 8e12 * 1e3, 4),
+                              text_s=round(tm["text_s"], 4), wall_s=round(wall, 3), numpy_s=numpy_s)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("mode", nargs="?", default="sites", choices=["sites", "signal"],
+                    help="sites: counts and nucleotide (the default); signal: pyatac signal")
+    ap.add_argument("--signal-sites", type=int, default=100_000)
+    ap.add_argument("--signal-ref-len", type=int, default=2_500_000)
     ap.add_argument("--fragments", type=int, default=50_000_000)
     ap.add_argument("--windows", type=int, default=1_000_000)
     ap.add_argument("--sites", type=int, default=1_000_000)
@@ -39,6 +127,8 @@ def main():
     ap.add_argument("--no-numpy", action="store_true", help="skip the NumPy restatement (minutes at the default sizes)")
     ap.add_argument("--out", default=None, help="directory for the synthetic inputs (default: a temporary one)")
     a = ap.parse_args()
+    if a.mode == "signal":
+        return bench_signal(a)
     import sites_ref as R
     from nucleoatac_amd import get_context
     from nucleoatac_amd.pyatac.chunk import read_bed_columns
