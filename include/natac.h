@@ -19,6 +19,8 @@
  *   (6) `pyatac counts`'s per-region fragment counts (pyatac/get_counts.py:30-45) -> natac_region_counts
  *       and `pyatac nucleotide`'s word counts around sites (pyatac/get_nucleotide.py:19-38) -> natac_site_seq_counts
  *   (7) `pyatac signal`'s per-site rows and their aggregate (pyatac/signal_around_sites.py:24-74) -> natac_site_signal
+ *   (8) the reference's only input, a BAM read through pysam (pyatac/fragments.pyx:21-25) -> natac_bam_open / natac_bam_open_device,
+ *       or, where only a fragment file (fragments.tsv.gz) is left of it, natac_frag_open / natac_frag_open_device
  * Every entry point below names the reference code it replaces.  INTEGRATION.md shows the ctypes binding a
  * maintainer of the reference would add.
  *
@@ -46,9 +48,9 @@ extern "C" {
  * natac_store_set_budget / natac_store_declined, gave natac_store_adopt's n_hard == -1 a meaning; 3: round 6 added natac_batch_format_fetch_begin / _wait;
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
  * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
- * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`);
- * the binding refuses another version */
-#define NATAC_ABI_VERSION 8
+ * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`;
+ * 9: added natac_frag_open / natac_frag_open_device for fragment files); the binding refuses another version */
+#define NATAC_ABI_VERSION 9
 
 enum {
     NATAC_OK = 0,
@@ -453,6 +455,31 @@ int natac_bam_ref_reads(natac_bam *bam, int32_t ref, int64_t *pos, int64_t *tlen
  * through the host decoder inside this call; *on_device (may be NULL) tells which one answered.  Damaged files fail with the host
  * decoder's messages. */
 int natac_bam_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int *on_device);
+/* ---- fragment file (fragments.tsv.gz: Cell Ranger ATAC, the ENCODE pipeline, chromap, sinto, SnapATAC / ArchR) -> the same handle ----
+ * THE FORMAT RULE (nucleoatac_amd/pyatac/fragments.py restates it; csrc/natac_fragfile.hpp: parse_line is it).
+ * Lines: a line ends in '\n', a '\r' directly before it is dropped; a last line without '\n' is a line; empty lines and lines whose
+ *   first byte is '#' are skipped.
+ * Fields: every other line is a data line: fields separated by TAB only, at least three; fields after the third are ignored whatever
+ *   bytes they hold (barcode, duplicate count: one line is one fragment, identical lines are separate fragments).  chrom is 1-255
+ *   bytes; start and end are 1-10 ASCII digits (no sign, no blanks), value <= 2^31 - 1, end >= start.
+ * Mapping: [start, end) is the insertion-to-insertion interval the reference's ATAC offsets produce (pyatac/fragments.pyx:26-31:
+ *   l = start, ilen = end - start), so the stored record is pos = start - 4 (may be negative), tlen = end - start + 8; end == start is
+ *   kept (the BAM path admits ilen == 0 too).  A file written with the +4/-5 convention is one base shorter at the right end than the
+ *   reference's +4/-4 reading of the same BAM; nothing is corrected: the writer's convention is not recorded in the file.
+ * Chromosomes: numbered in order of first appearance; one that comes back later in an unsorted file keeps its id, its records in file
+ *   order.  There is no sequence dictionary: a chromosome's length is the largest end on it.
+ * Errors: a malformed data line fails the call with "<path>: line <N>: <reason>", N 1-based and counting skipped lines, one fixed
+ *   reason per cause (fewer than three fields, empty chromosome name, chromosome name longer than 255 bytes, start / end not a
+ *   number, number out of range, end before start); nothing is returned.
+ * The container is chosen by magic bytes: BGZF, any other gzip (several members allowed), or plain text.  The result does not depend
+ * on n_threads (0 = the machine's cores, at most 64).  natac_bam_counts / _ref_info / _ref_reads / _close serve the handle, with
+ * n_records = n_kept = the number of data lines. */
+int natac_frag_open(const char *path, int n_threads, natac_bam **out);
+/* The same with a BGZF file's members inflated (CRC-32 checked) and its text split into lines, parsed and compacted ON THE DEVICE
+ * (csrc/natac_fragfile_dev.hpp).  The host decoder answers inside this call for another container, any malformed line or damaged
+ * member (so the message is natac_frag_open's by construction), a line longer than a window, more than 65,536 chromosome runs in a
+ * window, or a HIP failure; *on_device (may be NULL) tells which one answered. */
+int natac_frag_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int *on_device);
 /* test entry: the device's raw-deflate decoder run on the host (one BGZF member payload -> isize bytes); returns its error code */
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize);
 

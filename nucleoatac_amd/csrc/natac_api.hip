@@ -16,6 +16,8 @@
 #include "natac_pack.hpp"
 #include "natac_bam.hpp"
 #include "natac_bam_dev.hpp"
+#include "natac_fragfile.hpp"
+#include "natac_fragfile_dev.hpp"
 #include "natac_fasta.hpp"
 #include "natac_fuzzfit.hpp"
 #include "natac_bedtab.hpp"
@@ -3256,6 +3258,55 @@ int natac_bam_open_device(natac_ctx *c, const char *path, natac_bam **out, int *
         if (const char *e = getenv("NATAC_BAM_WINDOW")) { const long long v = atoll(e); if (v > 0) hw = (size_t)v; }
         impl = natac_bamio::decode(path, 0, err, hw);
     }
+    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
+    natac_bam *h = new natac_bam();
+    h->impl = impl;
+    *out = h;
+    return NATAC_OK;
+}
+
+/* ---------------- fragment files (fragments.tsv.gz) into the same handle ---------------- */
+
+static size_t frag_host_window() {                    // (compressed) bytes per streaming window; NATAC_BAM_WINDOW overrides (tests)
+    size_t window = (size_t)48 << 20;
+    if (const char *e = getenv("NATAC_BAM_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+    return window;
+}
+
+int natac_frag_open(const char *path, int n_threads, natac_bam **out) {
+    if (!path || !out) return fail(NATAC_E_ARG, "null argument");
+    *out = nullptr;
+    std::string err;
+    natac_bamio::Bam *impl = natac_fragio::decode(path, n_threads, err, frag_host_window());
+    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
+    natac_bam *h = new natac_bam();
+    h->impl = impl;
+    *out = h;
+    return NATAC_OK;
+}
+
+int natac_frag_open_device(natac_ctx *c, const char *path, natac_bam **out, int *on_device) {
+    if (!c || !path || !out) return fail(NATAC_E_ARG, "null argument");
+    *out = nullptr;
+    if (on_device) *on_device = 0;
+    HIPCHK(hipSetDevice(c->device));
+    bool bgzf = false;
+    if (FILE *f = std::fopen(path, "rb")) {
+        unsigned char magic[1040];
+        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
+        std::fclose(f);
+    }
+    natac_bamio::Bam *impl = nullptr;
+    std::string err;
+    if (bgzf) {                                       // other containers are the host decoder's
+        size_t window = (size_t)1 << 30;              // compressed bytes per device window; NATAC_FRAG_DEV_WINDOW overrides (tests)
+        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+        std::string why;
+        impl = natac_fragdev::decode_device(path, c->stream, why, window);
+        if (impl && on_device) *on_device = 1;
+    }
+    // not BGZF, a malformed line, a damaged file, a line longer than a window, too many runs or a HIP failure: the host decoder answers
+    if (!impl) impl = natac_fragio::decode(path, 0, err, frag_host_window());
     if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
     natac_bam *h = new natac_bam();
     h->impl = impl;

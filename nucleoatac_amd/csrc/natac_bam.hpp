@@ -36,28 +36,28 @@ inline uint32_t rd32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_
 inline int32_t rdi32(const unsigned char *p) { return (int32_t)rd32(p); }
 inline uint16_t rd16(const unsigned char *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
-// Streaming decode with bounded memory: the file is read in windows of ~batch_bytes of compressed data; the complete BGZF
-// blocks of a window are inflated in parallel into one buffer that is prefixed with the unparsed remainder of the
-// previous window (a BAM record -- or the header -- may straddle any number of blocks), the records are walked, and only
-// the two numbers per kept read stay.  Peak memory = one compressed window + its inflated form (+ the output arrays),
-// independent of the file size.  returns nullptr + error text on failure.
-inline Bam *decode(const char *path, int n_threads, std::string &err, size_t batch_bytes = (size_t)48 << 20) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) { err = std::string("cannot open ") + path; return nullptr; }
-    if (n_threads <= 0) n_threads = natac_cores::default_threads(64);
-    batch_bytes = std::max<size_t>(batch_bytes, (size_t)4096);           // + 64 KiB below: always room for one maximal BGZF block
+// The BGZF layer of the streaming decoders (BAM records here, fragment-file text in natac_fragfile.hpp): the file is read in windows of
+// ~batch_bytes of compressed data, and the complete BGZF blocks of a window are inflated in parallel (CRC-32 checked) behind the `pend`
+// bytes the caller kept at the front of its buffer.
+struct BgzfWindows {
     struct Blk { size_t off, csize; uint32_t isize; size_t uoff; uint32_t crc; };
-    std::vector<unsigned char> raw, data;
+    FILE *f = nullptr;
+    int n_threads = 1;
+    std::vector<unsigned char> raw;
     std::vector<Blk> blks;
     size_t raw_len = 0;            // valid bytes in raw (starts with the leftover of the previous window)
-    size_t pend = 0;               // unparsed bytes at the front of data
-    bool eof = false, header_done = false, any_block = false;
-    int32_t n_ref = 0;
-    Bam *bam = new Bam();
-    auto fail = [&](const char *msg) -> Bam * { err = msg; delete bam; std::fclose(f); return nullptr; };
+    bool eof = false, any_block = false;
     unsigned long long window_file_off = 0;      // file offset of raw[0]
-    raw.resize(batch_bytes + ((size_t)1 << 16));
-    while (!eof || raw_len > 0) {
+    std::string error;
+    BgzfWindows(FILE *file, int threads, size_t batch_bytes) : f(file), n_threads(threads) {
+        batch_bytes = std::max<size_t>(batch_bytes, (size_t)4096);       // + 64 KiB below: always room for one maximal BGZF block
+        raw.resize(batch_bytes + ((size_t)1 << 16));
+    }
+    bool drained() const { return eof && raw_len == 0; }
+    // the next window: data[pend, *utotal) = its inflated bytes.  1: a window, 0: the file is done, -1: `error` says why not
+    int next(std::vector<unsigned char> &data, size_t pend, size_t *utotal_out) {
+        auto fail = [&](const char *msg) { error = msg; return -1; };
+        if (drained()) return 0;
         // ---- refill the compressed window
         if (!eof) {
             const size_t want = raw.size() - raw_len;
@@ -93,7 +93,7 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t bat
         if (blks.empty()) {
             if (eof) {
                 if (raw_len > 0) return fail(any_block ? "trailing bytes after the last BGZF block" : "not a BGZF file (bad block header)");
-                break;
+                return 0;
             }
             return fail("BGZF block larger than the read window");
         }
@@ -142,7 +142,7 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t bat
                 size_t hdr = pay >= 18 ? pay - 18 : 0;
                 for (size_t b = pay >= 18 ? pay - 18 : 0; b + 12 <= pay; ++b)      // (only XLEN = pay - b - 12 is consistent)
                     if (raw[b] == 0x1f && raw[b + 1] == 0x8b && (size_t)rd16(raw.data() + b + 10) == pay - b - 12) { hdr = b; break; }
-                static thread_local char msg[128];
+                char msg[128];
                 std::snprintf(msg, sizeof msg, "CRC-32 mismatch in the BGZF member at file offset %llu (corrupt file)", window_file_off + hdr);
                 return fail(msg);
             }
@@ -150,6 +150,31 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t bat
         std::memmove(raw.data(), raw.data() + o, raw_len - o);      // leftover compressed bytes (a partial block)
         raw_len -= o;
         window_file_off += o;
+        *utotal_out = utotal;
+        return 1;
+    }
+};
+
+// Streaming decode with bounded memory: the file is read in windows of ~batch_bytes of compressed data (BgzfWindows); a window's
+// inflated bytes are prefixed with the unparsed remainder of the previous window (a BAM record -- or the header -- may straddle any
+// number of blocks), the records are walked, and only the two numbers per kept read stay.  Peak memory = one compressed window + its
+// inflated form (+ the output arrays), independent of the file size.  returns nullptr + error text on failure.
+inline Bam *decode(const char *path, int n_threads, std::string &err, size_t batch_bytes = (size_t)48 << 20) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) { err = std::string("cannot open ") + path; return nullptr; }
+    if (n_threads <= 0) n_threads = natac_cores::default_threads(64);
+    BgzfWindows z(f, n_threads, batch_bytes);
+    std::vector<unsigned char> data;
+    size_t pend = 0;               // unparsed bytes at the front of data
+    bool header_done = false;
+    int32_t n_ref = 0;
+    Bam *bam = new Bam();
+    auto fail = [&](const char *msg) -> Bam * { err = msg; delete bam; std::fclose(f); return nullptr; };
+    for (;;) {
+        size_t utotal = 0;
+        const int got = z.next(data, pend, &utotal);
+        if (got < 0) return fail(z.error.c_str());
+        if (got == 0) break;
         // ---- walk the uncompressed bytes [0, utotal)
         const unsigned char *p = data.data();
         const size_t n = utotal;
@@ -182,7 +207,7 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t bat
                 complete = true;
             } while (false);
             if (!complete) {
-                if (eof && raw_len == 0) return fail(n < 12 ? "not a BAM file (bad magic)" : "truncated BAM header");
+                if (z.drained()) return fail(n < 12 ? "not a BAM file (bad magic)" : "truncated BAM header");
                 pend = n;                                             // wait for more data
                 continue;
             }
@@ -207,10 +232,10 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t bat
         }
         pend = n - q;
         std::memmove(data.data(), data.data() + q, pend);
-        if (eof && raw_len == 0) break;
+        if (z.drained()) break;
     }
     std::fclose(f);
-    if (!header_done) { err = any_block ? "truncated BAM header" : "not a BGZF file (bad block header)"; delete bam; return nullptr; }
+    if (!header_done) { err = z.any_block ? "truncated BAM header" : "not a BGZF file (bad block header)"; delete bam; return nullptr; }
     if (pend != 0) { err = "truncated alignment record"; delete bam; return nullptr; }
     return bam;
 }

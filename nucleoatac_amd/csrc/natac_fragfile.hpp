@@ -1,0 +1,263 @@
+// natac_fragfile.hpp -- fragment file (fragments.tsv.gz of Cell Ranger ATAC, ENCODE, chromap, sinto, ArchR ...) -> fragment arrays, host C++17.
+//
+// A fragment file is tab-separated text, one fragment per line (chrom start end [barcode [count]]), usually BGZF-compressed.  The
+// store keeps (pos, |tlen|) of the forward proper-pair reads of a BAM (natac_bam.hpp), which is what such a line carries: the format
+// rule of include/natac.h (natac_frag_open) maps [start, end) to pos = start - 4, tlen = end - start + 8, the inverse of the reference's
+// ATAC offsets (pyatac/fragments.pyx:26-31).  parse_line below IS that rule; it is __host__ __device__ so that the device decoder
+// (natac_fragfile_dev.hpp) classifies every line with the same code.
+// Container by magic bytes: BGZF (the window reader of natac_bam.hpp), any other gzip (zlib, several members allowed), plain text.
+#pragma once
+#include "natac_bam.hpp"
+
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#ifdef __HIPCC__
+#define NATAC_FRAG_HD __host__ __device__
+#else
+#define NATAC_FRAG_HD
+#endif
+
+namespace natac_fragio {
+
+using natac_bamio::Bam;
+using natac_bamio::Ref;
+
+// what a line is: LINE_SKIP (empty or '#'), LINE_DATA, or a malformed data line (one value per fixed reason string)
+enum { LINE_SKIP = 0, LINE_DATA = 1, BAD_FIELDS = 2, BAD_NAME_EMPTY = 3, BAD_NAME_LONG = 4, BAD_NUMBER = 5, BAD_RANGE = 6, BAD_ORDER = 7 };
+
+inline const char *reason_text(int kind) {
+    switch (kind) {
+        case BAD_FIELDS: return "fewer than three tab-separated fields";
+        case BAD_NAME_EMPTY: return "empty chromosome name";
+        case BAD_NAME_LONG: return "chromosome name longer than 255 bytes";
+        case BAD_NUMBER: return "start / end is not a number";
+        case BAD_RANGE: return "start / end out of range (more than 2147483647)";
+        case BAD_ORDER: return "end before start";
+    }
+    return "";
+}
+
+// 1-10 ASCII digits, value <= 2^31 - 1.  LINE_DATA, BAD_NUMBER or BAD_RANGE.
+NATAC_FRAG_HD inline int parse_coord(const unsigned char *p, size_t len, int32_t *out) {
+    if (len == 0) return BAD_NUMBER;
+    unsigned long long v = 0;
+    for (size_t i = 0; i < len; ++i) {
+        const unsigned d = (unsigned)p[i] - (unsigned)'0';
+        if (d > 9u) return BAD_NUMBER;
+        if (i < 11) v = v * 10ull + d;                  // (eleven digits of nines fit 64 bits; more digits are out of range anyway)
+    }
+    if (len > 10 || v > 2147483647ull) return BAD_RANGE;
+    *out = (int32_t)v;
+    return LINE_DATA;
+}
+
+// One line p[0, len) without its '\n' (and without the '\r' before it).  Checks in this order: fields, name, start, end, end >= start.
+NATAC_FRAG_HD inline int parse_line(const unsigned char *p, size_t len, uint32_t *name_len, int32_t *start, int32_t *end) {
+    if (len == 0 || p[0] == '#') return LINE_SKIP;
+    size_t t1 = 0;
+    while (t1 < len && p[t1] != '\t') ++t1;
+    size_t t2 = t1 + 1;
+    while (t2 < len && p[t2] != '\t') ++t2;
+    if (t1 >= len || t2 >= len) return BAD_FIELDS;
+    size_t t3 = t2 + 1;
+    while (t3 < len && p[t3] != '\t') ++t3;
+    if (t1 == 0) return BAD_NAME_EMPTY;
+    if (t1 > 255) return BAD_NAME_LONG;
+    int rc = parse_coord(p + t1 + 1, t2 - t1 - 1, start);
+    if (rc != LINE_DATA) return rc;
+    rc = parse_coord(p + t2 + 1, t3 - t2 - 1, end);
+    if (rc != LINE_DATA) return rc;
+    if (*end < *start) return BAD_ORDER;
+    *name_len = (uint32_t)t1;
+    return LINE_DATA;
+}
+
+// chromosomes in order of first appearance; a chromosome that comes back gets its old id and its records go behind the earlier ones
+struct Builder {
+    Bam *bam;
+    std::unordered_map<std::string, int> ids;
+    explicit Builder(Bam *b) : bam(b) {}
+    Ref &ref_of(const std::string &name) {
+        auto it = ids.find(name);
+        if (it == ids.end()) {
+            it = ids.emplace(name, (int)bam->refs.size()).first;
+            bam->refs.emplace_back();
+            bam->refs.back().name = name;
+        }
+        return bam->refs[(size_t)it->second];
+    }
+};
+
+struct Run {                        // consecutive data lines of one chromosome
+    std::string name;
+    std::vector<int64_t> pos, tlen;
+    int64_t max_end = 0;
+};
+struct SliceOut {
+    std::vector<Run> runs;
+    size_t n_lines = 0;             // lines seen (up to and including a malformed one)
+    int bad = 0;                    // reason of the first malformed line (it is line n_lines of the slice)
+};
+
+// the complete lines of p[a, b) (b is behind a '\n', or `open_end`: the last line of the file has no '\n')
+inline void parse_slice(const unsigned char *p, size_t a, size_t b, bool open_end, SliceOut *out) {
+    Run *run = nullptr;
+    while (a < b) {
+        const unsigned char *nl = (const unsigned char *)std::memchr(p + a, '\n', b - a);
+        size_t e = nl ? (size_t)(nl - p) : b;
+        const size_t next = nl ? e + 1 : b;
+        if (!nl && !open_end) break;
+        if (nl && e > a && p[e - 1] == '\r') --e;
+        ++out->n_lines;
+        uint32_t nlen = 0;
+        int32_t s = 0, t = 0;
+        const int kind = parse_line(p + a, e - a, &nlen, &s, &t);
+        if (kind > LINE_DATA) { out->bad = kind; return; }
+        if (kind == LINE_DATA) {
+            if (!run || run->name.size() != nlen || std::memcmp(run->name.data(), p + a, nlen) != 0) {
+                out->runs.emplace_back();
+                run = &out->runs.back();
+                run->name.assign((const char *)p + a, nlen);
+            }
+            run->pos.push_back((int64_t)s - 4);
+            run->tlen.push_back((int64_t)t - (int64_t)s + 8);
+            if (t > run->max_end) run->max_end = t;
+        }
+        a = next;
+    }
+}
+
+inline void append_run(Builder &bd, const std::string &name, const int64_t *pos, const int64_t *tlen, size_t n, int64_t max_end) {
+    Ref &r = bd.ref_of(name);
+    r.pos.insert(r.pos.end(), pos, pos + n);
+    r.tlen.insert(r.tlen.end(), tlen, tlen + n);
+    if (max_end > r.length) r.length = max_end;
+    bd.bam->n_records += (int64_t)n;
+    bd.bam->n_kept += (int64_t)n;
+}
+
+// Lines of p[0, n) in line-aligned slices, one per thread; the slices are merged in file order, so the result (and the first error) does
+// not depend on n_threads.  *lines counts every line of the file so far.  false + err on a malformed line.
+inline bool parse_text(const unsigned char *p, size_t n, bool open_end, int n_threads, Builder &bd, unsigned long long *lines, std::string &err) {
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_threads), n / 256));
+    std::vector<size_t> cut((size_t)T + 1, n);
+    cut[0] = 0;
+    for (int t = 1; t < T; ++t) {
+        const size_t at = std::max(cut[(size_t)t - 1], n * (size_t)t / (size_t)T);
+        const unsigned char *nl = at < n ? (const unsigned char *)std::memchr(p + at, '\n', n - at) : nullptr;
+        cut[(size_t)t] = nl ? (size_t)(nl - p) + 1 : n;
+    }
+    std::vector<SliceOut> out((size_t)T);
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t) th.emplace_back(parse_slice, p, cut[(size_t)t], cut[(size_t)t + 1], open_end, &out[(size_t)t]);
+    parse_slice(p, cut[0], cut[1], open_end, &out[0]);
+    for (auto &x : th) x.join();
+    for (auto &so : out) {
+        *lines += so.n_lines;
+        if (so.bad) { err = "line " + std::to_string(*lines) + ": " + reason_text(so.bad); return false; }
+        for (auto &r : so.runs) append_run(bd, r.name, r.pos.data(), r.tlen.data(), r.pos.size(), r.max_end);
+    }
+    return true;
+}
+
+// BGZF: a gzip member whose extra field holds the BC subfield (SAM spec 4.1)
+inline bool is_bgzf(const unsigned char *h, size_t have) {
+    if (have < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return false;
+    const size_t xlen = natac_bamio::rd16(h + 10);
+    for (size_t x = 12; x + 4 <= 12 + xlen && x + 4 <= have;) {
+        const unsigned slen = natac_bamio::rd16(h + x + 2);
+        if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) return true;
+        x += 4 + slen;
+    }
+    return false;
+}
+
+// Streaming decode, bounded memory like natac_bamio::decode: ~window bytes of (compressed) input at a time, the bytes behind a window's
+// last '\n' carried to the front of the next.  returns nullptr + error text ("line N: reason" for a malformed line).
+inline Bam *decode(const char *path, int n_threads, std::string &err, size_t window = (size_t)48 << 20) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) { err = std::string("cannot open ") + path; return nullptr; }
+    if (n_threads <= 0) n_threads = natac_cores::default_threads(64);
+    window = std::max<size_t>(window, (size_t)4096);
+    unsigned char magic[1040];
+    const size_t have = std::fread(magic, 1, sizeof magic, f);
+    std::rewind(f);
+    const bool gz = have >= 2 && magic[0] == 0x1f && magic[1] == 0x8b, bgzf = is_bgzf(magic, have);
+    Bam *bam = new Bam();
+    Builder bd(bam);
+    std::vector<unsigned char> data, in;
+    std::unique_ptr<natac_bamio::BgzfWindows> z(bgzf ? new natac_bamio::BgzfWindows(f, n_threads, window) : nullptr);
+    z_stream zs;
+    std::memset(&zs, 0, sizeof zs);
+    bool zs_open = false, in_member = false, file_end = false;
+    auto fail = [&](const std::string &msg) -> Bam * {
+        err = msg;
+        delete bam;
+        if (zs_open) inflateEnd(&zs);
+        std::fclose(f);
+        return nullptr;
+    };
+    if (gz && !bgzf) {
+        if (inflateInit2(&zs, 15 + 16) != Z_OK) return fail("zlib: inflateInit2 failed");
+        zs_open = true;
+        in.resize(std::min<size_t>(window, (size_t)4 << 20));
+    }
+    // the next window of text behind data[0, pend): 1 a window, 0 the file is done, -1 error (in msg)
+    std::string msg;
+    auto next = [&](size_t pend, size_t *n) -> int {
+        if (bgzf) { const int rc = z->next(data, pend, n); if (rc < 0) msg = z->error; return rc; }
+        if (data.size() < pend + window) data.resize(pend + window);
+        if (!gz) {
+            const size_t got = std::fread(data.data() + pend, 1, window, f);
+            *n = pend + got;
+            return got ? 1 : 0;
+        }
+        size_t o = pend;
+        while (o < pend + window) {
+            if (zs.avail_in == 0) {
+                if (file_end) break;
+                zs.avail_in = (uInt)std::fread(in.data(), 1, in.size(), f);
+                zs.next_in = in.data();
+                if (zs.avail_in == 0) { file_end = true; break; }
+            }
+            if (!in_member) {            // between members: zero padding is skipped (as gzip does), anything else must be a member
+                while (zs.avail_in && *zs.next_in == 0) { ++zs.next_in; --zs.avail_in; }
+                if (!zs.avail_in) continue;
+                in_member = true;
+            }
+            zs.next_out = data.data() + o;
+            zs.avail_out = (uInt)std::min<size_t>(pend + window - o, (size_t)1 << 30);
+            const size_t before = zs.avail_out;
+            const int rc = inflate(&zs, Z_NO_FLUSH);
+            o += before - zs.avail_out;
+            if (rc == Z_STREAM_END) { in_member = false; inflateReset(&zs); }
+            else if (rc != Z_OK && rc != Z_BUF_ERROR) { msg = "inflate failed (corrupt gzip stream)"; return -1; }
+        }
+        if (file_end && zs.avail_in == 0 && in_member && o < pend + window) { msg = "truncated gzip stream"; return -1; }
+        *n = o;
+        return o > pend || !file_end ? 1 : 0;
+    };
+    size_t pend = 0;
+    unsigned long long lines = 0;
+    for (;;) {
+        size_t n = 0;
+        const int got = next(pend, &n);
+        if (got < 0) return fail(msg);
+        if (got == 0) break;
+        size_t last = n;                                   // behind the last '\n' of the window
+        while (last > pend && data[last - 1] != '\n') --last;
+        if (last == pend) { pend = n; continue; }           // no line ends in this window: a line longer than it
+        if (!parse_text(data.data(), last, false, n_threads, bd, &lines, err)) return fail(err);
+        pend = n - last;
+        std::memmove(data.data(), data.data() + last, pend);
+    }
+    if (pend && !parse_text(data.data(), pend, true, 1, bd, &lines, err)) return fail(err);       // a last line without '\n' is a line
+    if (zs_open) inflateEnd(&zs);
+    std::fclose(f);
+    return bam;
+}
+
+}  // namespace natac_fragio

@@ -1,0 +1,435 @@
+// natac_fragfile_dev.hpp -- BGZF fragment file -> fragment arrays on the GPU.
+//
+// The members are found, staged and inflated exactly as for a BAM (natac_bam_dev.hpp: walk_chain, two pinned staging buffers,
+// bamdev_inflate with its CRC check).  What follows the inflate differs: a window's inflated bytes are TEXT, and a line may start
+// anywhere and straddle any number of members, so nothing here works per member.  On the window's contiguous text:
+//   (a) frag_count_nl / frag_scan / frag_line_starts: every lane loads 16 bytes and builds a newline mask; the per-tile counts are
+//       scanned and become the offsets at which the lanes write the line starts.
+//   (b) frag_parse: one lane per line runs natac_fragio::parse_line (the host decoder's own classifier) and compares the line's
+//       chromosome field byte-wise with the previous data line's: a difference starts a RUN.
+//   (c) frag_compact: a scan over (is data, starts a run) gives every data line its output slot and its run; start / end are
+//       written in file order, and per run its first slot, the offset and length of its name and its largest end.
+// The host reads the few run names back (frag_gather_names), maps them to chromosome ids with the host decoder's dictionary (this is
+// where a chromosome that comes back gets its old id) and appends.  The bytes behind a window's last '\n' are carried to the front
+// of the next window.  Every device read is bounded by the window's length n, whatever the text holds.
+// The host decoder answers instead (the caller runs it) for: a malformed line or a damaged file (so both paths give the same message
+// by construction), a window without any line end, more than MAX_RUNS runs in a window, a HIP failure.
+#pragma once
+#include "natac_bam_dev.hpp"
+#include "natac_fragfile.hpp"
+
+namespace natac_fragdev {
+
+using natac_bamdev::Chain;
+using natac_bamdev::DevBuf;
+using natac_bamdev::Member;
+typedef unsigned long long u64;
+
+constexpr int TILE_T = 256;                 // lanes per workgroup
+constexpr int TILE_B = 16 * TILE_T;         // text bytes per workgroup in (a)
+constexpr unsigned int MAX_RUNS = 65536;    // per window
+
+// exclusive prefix sum of v over the workgroup (blockDim.x a multiple of 64, at most 1024); *total = the workgroup's sum
+__device__ __forceinline__ u64 block_excl_scan(u64 v, u64 *total) {
+    __shared__ u64 wsum[16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    u64 inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 up = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += up;
+    }
+    __syncthreads();                        // (a second call in one kernel: the sums of the first are no longer read)
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    u64 before = 0, all = 0;
+    for (int k = 0; k < nw; ++k) { const u64 s = wsum[k]; if (k < w) before += s; all += s; }
+    *total = all;
+    return before + inc - v;
+}
+
+// newline mask of the 16 bytes at `base` (a multiple of 16; the buffer is readable up to the next multiple of 16 behind n)
+__device__ __forceinline__ unsigned int nl_mask16(const unsigned char *__restrict__ data, u64 base, u64 n) {
+    if (base >= n) return 0u;
+    const uint4 q = *(const uint4 *)(data + base);
+    const unsigned int w[4] = {q.x, q.y, q.z, q.w};
+    unsigned int m = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m |= (((w[k >> 2] >> (8 * (k & 3))) & 0xffu) == 10u ? 1u : 0u) << k;
+    if (n - base < 16) m &= (1u << (unsigned int)(n - base)) - 1u;
+    return m;
+}
+
+__global__ void __launch_bounds__(TILE_T) frag_count_nl(const unsigned char *__restrict__ data, u64 n, u64 *__restrict__ tile_cnt) {
+    const u64 base = ((u64)blockIdx.x * TILE_T + threadIdx.x) * 16;
+    u64 total;
+    block_excl_scan((u64)__popc(nl_mask16(data, base, n)), &total);
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+}
+
+// exclusive scan of a[0, count) in place, one workgroup of 1024 (count is a number of TILES or of workgroups: a few hundred thousand
+// at most); *total = the sum.  Values that pack two 32-bit counters scan as two sums.
+__global__ void __launch_bounds__(1024) frag_scan(u64 *__restrict__ a, u64 count, u64 *__restrict__ total) {
+    const u64 per = (count + 1023) / 1024, lo = min(count, per * threadIdx.x), hi = min(count, lo + per);
+    u64 s = 0;
+    for (u64 i = lo; i < hi; ++i) s += a[i];
+    u64 all;
+    u64 run = block_excl_scan(s, &all);
+    for (u64 i = lo; i < hi; ++i) { const u64 v = a[i]; a[i] = run; run += v; }
+    if (threadIdx.x == 0) *total = all;
+}
+
+// ls[1 + k] = offset behind the k-th '\n' (ls[0] = 0 is the host's); cap = number of '\n' counted
+__global__ void __launch_bounds__(TILE_T) frag_line_starts(const unsigned char *__restrict__ data, u64 n, const u64 *__restrict__ tile_off, u64 cap,
+                                                           u64 *__restrict__ ls) {
+    const u64 base = ((u64)blockIdx.x * TILE_T + threadIdx.x) * 16;
+    unsigned int m = nl_mask16(data, base, n);
+    u64 total;
+    u64 k = tile_off[blockIdx.x] + block_excl_scan((u64)__popc(m), &total);
+    while (m) {
+        const int b = __ffs(m) - 1;
+        m &= m - 1;
+        if (k < cap) ls[1 + k] = base + (u64)b + 1;
+        ++k;
+    }
+}
+
+// line i = data[ls[i], ls[i + 1] - 1) without the '\r' before its '\n'; open_tail: the last line has no '\n' (ls[n_lines] = n + 1)
+__device__ __forceinline__ void line_span(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 i, u64 n_lines, int open_tail, u64 *a, u64 *e) {
+    *a = ls[i];
+    *e = ls[i + 1] - 1;
+    if (!(open_tail && i + 1 == n_lines) && *e > *a && data[*e - 1] == '\r') --*e;
+}
+
+// code[i] = (is data) << 32 | (starts a run); status[0] |= 1 for a malformed line
+__global__ void __launch_bounds__(TILE_T) frag_parse(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 n_lines, int open_tail,
+                                                     u64 *__restrict__ code, int *__restrict__ start, int *__restrict__ end, unsigned int *__restrict__ name_len,
+                                                     u64 *__restrict__ block_sum, int *__restrict__ status) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    u64 c = 0;
+    if (i < n_lines) {
+        u64 a, e;
+        line_span(data, ls, i, n_lines, open_tail, &a, &e);
+        uint32_t nlen = 0;
+        int32_t s = 0, t = 0;
+        const int kind = natac_fragio::parse_line(data + a, (size_t)(e - a), &nlen, &s, &t);
+        if (kind > natac_fragio::LINE_DATA) atomicOr(&status[0], 1);
+        if (kind == natac_fragio::LINE_DATA) {
+            bool differs = true;
+            for (u64 j = i; j-- > 0;) {                      // the previous line that is not skipped
+                u64 pa, pe;
+                line_span(data, ls, j, n_lines, open_tail, &pa, &pe);
+                if (pe == pa || data[pa] == '#') continue;
+                differs = pe - pa <= nlen || data[pa + nlen] != '\t';
+                for (uint32_t k = 0; k < nlen && !differs; ++k) differs = data[pa + k] != data[a + k];
+                break;
+            }
+            c = (1ull << 32) | (differs ? 1ull : 0ull);
+            start[i] = s;
+            end[i] = t;
+            name_len[i] = nlen;
+        }
+        code[i] = c;
+    }
+    u64 total;
+    block_excl_scan(c, &total);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
+}
+
+// block_off = the scanned block_sum.  Data line -> slot d (file order), run r; per run: first slot, name offset / length, largest end
+__global__ void __launch_bounds__(TILE_T) frag_compact(const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ code, const int *__restrict__ start,
+                                                       const int *__restrict__ end, const unsigned int *__restrict__ name_len, const u64 *__restrict__ block_off,
+                                                       u64 n_data, unsigned int n_runs, int *__restrict__ o_start, int *__restrict__ o_end,
+                                                       u64 *__restrict__ run_first, u64 *__restrict__ run_name, unsigned int *__restrict__ run_nlen,
+                                                       int *__restrict__ run_max) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    const u64 c = i < n_lines ? code[i] : 0ull;
+    u64 total;
+    const u64 ex = block_off[blockIdx.x] + block_excl_scan(c, &total);
+    const u64 d = ex >> 32;
+    const unsigned int r = (unsigned int)(ex & 0xffffffffull) + (unsigned int)(c & 1ull) - 1u;      // a data line's run (the first data line starts run 0)
+    const bool is_data = (c >> 32) != 0 && d < n_data && r < n_runs;
+    int en = 0;
+    if (is_data) {
+        en = end[i];
+        o_start[d] = start[i];
+        o_end[d] = en;
+        if (c & 1ull) { run_first[r] = d; run_name[r] = ls[i]; run_nlen[r] = name_len[i]; }
+    }
+    // largest end per run: one atomic per wave where the wave's data lines share a run (nearly every wave of a sorted file)
+    const u64 m = __ballot(is_data);
+    if (m == 0) return;
+    const int lead = __ffsll((long long)m) - 1;
+    const unsigned int r0 = __shfl(r, lead, 64);
+    if (__ballot(is_data && r != r0) == 0) {
+        int v = en;
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) v = max(v, __shfl_xor(v, k, 64));
+        if ((int)(threadIdx.x & 63) == lead) atomicMax(&run_max[r0], v);
+    } else if (is_data) atomicMax(&run_max[r], en);
+}
+
+// names[r * 256 ...] = the name of run r (at most 255 bytes: parse_line's rule), read inside [0, n)
+__global__ void __launch_bounds__(64) frag_gather_names(const unsigned char *__restrict__ data, u64 n, const u64 *__restrict__ run_name,
+                                                        const unsigned int *__restrict__ run_nlen, unsigned int n_runs, unsigned char *__restrict__ names) {
+    const unsigned int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= n_runs) return;
+    const u64 a = run_name[r];
+    const unsigned int len = min(run_nlen[r], 255u);
+    for (unsigned int k = 0; k < len && a + k < n; ++k) names[(u64)r * 256 + k] = data[a + k];
+}
+
+// Returns the same object as natac_fragio::decode, or nullptr: the host decoder answers (`why` says what stopped the device path).
+inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std::string &why, size_t window_bytes = (size_t)1 << 30) {
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) { why = std::string("cannot open ") + path; return nullptr; }
+    struct stat sb;
+    if (fstat(fd, &sb) != 0) { close(fd); why = "cannot size the file"; return nullptr; }
+    const u64 fsize = (u64)sb.st_size;
+    window_bytes = std::max<size_t>(window_bytes, (size_t)4096);
+    const size_t STAGE = (size_t)std::min<u64>((u64)32 << 20, std::max<u64>(fsize, 4096));      // two small pinned buffers: natac_bam_dev.hpp says why
+    unsigned char *stage[2] = {nullptr, nullptr};
+    hipEvent_t staged[2] = {nullptr, nullptr};
+    natac_bamio::Bam *bam = new natac_bamio::Bam();
+    natac_fragio::Builder bd(bam);
+    DevBuf d_raw, d_mem, d_data[2], d_status, d_queue, d_crc, d_tile, d_ls, d_code, d_start, d_end, d_nlen, d_bsum, d_total, d_ostart, d_oend, d_rfirst,
+        d_rname, d_rnlen, d_rmax, d_names;
+    hipStream_t aux[3] = {nullptr, nullptr, nullptr};
+    std::vector<Member> mem;
+    std::vector<int> h_start, h_end, h_rmax;
+    std::vector<u64> h_rfirst;
+    std::vector<unsigned int> h_rnlen;
+    std::vector<unsigned char> h_names;
+    std::vector<int64_t> pos, tlen;
+    int cur_buf = 0;
+    Chain chain;
+    std::thread walker(natac_bamdev::walk_chain, fd, fsize, &chain);
+    auto cleanup = [&]() {
+        if (walker.joinable()) walker.join();
+        for (int i = 0; i < 3; ++i) if (aux[i]) { (void)hipStreamSynchronize(aux[i]); (void)hipStreamDestroy(aux[i]); }
+        (void)hipStreamSynchronize(stream);
+        for (int i = 0; i < 2; ++i) { if (stage[i]) (void)hipHostFree(stage[i]); if (staged[i]) (void)hipEventDestroy(staged[i]); }
+        close(fd);
+    };
+    auto give_up = [&](const std::string &msg) -> natac_bamio::Bam * { why = msg; delete bam; cleanup(); return nullptr; };
+#define FRAGDEV_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return give_up(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    for (int i = 0; i < 2; ++i) {
+        FRAGDEV_HIP(hipHostMalloc((void **)&stage[i], STAGE, hipHostMallocDefault));
+        FRAGDEV_HIP(hipEventCreateWithFlags(&staged[i], hipEventDisableTiming));
+    }
+    for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
+    FRAGDEV_HIP(d_status.reserve(4 * sizeof(int)));
+    FRAGDEV_HIP(d_total.reserve(2 * sizeof(u64)));
+    {
+        std::vector<unsigned int> t8(8 * 256);
+        natac_bamdev::crc32_slice8_tables(t8.data());
+        FRAGDEV_HIP(d_crc.reserve(t8.size() * sizeof(unsigned int)));
+        FRAGDEV_HIP(hipMemcpyAsync(d_crc.p, t8.data(), t8.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipStreamSynchronize(stream));      // t8 is a local
+    }
+    int n_cu = 256;
+    {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+    }
+    const bool timing = getenv("NATAC_FRAG_DEV_TIMING") != nullptr;
+    double t_read = 0, t_scan = 0, t_inflate = 0, t_lines = 0, t_parse = 0, t_out = 0;
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t0 = now();
+    auto lap = [&](double &acc) { const double t = now(); acc += t - t0; t0 = t; };
+    u64 pend = 0;          // carried bytes at the front of d_data[cur_buf]
+    u64 win_start = 0;     // file offset of the window = start of its first member
+    size_t m0 = 0;         // its first member in the chain
+    for (;;) {
+        // ---- the members of this window: as many as fit window_bytes (at least one), once the chain walk has got that far
+        size_t m1 = m0;
+        u64 win_end = win_start;
+        {
+            std::unique_lock<std::mutex> lk(chain.mu);
+            chain.cv.wait(lk, [&]() { return chain.done || (!chain.ends.empty() && chain.ends.back() >= win_start + window_bytes); });
+            if (!chain.error.empty()) { const std::string e = chain.error; lk.unlock(); return give_up(e); }
+            while (m1 < chain.ends.size() && (m1 == m0 || chain.ends[m1] <= win_start + window_bytes)) ++m1;
+            mem.assign(chain.members.begin() + (long)m0, chain.members.begin() + (long)m1);
+            if (m1 > m0) win_end = chain.ends[m1 - 1];
+        }
+        if (mem.empty()) break;                                         // the whole chain is done
+        u64 n = pend;
+        for (auto &mb : mem) { mb.coff -= win_start; mb.uoff = n; n += mb.isize; }
+        const int M = (int)mem.size();
+        const size_t o = (size_t)(win_end - win_start);
+        lap(t_scan);
+        // ---- upload (the read of one staging buffer next to the copy of the other) + inflate of the members that have arrived
+        FRAGDEV_HIP(d_raw.reserve(o + 64));
+        FRAGDEV_HIP(d_mem.reserve(mem.size() * sizeof(Member)));
+        FRAGDEV_HIP(d_data[cur_buf].reserve((size_t)n + 64, (size_t)pend, stream));      // the carry at the front stays
+        unsigned char *data = (unsigned char *)d_data[cur_buf].p;
+        const size_t SUBWIN = (size_t)256 << 20;
+        const int max_launches = (int)(o / SUBWIN) + 2;
+        FRAGDEV_HIP(d_queue.reserve((size_t)max_launches * sizeof(int)));
+        FRAGDEV_HIP(hipMemcpyAsync(d_mem.p, mem.data(), mem.size() * sizeof(Member), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipMemsetAsync(d_status.p, 0, 4 * sizeof(int), stream));
+        FRAGDEV_HIP(hipMemsetAsync(d_queue.p, 0, (size_t)max_launches * sizeof(int), stream));
+        {
+            int which = 0, launched = 0, n_launch = 0;
+            size_t since = 0;
+            for (size_t at = 0; at < o; which ^= 1) {
+                const size_t len = std::min(STAGE, o - at);
+                FRAGDEV_HIP(hipEventSynchronize(staged[which]));         // the copy that used this buffer last has finished
+                {   // four concurrent preads fill the staging buffer, as for a BAM
+                    const int RT = len >= ((size_t)4 << 20) ? 4 : 1;
+                    bool bad[4] = {false, false, false, false};
+                    auto fill = [&](int t) {
+                        size_t a = len * (size_t)t / (size_t)RT;
+                        const size_t b = len * ((size_t)t + 1) / (size_t)RT;
+                        while (a < b) {
+                            const ssize_t r = pread(fd, stage[which] + a, b - a, (off_t)(win_start + at + a));
+                            if (r <= 0) { bad[t] = true; return; }
+                            a += (size_t)r;
+                        }
+                    };
+                    std::thread th[3];
+                    for (int t = 1; t < RT; ++t) th[t - 1] = std::thread(fill, t);
+                    fill(0);
+                    for (int t = 1; t < RT; ++t) th[t - 1].join();
+                    if (bad[0] || bad[1] || bad[2] || bad[3]) return give_up("read error");
+                }
+                FRAGDEV_HIP(hipMemcpyAsync((unsigned char *)d_raw.p + at, stage[which], len, hipMemcpyHostToDevice, stream));
+                FRAGDEV_HIP(hipEventRecord(staged[which], stream));
+                at += len;
+                since += len;
+                if (since >= SUBWIN || at == o) {
+                    int upto = launched;                                // members that lie completely inside the uploaded bytes
+                    while (upto < M && mem[(size_t)upto].coff + mem[(size_t)upto].csize + 8 <= at) ++upto;
+                    if (at == o) upto = M;
+                    if (upto > launched) {
+                        hipStream_t side = aux[n_launch % 3];
+                        FRAGDEV_HIP(hipStreamWaitEvent(side, staged[which], 0));
+                        const int cnt = upto - launched;
+                        hipLaunchKernelGGL(natac_bamdev::bamdev_inflate, dim3((unsigned)std::min<long long>((cnt + 63) / 64, 3ll * n_cu)), dim3(64), 0, side,
+                                           (const unsigned char *)d_raw.p, (const Member *)d_mem.p, launched, upto, data, (int *)d_status.p,
+                                           (int *)d_queue.p + n_launch, (const unsigned int *)d_crc.p);
+                        launched = upto;
+                        ++n_launch;
+                        since = 0;
+                    }
+                }
+            }
+        }
+        lap(t_read);
+        for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamSynchronize(aux[i]));
+        int st[2] = {0, 0};
+        FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
+        FRAGDEV_HIP(hipStreamSynchronize(stream));
+        if (st[0] != 0) return give_up("a BGZF member does not inflate or fails its CRC-32");
+        const bool eof = win_end == fsize;
+        win_start = win_end;
+        m0 = m1;
+        lap(t_inflate);
+        u64 cur = 0;                        // the carry into the next window starts here
+        if (n > 0) {
+            // ---- (a) line index
+            const u64 tiles = (n + TILE_B - 1) / TILE_B;
+            FRAGDEV_HIP(d_tile.reserve((size_t)tiles * sizeof(u64)));
+            hipLaunchKernelGGL(frag_count_nl, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, (const unsigned char *)data, n, (u64 *)d_tile.p);
+            hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_tile.p, tiles, (u64 *)d_total.p);
+            u64 n_nl = 0;
+            unsigned char last_byte = 0;
+            FRAGDEV_HIP(hipMemcpyAsync(&n_nl, d_total.p, sizeof n_nl, hipMemcpyDeviceToHost, stream));
+            FRAGDEV_HIP(hipMemcpyAsync(&last_byte, data + n - 1, 1, hipMemcpyDeviceToHost, stream));
+            FRAGDEV_HIP(hipStreamSynchronize(stream));
+            if (n_nl > n) return give_up("line count out of range");
+            const int open_tail = eof && last_byte != '\n' ? 1 : 0;        // a last line without '\n' is a line
+            const u64 n_lines = n_nl + (u64)open_tail;
+            if (n_lines == 0) return give_up("a window without a line end (a line longer than a window)");
+            {
+                FRAGDEV_HIP(d_ls.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+                u64 *ls = (u64 *)d_ls.p;
+                const u64 zero = 0, behind = n + 1;
+                FRAGDEV_HIP(hipMemcpyAsync(ls, &zero, sizeof zero, hipMemcpyHostToDevice, stream));
+                hipLaunchKernelGGL(frag_line_starts, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, (const unsigned char *)data, n, (const u64 *)d_tile.p, n_nl, ls);
+                if (open_tail) FRAGDEV_HIP(hipMemcpyAsync(ls + n_lines, &behind, sizeof behind, hipMemcpyHostToDevice, stream));
+                FRAGDEV_HIP(hipMemcpyAsync(&cur, ls + n_nl, sizeof cur, hipMemcpyDeviceToHost, stream));
+                lap(t_lines);
+                // ---- (b) parse
+                const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
+                FRAGDEV_HIP(d_code.reserve((size_t)n_lines * sizeof(u64)));
+                FRAGDEV_HIP(d_start.reserve((size_t)n_lines * sizeof(int)));
+                FRAGDEV_HIP(d_end.reserve((size_t)n_lines * sizeof(int)));
+                FRAGDEV_HIP(d_nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
+                FRAGDEV_HIP(d_bsum.reserve((size_t)blocks * sizeof(u64)));
+                hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines, open_tail,
+                                   (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p, (int *)d_status.p);
+                hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_bsum.p, blocks, (u64 *)d_total.p + 1);
+                u64 packed = 0;
+                FRAGDEV_HIP(hipMemcpyAsync(&packed, (u64 *)d_total.p + 1, sizeof packed, hipMemcpyDeviceToHost, stream));
+                FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
+                FRAGDEV_HIP(hipStreamSynchronize(stream));
+                if (st[0] != 0) return give_up("a malformed line");
+                const u64 n_data = packed >> 32, n_runs = packed & 0xffffffffull;
+                if (n_data > n_lines || n_runs > n_data || cur > n) return give_up("counts out of range");
+                if (n_runs > MAX_RUNS) return give_up("more than 65,536 chromosome runs in a window");
+                if (open_tail) cur = n;
+                lap(t_parse);
+                // ---- (c) compaction, the run names, and the append on the host
+                if (n_data) {
+                    FRAGDEV_HIP(d_ostart.reserve((size_t)n_data * sizeof(int)));
+                    FRAGDEV_HIP(d_oend.reserve((size_t)n_data * sizeof(int)));
+                    FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
+                    FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
+                    FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
+                    FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
+                    FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                    hipLaunchKernelGGL(frag_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
+                                       (const int *)d_start.p, (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data,
+                                       (unsigned int)n_runs, (int *)d_ostart.p, (int *)d_oend.p, (u64 *)d_rfirst.p, (u64 *)d_rname.p,
+                                       (unsigned int *)d_rnlen.p, (int *)d_rmax.p);
+                    hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
+                                       (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
+                    h_start.resize(n_data); h_end.resize(n_data);
+                    h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256);
+                    FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipStreamSynchronize(stream));
+                    for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                        const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
+                        if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
+                        pos.resize((size_t)(b - a));
+                        tlen.resize((size_t)(b - a));
+                        for (u64 i = a; i < b; ++i) {
+                            pos[(size_t)(i - a)] = (int64_t)h_start[(size_t)i] - 4;
+                            tlen[(size_t)(i - a)] = (int64_t)h_end[(size_t)i] - (int64_t)h_start[(size_t)i] + 8;
+                        }
+                        natac_fragio::append_run(bd, std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), pos.data(), tlen.data(), (size_t)(b - a),
+                                                 h_rmax[r]);
+                    }
+                }
+            }
+        }
+        // ---- carry the bytes behind the last '\n' to the front of the other buffer
+        pend = n - cur;
+        FRAGDEV_HIP(d_data[cur_buf ^ 1].reserve((size_t)pend + 64));
+        if (pend) FRAGDEV_HIP(hipMemcpyAsync(d_data[cur_buf ^ 1].p, data + cur, (size_t)pend, hipMemcpyDeviceToDevice, stream));
+        FRAGDEV_HIP(hipStreamSynchronize(stream));
+        cur_buf ^= 1;
+        lap(t_out);
+        if (eof) break;
+    }
+    if (timing)
+        std::fprintf(stderr, "[natac_frag_dev] read + upload %.3f s, waiting for the member chain %.3f, inflate %.3f, line index %.3f, parse %.3f, compaction + append + carry %.3f\n",
+                     t_read, t_scan, t_inflate, t_lines, t_parse, t_out);
+#undef FRAGDEV_HIP
+    if (pend != 0) return give_up("bytes left behind the last window");
+    cleanup();
+    return bam;
+}
+
+}  // namespace natac_fragdev

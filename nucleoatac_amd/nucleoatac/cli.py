@@ -7,7 +7,7 @@ import sys
 def add_occ_parser(sub):
     p = sub.add_parser("occ", help="Call nucleosome occupancy")
     p.add_argument("--bed", required=True, help="Peaks in bed format")
-    p.add_argument("--bam", required=True, help="Sorted BAM file (or a FragmentStore .npz)")
+    p.add_argument("--bam", required=True, help="Sorted reads: BAM, fragment file or FragmentStore .npz")
     p.add_argument("--out", required=True, help="output basename")
     p.add_argument("--fasta", help="genome fasta (if absent, bias is not calculated)")
     p.add_argument("--pwm", default="Human", help="Tn5 PWM name or descriptor file")
@@ -25,7 +25,7 @@ def add_nuc_parser(sub):
     p = sub.add_parser("nuc", help="Call nucleosome positions and make signal tracks")
     p.add_argument("--bed", required=True)
     p.add_argument("--vmat", required=True, help="VMat file (text descriptor or .npz)")
-    p.add_argument("--bam", required=True)
+    p.add_argument("--bam", required=True, help="Sorted reads: BAM, fragment file or FragmentStore .npz")
     p.add_argument("--out", required=True)
     p.add_argument("--fasta")
     p.add_argument("--pwm", default="Human")
@@ -68,7 +68,7 @@ def add_nfr_parser(sub):
     p.add_argument("--occ_track", required=True, help="bgzip compressed, tabix-indexed bedgraph file with occupancy track")
     p.add_argument("--calls", required=True, help="bed file with nucleosome center calls")
     p.add_argument("--ins_track", help="insertion track; generated from --bam if not included")
-    p.add_argument("--bam")
+    p.add_argument("--bam", help="Sorted reads: BAM, fragment file or FragmentStore .npz")
     p.add_argument("--fasta")
     p.add_argument("--pwm", default="Human")
     p.add_argument("--out")
@@ -80,7 +80,7 @@ def add_nfr_parser(sub):
 def add_run_parser(sub):
     p = sub.add_parser("run", help="Main nucleoatac utility -- occupancy determination & calling nuc positions")
     p.add_argument("--bed", required=True)
-    p.add_argument("--bam", required=True)
+    p.add_argument("--bam", required=True, help="Sorted reads: BAM, fragment file or FragmentStore .npz")
     p.add_argument("--out", required=True)
     p.add_argument("--fasta", required=True)
     p.add_argument("--pwm", default="Human")

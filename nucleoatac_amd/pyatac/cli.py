@@ -11,7 +11,7 @@ import sys
 def add_pwm_parser(sub):
     p = sub.add_parser("pwm", help="pyatac function-- get nucleotide content around insertion sites")
     p.add_argument("--fasta", required=True, help="Accepts fasta file")
-    p.add_argument("--bam", required=True, help="Reads around which to get nucleotide freq (BAM or a FragmentStore .npz)")
+    p.add_argument("--bam", required=True, help="Reads around which to get nucleotide freq (BAM, fragment file or FragmentStore .npz)")
     p.add_argument("--bed", help="Regions from which to use reads")
     p.add_argument("--dinucleotide", action="store_true", default=False, help="accepted for compatibility; ignored, like the reference")
     p.add_argument("--flank", type=int, default=10, help="Bases away from insertion site to get frequencies for. Default is 10")
@@ -25,7 +25,7 @@ def add_pwm_parser(sub):
 
 def add_sizes_parser(sub):
     p = sub.add_parser("sizes", help="pyatac function-- compute fragment size distribution")
-    p.add_argument("--bam", required=True, help="Aligned reads (BAM or a FragmentStore .npz)")
+    p.add_argument("--bam", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
     p.add_argument("--bed", help="Only compute size distribution for fragment centered within regions in bed file")
     p.add_argument("--out", help="Basename for output")
     p.add_argument("--not_atac", dest="atac", action="store_false", default=True, help="Don't use atac offsets")
@@ -35,7 +35,7 @@ def add_sizes_parser(sub):
 
 
 def _add_track_options(p):
-    p.add_argument("--bam", metavar="bam_file", required=True, help="Accepts sorted BAM file (or a FragmentStore .npz)")
+    p.add_argument("--bam", metavar="bam_file", required=True, help="Sorted reads (BAM, fragment file or FragmentStore .npz)")
     p.add_argument("--bed", metavar="bed_file", help="Regions in which to get insertions")
     p.add_argument("--out", metavar="basename")
     p.add_argument("--cores", metavar="int", default=1, type=int, help="accepted for compatibility; the GPU replaces the pool")
@@ -72,7 +72,7 @@ def add_bias_parser(sub):
 
 def add_counts_parser(sub):
     p = sub.add_parser("counts", help="pyatac function-- compute fragment counts within windows")
-    p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM or a FragmentStore .npz)")
+    p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
     p.add_argument("--bed", metavar="bed_file", required=True, help="Windows in which to compute counts")
     p.add_argument("--out", metavar="output_basename", help="Basename for output")
     p.add_argument("--not_atac", action="store_false", dest="atac", default=True, help="Don't use atac offsets")

@@ -4,7 +4,8 @@ The reference re-opens the BAM and iterates `AlignmentFile.fetch` inside every c
 Here the alignment file is decoded ONCE into a FragmentStore (per chromosome: sorted leftmost positions and
 template lengths of the forward proper-pair reads, which are the only reads the reference keeps,
 fragments.pyx:25); the extractor functions keep the reference's names and argument order -- `bamfile` may be a
-FragmentStore or a path (.bam / .npz) -- and run on the GPU through the C-ABI.
+FragmentStore or a path (.bam / .npz, or a fragment file: .tsv / .tsv.gz / .bed / .bed.gz) -- and run on the GPU through the
+C-ABI.
 """
 import gzip
 import os
@@ -14,6 +15,11 @@ import numpy as np
 
 _CACHE = {}
 _PENDING = {}     # src -> (thread, result box) of FragmentStore.prefetch
+FRAGMENT_SUFFIXES = (".tsv", ".tsv.gz", ".bed", ".bed.gz")      # names FragmentStore._load reads as fragment files
+# the fixed reason per cause of a malformed fragment line (csrc/natac_fragfile.hpp: reason_text)
+_FRAG_REASONS = dict(fields="fewer than three tab-separated fields", empty="empty chromosome name",
+                     long="chromosome name longer than 255 bytes", number="start / end is not a number",
+                     range="start / end out of range (more than 2147483647)", order="end before start")
 
 
 class FragmentStore(object):
@@ -45,7 +51,7 @@ class FragmentStore(object):
         if isinstance(src, FragmentStore) or src in _CACHE or src in _PENDING:
             return
         import threading
-        if os.environ.get("NATAC_DEVICE_BAM", "1") != "0" and str(src).endswith(".bam"):
+        if os.environ.get("NATAC_DEVICE_BAM", "1") != "0" and str(src).endswith((".bam",) + FRAGMENT_SUFFIXES):
             from .. import get_context
             from ..device import Context
             if Context.device_count() > 0:
@@ -82,8 +88,11 @@ class FragmentStore(object):
             st = FragmentStore.from_npz(src)
         elif src.endswith(".bam"):
             st = FragmentStore.from_bam(src)
+        elif src.endswith(FRAGMENT_SUFFIXES):
+            st = FragmentStore.from_fragments(src)
         else:
-            raise ValueError("unsupported alignment source %r (expected FragmentStore, .bam or .npz)" % (src,))
+            raise ValueError("unsupported alignment source %r (expected FragmentStore, .bam, .npz or a fragment file: %s)"
+                             % (src, ", ".join(FRAGMENT_SUFFIXES)))
         return st
 
     @staticmethod
@@ -128,6 +137,13 @@ class FragmentStore(object):
         else:
             L.check(lib.natac_bam_open(str(path).encode(), int(n_threads), C.byref(h)))
             FragmentStore.last_bam_on_device = False
+        return FragmentStore._from_handle(lib, h)
+
+    @staticmethod
+    def _from_handle(lib, h):
+        """the per-reference arrays of a natac_bam handle (natac_bam_open* / natac_frag_open*); closes the handle"""
+        import ctypes as C
+        from .. import _lib as L
         try:
             nref = C.c_int32(0)
             L.check(lib.natac_bam_counts(h, C.byref(nref), None, None))
@@ -137,6 +153,8 @@ class FragmentStore(object):
                 ln, nr = C.c_int64(0), C.c_int64(0)
                 L.check(lib.natac_bam_ref_info(h, r, name, 512, C.byref(ln), C.byref(nr)))
                 c = name.value.decode()
+                if c in pos:
+                    raise ValueError("two chromosomes read as %r" % (c,))      # (fragment-file names that differ only behind a NUL byte)
                 p = np.empty(nr.value, dtype=np.int64)
                 t = np.empty(nr.value, dtype=np.int64)
                 L.check(lib.natac_bam_ref_reads(h, r, p.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), nr.value))
@@ -146,6 +164,117 @@ class FragmentStore(object):
         finally:
             lib.natac_bam_close(h)
         return FragmentStore(names, lens, pos, tl)
+
+    @staticmethod
+    def from_fragments(path, n_threads=0, device=None):
+        """A fragment file (fragments.tsv.gz of Cell Ranger ATAC, the ENCODE pipeline, chromap, sinto, SnapATAC / ArchR) read by the
+        native decoder.  The format rule (include/natac.h states it, csrc/natac_fragfile.hpp: parse_line is it):
+
+        - lines end in "\\n", a "\\r" directly before it is dropped, a last line without "\\n" is a line; empty lines and lines
+          whose first byte is "#" (the 10x header) are skipped;
+        - every other line is a data line: TAB-separated, at least three fields, fields after the third ignored whatever they hold
+          (barcode, duplicate count: one line is one fragment, identical lines are separate fragments); chrom is 1-255 bytes, start
+          and end are 1-10 ASCII digits without sign or blanks, at most 2**31 - 1, end >= start;
+        - [start, end) is taken as the insertion-to-insertion interval the reference's ATAC offsets produce
+          (pyatac/fragments.pyx:26-31: l = start, ilen = end - start): the stored record is pos = start - 4 (may be negative),
+          tlen = end - start + 8; end == start is kept.  Files written with the +4/-5 convention are one base shorter at the right
+          end than the reference's +4/-4 reading of the same BAM; nothing is corrected, because the writer's convention is not
+          recorded in the file;
+        - chromosomes are numbered in order of first appearance (one that comes back later keeps its id); there is no sequence
+          dictionary, so a chromosome's length is the largest end on it (commands given --fasta take sizes from the FASTA);
+        - a malformed data line raises "<path>: line <N>: <reason>" (N 1-based, counting skipped lines), nothing is returned.
+
+        The container goes by magic bytes: BGZF, any other gzip, plain text.  On a GPU box a BGZF file goes through
+        natac_frag_open_device (csrc/natac_fragfile_dev.hpp): the members are staged and inflated as a BAM's, then the text is split
+        into lines, parsed and compacted on the device; FragmentStore.last_frag_on_device tells whether the device answered (the host
+        decoder answers inside the call for another container, a malformed line, a damaged file, a line longer than a window, more
+        than 65,536 chromosome runs in a window).  Without a GPU, or with device=False / NATAC_DEVICE_BAM=0: natac_frag_open, parallel
+        inflate and parse over line-aligned slices on the host cores.  Both give the same arrays.
+        Measured on the MI355X box (tools/bench_bam.py 20000000 --fragments, one box): a 20 M-record BAM's 10.0 M kept reads as a fragment
+        file (436 MB of text, 129 MB BGZF): device 0.15 s; host 0.26 s with 16 threads, 0.50 s with 4; the device decode of the BAM itself
+        (1.25 GB) 0.28 s."""
+        import ctypes as C
+        from .. import _lib as L
+        lib = L.load()
+        h = C.c_void_p()
+        if device is None:
+            from ..device import Context
+            device = os.environ.get("NATAC_DEVICE_BAM", "1") != "0" and Context.device_count() > 0
+        if device:
+            from .. import get_context
+            on_dev = C.c_int(0)
+            L.check(lib.natac_frag_open_device(get_context()._h, str(path).encode(), C.byref(h), C.byref(on_dev)))
+            FragmentStore.last_frag_on_device = bool(on_dev.value)
+        else:
+            L.check(lib.natac_frag_open(str(path).encode(), int(n_threads), C.byref(h)))
+            FragmentStore.last_frag_on_device = False
+        return FragmentStore._from_handle(lib, h)
+
+    @staticmethod
+    def from_fragments_python(path):
+        """pure-Python restatement of the format rule of from_fragments, kept as an independent check of the native decoders"""
+        with open(path, "rb") as fh:
+            zipped = fh.read(2) == b"\x1f\x8b"
+        with (gzip.open if zipped else open)(path, "rb") as fh:
+            lines = fh.read().split(b"\n")
+        open_end = lines[-1] != b""          # the last line has no "\n" (and keeps a "\r")
+        if not open_end:
+            lines.pop()
+        names, pos, tl, length = [], {}, {}, {}
+
+        def bad(no, why):
+            return ValueError("%s: line %d: %s" % (path, no, _FRAG_REASONS[why]))
+
+        def coord(no, b):
+            if not b or not b.isdigit():
+                raise bad(no, "number")
+            if len(b) > 10 or int(b) > 2 ** 31 - 1:
+                raise bad(no, "range")
+            return int(b)
+        for no, line in enumerate(lines, 1):
+            if line.endswith(b"\r") and not (open_end and no == len(lines)):
+                line = line[:-1]
+            if not line or line[:1] == b"#":
+                continue
+            f = line.split(b"\t")
+            if len(f) < 3:
+                raise bad(no, "fields")
+            if not f[0]:
+                raise bad(no, "empty")
+            if len(f[0]) > 255:
+                raise bad(no, "long")
+            start = coord(no, f[1])
+            end = coord(no, f[2])
+            if end < start:
+                raise bad(no, "order")
+            c = f[0].decode()
+            if c not in pos:
+                names.append(c)
+                pos[c], tl[c], length[c] = [], [], 0
+            pos[c].append(start - 4)
+            tl[c].append(end - start + 8)
+            length[c] = max(length[c], end)
+        return FragmentStore(names, [length[c] for c in names], {c: np.array(pos[c], np.int64) for c in names},
+                             {c: np.array(tl[c], np.int64) for c in names})
+
+    def save_fragments(self, path):
+        """write the store as a fragment file (chrom, start = pos + 4, end = pos + tlen - 4 per line, in the store's order: chromosome
+        by chromosome, sorted by start), BGZF-compressed by natac_bgzip_file with its .tbi by natac_tabix_index: a BAM converted once
+        reads back as the same pos / tlen arrays through from_fragments"""
+        from ..writer import bgzip_file, tabix_index
+        tmp = str(path) + ".tmp"
+        with open(tmp, "w") as fh:
+            for c in self.references:
+                start, end = self.pos[c] + 4, self.pos[c] + self.tlen[c] - 4
+                if len(start) and (int(start.min()) < 0 or bool(np.any(end < start)) or int(end.max()) > 2 ** 31 - 1):
+                    os.remove(tmp)
+                    raise ValueError("%s holds a read a fragment line cannot carry (pos < -4, |tlen| < 8 or an end beyond 2**31 - 1)" % c)
+                row = c + "\t%d\t%d\n"
+                for o in range(0, len(start), 1 << 16):
+                    fh.write("".join([row % se for se in zip(start[o:o + (1 << 16)].tolist(), end[o:o + (1 << 16)].tolist())]))
+        bgzip_file(tmp, str(path))
+        tabix_index(str(path))
+        return str(path)
 
     @staticmethod
     def from_bam_python(path):

@@ -1,6 +1,8 @@
 """Throughput of the native BAM extractor (csrc/natac_bam.hpp: natac_bam_open decodes every record, keeps the forward reads of
 proper pairs) on a synthetic coordinate-sorted BAM of N paired-end records with realistic record sizes (50-base reads, names of
-~20 characters, one 50M cigar; BGZF members of 0xff00 bytes at zlib level 6 like samtools):  python tools/bench_bam.py 4000000"""
+~20 characters, one 50M cigar; BGZF members of 0xff00 bytes at zlib level 6 like samtools):  python tools/bench_bam.py 4000000
+With --fragments, after the BAM run: the fragment file of the same BAM's kept reads (chrom, start, end, a 16-base barcode, a count; the
+same members and level) through natac_frag_open_device and through natac_frag_open at 16 and at 4 threads, on the same box."""
 import os
 import struct
 import sys
@@ -43,8 +45,11 @@ def synth_bam(path, n, n_refs=4, ref_len=50_000_000, seed=0):
     a["cigar"] = seq_len << 4
     a["seq"] = rng.integers(0, 256, (n, (seq_len + 1) // 2), dtype=np.uint8)
     a["qual"] = rng.integers(20, 41, (n, seq_len), dtype=np.uint8)
-    data = b"".join(head) + a.tobytes()
+    bgzf_write(path, b"".join(head) + a.tobytes())
+    return a.nbytes + sum(len(h) for h in head), int(fwd.sum())
 
+
+def bgzf_write(path, data):
     def member(o):
         chunk = data[o:o + 0xff00]
         co = zlib.compressobj(6, zlib.DEFLATED, -15)
@@ -55,11 +60,40 @@ def synth_bam(path, n, n_refs=4, ref_len=50_000_000, seed=0):
         for m in pool.map(member, range(0, len(data), 0xff00)):
             f.write(m)
         f.write(bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
-    return len(data), int(fwd.sum())
+
+
+def bench_fragments(d, store):
+    """the fragment file of `store` (what the BAM run decoded): device twice (the first call pays the first launches), host at 16 and 4"""
+    from nucleoatac_amd.device import Context
+    from nucleoatac_amd.pyatac.fragments import FragmentStore
+    rng = np.random.default_rng(1)
+    parts = [b"# id=bench\n"]
+    for c in store.references:
+        start, end = (store.pos[c] + 4).tolist(), (store.pos[c] + store.tlen[c] - 4).tolist()
+        bc = rng.integers(0, 4, (len(start), 16), dtype=np.uint8)
+        bc = np.frombuffer(b"ACGT", dtype=np.uint8)[bc].view("S16").ravel().tolist()
+        row = c.encode() + b"\t%d\t%d\t%s-1\t1\n"
+        parts.append(b"".join([row % t for t in zip(start, end, bc)]))
+    text = b"".join(parts)
+    path = os.path.join(d, "fragments.tsv.gz")
+    bgzf_write(path, text)
+    size, n = os.path.getsize(path), sum(len(store.pos[c]) for c in store.references)
+    print("fragment file: %d lines, %.0f MB of text, %.0f MB compressed" % (n, len(text) / 1e6, size / 1e6))
+    modes = ([(0, True), (0, True)] if Context.device_count() > 0 else []) + [(16, False), (4, False)]
+    for threads, device in modes:
+        t0 = time.perf_counter()
+        st = FragmentStore.from_fragments(path, n_threads=threads, device=device)
+        dt = time.perf_counter() - t0
+        if device:
+            threads = "device" if FragmentStore.last_frag_on_device else "device->host"
+        same = all(np.array_equal(st.pos[c], store.pos[c]) and np.array_equal(st.tlen[c], store.tlen[c]) for c in st.references)
+        print("fragments threads=%s  %d lines (same arrays as the BAM: %s): %.2f s = %.1f M lines/s, %.0f MB/s compressed, %.0f MB/s inflated"
+              % (threads, n, same, dt, n / dt / 1e6, size / dt / 1e6, len(text) / dt / 1e6))
 
 
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 4_000_000
+    args = [a for a in sys.argv[1:] if a != "--fragments"]
+    n = int(args[0]) if args else 4_000_000
     from nucleoatac_amd.pyatac.fragments import FragmentStore
     d = tempfile.mkdtemp(prefix="natac_bam_")
     path = os.path.join(d, "synth.bam")
@@ -84,6 +118,8 @@ def main():
             total = sum(len(st.pos[c]) for c in st.pos) if hasattr(st, "pos") else -1
             print("threads=%s  %d records, %d kept (expected %d): %.2f s = %.1f M records/s, %.0f MB/s compressed, %.0f MB/s inflated"
                   % (threads or "auto", n, total, kept, dt, n / dt / 1e6, size / dt / 1e6, raw / dt / 1e6))
+        if "--fragments" in sys.argv:
+            bench_fragments(d, st)
     finally:
         import shutil
         shutil.rmtree(d, ignore_errors=True)
