@@ -124,6 +124,26 @@ int natac_ctx_device_info(natac_ctx *ctx, char *name, size_t name_len, int *n_cu
 int natac_ctx_device_ids(natac_ctx *ctx, int *hip_device, char *pci_bus_id, size_t pci_len);
 
 /* ---- run-level constants --------------------------------------------------------------- */
+/* The three setters below may be called again at any time on a context that has run, with batches alive.  They wait for the
+ * context's stream.  Two rules hold afterwards (tests/test_gpu_model_changes.py):
+ *
+ * A. Re-run equivalence.  After any sequence of natac_set_vmat, natac_set_sizes, natac_set_occ_model and changes of smooth_sd, a
+ *    stage run on a live batch gives bit for bit what a fresh context and a fresh batch give for the same model and the same order
+ *    of calls: tracks, grids, status words, peaks and statistics.  Everything the context and the batch keep between calls is a
+ *    table derived from the model or from the batch's geometry, keyed on what it was derived from.  Each stage owns one bit of
+ *    the status words and drops it before it launches (natac_batch_status), so a bit never outlives the run that raised it.
+ *
+ * B. No silent mixing.  A call that combines what an earlier stage left on the batch with the context's model takes the context's
+ *    values and requires the geometry the stage ran with; it fails with NATAC_E_STATE, before any device work, when the geometry
+ *    differs.  Setting a model of the same geometry again between a stage and its consumers is always allowed.
+ *      natac_run_candidates, natac_run_candidates_cov, natac_run_peaks: the V-plot's (lower, upper, w) must be natac_run_nuc's.
+ *        The template, the sizes and hence the statistics are those of the model that is set now.
+ *      NATAC_T_OCC_PREFILL while it is still to be formed (any reader: download, track_ptr, format_track, natac_store_adopt) and
+ *        natac_run_occ_peaks: (step, flank, upper) must be natac_run_occ's; the alpha grid, the cutoff and the probabilities may
+ *        differ, none of these reads them.
+ *    Tracks that are already formed (NATAC_T_BACKGROUND included: it is formed from what natac_run_nuc left, not from the model),
+ *    the grids and the peaks of an earlier search stay readable as the run left them.  Outputs that only natac_batch_set_track
+ *    wrote carry no geometry.  After a refusal, running the stage again is all it takes. */
 /* VMat template (pyatac/VMat.py:24-37): mat[(upper-lower) x (2w+1)] row-major, insert sizes [lower,upper). */
 int natac_set_vmat(natac_ctx *ctx, const double *mat, int lower, int upper, int w);
 /* global insert-size distribution over [0, upper) used by BiasMat2D.normByInsertDist (chunkmat2d.py:154-156). */
@@ -240,7 +260,10 @@ int natac_batch_download_grid(natac_batch *b, int which, double *dst, size_t dst
  * natac_run_nuc computed as it was; natac_run_occ then takes OCC_COV from the fragments, not from host-written coverage. */
 int natac_batch_set_track(natac_batch *b, int track, const double *vals, size_t n);
 /* per-chunk status flags (int32[n_chunks]; 0 = ok, bit0 = occupancy likelihood undefined at some grid point
- * -- the reference would raise ValueError at Occupancy.py:118). */
+ * -- the reference would raise ValueError at Occupancy.py:118 --, bit1 = a peak search truncated the chunk's list of maxima).
+ * Bit 0 is natac_run_occ's and describes its last run; bit 1 describes the last peak search (natac_run_peaks,
+ * natac_run_track_peaks, natac_run_occ_peaks): each drops its bit for every chunk before it launches and leaves the other alone.
+ * natac_batch_release_outputs clears both. */
 int natac_batch_status(natac_batch *b, int32_t *dst, size_t dst_bytes);
 /* raw device pointer of a per-base track (for zero-copy consumers); NULL if the track holds nothing (NATAC_E_STATE above). */
 int natac_batch_track_ptr(natac_batch *b, int track, void **dptr);

@@ -164,8 +164,10 @@ struct BatchOutputs {
     TrackState track[NATAC_T_COUNT] = {};
     bool grids = false;               // d_grid written by natac_run_occ
     long long bg_gen = -1;            // model generation d_bnum / d_bcov were formed with (natac_run_nuc); -1: none
-    int nuc_w = -1, nuc_upper = -1;   // V-plot geometry natac_run_nuc ran with (the coverage tracks depend on it)
+    int nuc_w = -1, nuc_lower = -1, nuc_upper = -1;   // V-plot geometry natac_run_nuc ran with (its tracks depend on it); -1: no run
     bool occ_cov_by_nuc = false;      // OCC_COV holds natac_run_nuc's nuc_cov + nfr_cov for that geometry
+    // occupancy geometry natac_run_occ ran with (the grids and the OCC tracks depend on it); -1: no run
+    int occ_step = -1, occ_half = -1, occ_flank = -1, occ_upper = -1;
 };
 
 struct natac_batch {
@@ -225,6 +227,25 @@ struct natac_batch {
     std::vector<std::string> fmt_names;
     long long fmt_text_bytes = 0;
 };
+
+// Contract B of natac.h: a call that combines what an earlier stage left on the batch with the context's model goes on only while
+// the context holds the geometry that stage ran with; NATAC_E_STATE otherwise, before any HIP call.  Values may differ (the readers
+// below take none of them from the earlier run's model).  Outputs no stage wrote (natac_batch_set_track alone) carry no geometry.
+static int need_nuc_geometry(const natac_batch *b, const char *who) {
+    const natac_ctx *c = b->ctx;
+    const BatchOutputs &o = b->out;
+    if (o.nuc_w < 0 || (o.nuc_w == c->vw && o.nuc_lower == c->vlower && o.nuc_upper == c->vupper)) return NATAC_OK;
+    return fail(NATAC_E_STATE, "%s: natac_run_nuc ran with the V-plot geometry lower=%d upper=%d w=%d, the context now holds lower=%d "
+                "upper=%d w=%d: run natac_run_nuc again", who, o.nuc_lower, o.nuc_upper, o.nuc_w, c->vlower, c->vupper, c->vw);
+}
+static int need_occ_geometry(const natac_batch *b, const char *who) {
+    const natac_ctx *c = b->ctx;
+    const BatchOutputs &o = b->out;
+    if (o.occ_step < 0 || (o.occ_step == c->step && o.occ_half == c->halfstep && o.occ_flank == c->flank && o.occ_upper == c->occ_upper))
+        return NATAC_OK;
+    return fail(NATAC_E_STATE, "%s: natac_run_occ ran with step=%d flank=%d upper=%d, the context now holds step=%d flank=%d upper=%d: "
+                "run natac_run_occ again", who, o.occ_step, o.occ_flank, o.occ_upper, c->step, c->flank, c->occ_upper);
+}
 
 static hipError_t sync_all(natac_ctx *c) { return hipStreamSynchronize(c->stream); }
 
@@ -1386,7 +1407,11 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
         b->ranges256_w = c->vw;
     }
     // OccChunk.getCov = nuc_cov + nfr_cov when the occupancy model's window / size range are the V-plot's: written here too
-    const bool cov_too = c->have_occ && c->flank == c->vw && c->occ_upper == c->vupper;
+    // -- unless OCC_COV holds what another writer left (natac_run_occ under another window, natac_batch_set_track) or what this stage
+    // wrote for another window or size range: that stays readable as it is, and the next natac_run_occ forms the sum itself
+    const bool cov_mine = b->out.occ_cov_by_nuc && b->out.nuc_w == c->vw && b->out.nuc_upper == c->vupper;
+    const bool cov_too = c->have_occ && c->flank == c->vw && c->occ_upper == c->vupper &&
+                         (b->out.track[NATAC_T_OCC_COV] == TS_EMPTY || cov_mine);
     if (cov_too && (rc = ensure_track(b, NATAC_T_OCC_COV))) return rc;
     constexpr int GNBL = NATAC_GNBL;      // adjacent bases per lane: 2.  Round 5, lanes outside a window reading one shared zero line:
                                           // 0.63 ms per 20 k chunks against 0.79 with 4 and 0.85 with 1 (round 2: 3.5 / 4.5 / 3.8 ms per step)
@@ -1434,6 +1459,7 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     b->out.track[NATAC_T_BACKGROUND] = use_fft ? TS_PENDING : TS_RUN;
     b->out.bg_gen = c->model_gen;
     b->out.nuc_w = c->vw;
+    b->out.nuc_lower = c->vlower;
     b->out.nuc_upper = c->vupper;
     b->out.occ_cov_by_nuc = cov_too;     // OCC_COV itself becomes readable through natac_run_occ only
     return NATAC_OK;
@@ -1509,6 +1535,8 @@ static int materialise_prefill(natac_batch *b) {
     natac_ctx *c = b->ctx;
     int rc = ensure_track(b, NATAC_T_OCC_PREFILL);
     if (rc) return rc;
+    // the context's step, halfstep and flank are the run's (need_track); its window may be another batch's by now
+    if ((rc = ensure_window(c, c->d_win_occ, &c->win_occ_M, &c->win_occ_sd, 2 * c->flank + 1, c->flank / 3.0))) return rc;
     const ChunkTable ct = make_table(b);
     const OccModelDev om = make_occ(c);
     launch_occ_smooth_generic(b, ct, om, 2 * c->flank + 1, b->d_track[NATAC_T_OCC_PREFILL], nullptr, nullptr);
@@ -1525,6 +1553,10 @@ static int need_track(natac_batch *b, int t) {
     if (b->out.track[t] == TS_EMPTY)
         return fail(NATAC_E_STATE, "track NATAC_T_%s holds nothing: no stage has written it and natac_batch_set_track has not", names[t]);
     if (b->out.track[t] != TS_PENDING) return NATAC_OK;
+    if (t == NATAC_T_OCC_PREFILL) {      // formed from the grids with the context's step and window: they must be the run's
+        const int rc = need_occ_geometry(b, "NATAC_T_OCC_PREFILL");
+        if (rc) return rc;
+    }
     HIPCHK(hipSetDevice(b->ctx->device));
     return t == NATAC_T_BACKGROUND ? materialise_bg(b) : materialise_prefill(b);
 }
@@ -1554,6 +1586,9 @@ static int occ_prepare(natac_batch *b) {
         }
         b->total_grid = b->h_grid_off[b->nc];
         HIPCHK(sync_all(c));
+        // the grids of the earlier run go with their layout, whatever becomes of this call
+        b->out.grids = false;
+        if (b->out.track[NATAC_T_OCC_PREFILL] == TS_PENDING) b->out.track[NATAC_T_OCC_PREFILL] = TS_EMPTY;
         if ((rc = dev_upload(c, b->d_grid_off, b->h_grid_off.data(), (size_t)b->nc + 1))) return rc;
         for (auto &g : b->d_grid)
             if ((rc = dev_alloc(g, (size_t)b->total_grid))) return rc;
@@ -1639,6 +1674,8 @@ static int occ_launch(natac_batch *b) {
     natac_ctx::Ev ev;
     const bool fast = c->occ_fast_ok && !c->occ_force_general;
     prof_begin(c, NATAC_K_OCC_MLE, ev, c->stream);
+    // bit 0 of the status words is this stage's: what an earlier run under another model raised does not outlive it
+    hipLaunchKernelGGL(natac_status_clear, dim3((b->nc + 255) / 256), dim3(256), 0, c->stream, b->d_status, b->nc, 1);
     {
         const int U = c->occ_upper, UP = (U + 1) & ~1;
         const int span = (OCC_T * OCC_NP - 1) * c->step + M + c->step;
@@ -1737,6 +1774,7 @@ static int occ_launch(natac_batch *b) {
     for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV}) b->out.track[t] = TS_RUN;
     b->out.track[NATAC_T_OCC_PREFILL] = blk ? TS_PENDING : TS_RUN;
     b->out.grids = true;
+    b->out.occ_step = c->step; b->out.occ_half = c->halfstep; b->out.occ_flank = c->flank; b->out.occ_upper = c->occ_upper;
     return NATAC_OK;
 }
 
@@ -1881,7 +1919,7 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     natac_ctx *c = b->ctx;
     int rc = need_candidate_inputs(b);
-    if (rc) return rc;
+    if (rc || (rc = need_nuc_geometry(b, "natac_run_candidates"))) return rc;
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !lr || !var || !z))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
     if (n_cand > 0x7fffffffLL) return fail(NATAC_E_ARG, "too many candidates");
@@ -1892,6 +1930,7 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
         if (ci < 0 || ci >= b->nc || cand_pos[k] < 0 || cand_pos[k] >= b->h_len[ci])
             return fail(NATAC_E_ARG, "candidate %lld out of range (chunk %d pos %d)", (long long)k, ci, cand_pos[k]);
     }
+    if ((rc = ensure_srow(c))) return rc;      // the size weights of the model that is set now, whichever call set it
     const int *d_cc = dc.upload(cand_chunk, (size_t)n_cand), *d_cp = dc.upload(cand_pos, (size_t)n_cand);
     double *d_out = dc.alloc<double>((size_t)3 * n_cand);
     if (dc.ok()) {
@@ -1916,18 +1955,18 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     natac_ctx *c = b->ctx;
     int rc = need_track(b, NATAC_T_NUC_COV);
-    if (rc) return rc;
+    if (rc || (rc = need_nuc_geometry(b, "natac_run_candidates_cov"))) return rc;
     if (mode < 0 || mode > 2) return fail(NATAC_E_ARG, "mode must be 0 (closed form), 1 (literal) or 2 (closed form in fp32)");
     if (n_cand < 0 || (n_cand > 0 && (!cand_chunk || !cand_pos || !var))) return fail(NATAC_E_ARG, "null argument");
     if (n_cand == 0) return NATAC_OK;
     DeviceCall dc(c, "candidates_cov");
     if (!dc.ok()) return dc.finish();
-    if ((rc = ensure_srow(c))) return rc;
     for (int64_t k = 0; k < n_cand; ++k) {
         const int ci = cand_chunk[k];
         if (ci < 0 || ci >= b->nc || cand_pos[k] < 0 || cand_pos[k] >= b->h_len[ci])
             return fail(NATAC_E_ARG, "candidate %lld out of range (chunk %d pos %d)", (long long)k, ci, cand_pos[k]);
     }
+    if ((rc = ensure_srow(c))) return rc;
     const int N = c->R * c->W;
     const int NBLK = 64;                       // row groups of the literal pair sum per candidate
     const int64_t SLAB = 2048;                 // candidates per pass: 2048 x N doubles = 289 MB for the default V-plot
@@ -1993,6 +2032,7 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
     int rc;
+    if (with_stats && (rc = ensure_srow(c))) return rc;      // as natac_run_candidates
     if (!b->d_jitter || b->n_jitter < maxL) {
         if ((rc = dev_upload(c, b->d_jitter, jitter, (size_t)maxL))) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -2017,6 +2057,8 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     const double *norm = sig_a, *sm = sig_b;
     natac_ctx::Ev ev;
     prof_begin(c, NATAC_K_CAND, ev);
+    // bit 1 of the status words belongs to the peak search: it describes this one
+    hipLaunchKernelGGL(natac_status_clear, dim3((b->nc + 255) / 256), dim3(256), 0, c->stream, b->d_status, b->nc, 2);
     {   // one workgroup per chunk: LDS = the jittered signal (or a segment of it) + the chunk's list of maxima
         const int pk_cap = (std::min(PEAK_MAX, maxL / (order + 1) + 2) + 7) & ~7;
         const size_t lds_lists = (size_t)pk_cap * (sizeof(double) + sizeof(int) + 1);
@@ -2103,7 +2145,7 @@ int natac_run_peaks(natac_batch *b, double min_signal, int sep, int boundary, in
                     int64_t *n_cand) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     int rc;
-    if ((rc = need_track(b, NATAC_T_SMOOTH)) || (rc = need_candidate_inputs(b))) return rc;
+    if ((rc = need_track(b, NATAC_T_SMOOTH)) || (rc = need_candidate_inputs(b)) || (rc = need_nuc_geometry(b, "natac_run_peaks"))) return rc;
     return run_peaks_impl(b, b->d_track[NATAC_T_NORM], b->d_track[NATAC_T_SMOOTH], true, min_signal, sep, boundary, order, jitter,
                           n_jitter, n_cand);
 }
@@ -2121,6 +2163,8 @@ int natac_run_occ_peaks(natac_batch *b, double min_occ, int sep, const double *j
     if (!b || !n_peaks) return fail(NATAC_E_ARG, "null argument");
     int rc;
     for (int t : {NATAC_T_OCC, NATAC_T_OCC_LOWER, NATAC_T_OCC_UPPER, NATAC_T_OCC_COV}) if ((rc = need_track(b, t))) return rc;
+    // natac_occ_peak_dist reads the context's flank and size range next to the run's tracks
+    if ((rc = need_occ_geometry(b, "natac_run_occ_peaks"))) return rc;
     natac_ctx *c = b->ctx;
     const int U = c->occ_upper;
     if (U > 1024) return fail(NATAC_E_ARG, "upper > 1024");

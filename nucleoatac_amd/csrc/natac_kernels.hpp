@@ -145,6 +145,12 @@ __global__ void __launch_bounds__(256) natac_exp_bias(const double *__restrict__
     for (; i < n; i += stride) e[i] = exp(b[i]);
 }
 
+// status[i] &= ~mask: a stage drops its own bit of every chunk's status word before it launches (the other stages' bits stay)
+__global__ void __launch_bounds__(256) natac_status_clear(int *__restrict__ status, int nc, int mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < nc) status[i] &= ~mask;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K0  sparse V-plot gather: nuc_cov, nfr_cov, raw signal.
 //   nuc_cov[g] = #{frag: vlower <= n < vupper, |c-g| <= w}          tracks.py:209-222 via NucleosomeCalling.py:257-260

@@ -638,6 +638,8 @@ class DeviceBatch(object):
         cc, cp, keep = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
         occ, lo, up, rd = (np.empty(n, np.float64) for _ in range(4))
         L.check(self._lib.natac_download_occ_peaks(self._h, n, _ptr(cc), _ptr(cp), _ptr(occ), _ptr(lo), _ptr(up), _ptr(rd), _ptr(keep)))
+        # the context's size range is the run's here: natac_run_occ_peaks above refuses (NATAC_E_STATE) when the occupancy geometry
+        # was changed after natac_run_occ, and natac_download_nuc_dist checks the buffer's size against the run's
         upper = self.ctx.occ_upper
         nd = np.empty((self.packed.n_chunks, upper), dtype=np.float64)
         L.check(self._lib.natac_download_nuc_dist(self._h, _ptr(nd), nd.nbytes))

@@ -2,6 +2,7 @@
 odd row count, width), smoothing width, occupancy window / step / size range / alpha grid -- so the fallback kernels run
 (generic smoothing, natac_occ_mle, natac_candidates4, the FFT kernel's odd-row loop, natac_background_generic) -- on a
 few ragged chunks, against the CPU oracle.   usage: python tests/fuzz/fuzz_generic.py [n_rounds] [seed]"""
+import contextlib
 import os
 import sys
 import time
@@ -19,7 +20,9 @@ from nucleoatac_amd.synth import synth_occ_distributions, synth_size_distributio
 from oracle import natac_oracle as O  # noqa: E402
 
 
-def one_round(rng, par):
+def one_round(rng, par, ctx=None):
+    """one random geometry on a context of its own, or installed on the caller's `ctx` (which then carries the tables of every
+    earlier round's model: natac.h, rule A)"""
     w = int(rng.choice([30, 50, 60]))
     vlo = int(rng.integers(80, 131))
     R = int(rng.integers(40, 147))
@@ -57,7 +60,7 @@ def one_round(rng, par):
     pk = PackedChunks(np.arange(len(lens)) * 20000, lens, off, np.concatenate([x[0] for x in fr]), np.concatenate([x[1] for x in fr]),
                       np.concatenate(([0], np.cumsum(nb))), bias, bias_left=BL, bias_right=BR)
     desc = dict(w=w, vlo=vlo, vup=vup, occ_up=occ_up, flank=flank, step=step, n_alpha=n_alpha, sd=sd, lens=lens)
-    with Context(0) as c:
+    with (Context(0) if ctx is None else contextlib.nullcontext(ctx)) as c:
         c.set_vmat(vm, vlo, vup)
         c.set_sizes(sizes[:max(vup, occ_up)])
         c.set_occ_model(nucp, nfrp, alphas=np.linspace(0, 1, n_alpha), cutoff=cutoff, step=step, flank=flank)

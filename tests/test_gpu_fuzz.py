@@ -44,6 +44,20 @@ def test_random_model_geometries_match_the_oracle():
     assert bp > 10000
 
 
+def test_random_model_geometries_on_one_context():
+    """the same rounds and seed on ONE long-lived context: every round installs its geometry over the tables the earlier rounds left
+    (template spectra, log(V / s), size weights, windows, block weights, q4 / rho), and the checks against the oracle are the same"""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "fuzz"))
+    import fuzz_generic as G
+    from helpers import golden
+    from nucleoatac_amd.device import Context
+    par = golden("params_example")
+    rng = np.random.default_rng(99)
+    with Context(0) as ctx:
+        bp = sum(G.one_round(rng, par, ctx) for _ in range(25))
+    assert bp > 10000
+
+
 def test_random_dropin_calls_match_the_oracle():
     """a short run of tests/fuzz/fuzz_dropins.py: the Cython functions' replacements and the operator-level helpers on random
     regions / fragment sets / chunk lists / windows / PWMs"""

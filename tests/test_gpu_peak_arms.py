@@ -217,7 +217,7 @@ def check_search(cc, cp, st, sigs, maxL, order, boundary, sep, min_signal, what)
 @pytest.mark.parametrize("maxL", LENGTHS)
 def test_track_peaks_every_arm(ctx, maxL):
     """natac_run_track_peaks on designed signals (set_track) for every order / boundary / sep / min_signal of PARAMS: a fresh
-    set of outputs per search (release_outputs), since the overflow flag of a batch is kept until then"""
+    set of outputs per search (release_outputs)"""
     sigs = designed_signals(maxL, seed=maxL)
     lens = [len(s) for s in sigs]
     assert max(lens) == maxL
@@ -306,12 +306,12 @@ def test_overflow_flag_at_the_boundary(ctx, sep):
 
 @pytest.mark.gpu
 def test_overflow_flag_lifetime(ctx):
-    """Pins the lifetime of the per-chunk status word: d_status is cleared only when the batch is created and by
-    natac_batch_release_outputs.  A later search that does not overflow does NOT clear a flag an earlier search set -- the flag
-    means "some search on these outputs overflowed".  The drivers rely on exactly that conservative reading: the executor
-    (executor.py, PipelinedExecutor._process) and BatchRunner read status() once, after all stages of a fresh batch, and a driver
-    uses bit 2 only from a batch that ran a single peak search (occ: natac_run_occ_peaks; nuc: natac_run_peaks), so a set bit
-    always names the search whose result they replace."""
+    """Pins the lifetime of the per-chunk status word (natac_batch_status): d_status is cleared when the batch is created and by
+    natac_batch_release_outputs, and each stage drops its OWN bit for every chunk before it launches -- value 2 belongs to the peak
+    search, value 1 to natac_run_occ.  So value 2 always describes the LAST search on the batch, whatever ran on it before (a search
+    under another model included: natac.h, rule A), and a search never touches value 1.  The drivers read status() once, after all
+    stages of a batch, and use value 2 only from a batch that ran a single peak search (occ: natac_run_occ_peaks; nuc:
+    natac_run_peaks), so a set bit names the search whose result they replace."""
     rng = np.random.default_rng(5)
     sigs = [_spikes(5000, 2049, rng), rng.standard_normal(3000)]
     b = ctx.upload(_packed([len(s) for s in sigs]))
@@ -319,14 +319,16 @@ def test_overflow_flag_lifetime(ctx):
     b.set_track(L.T_OCC, np.concatenate(sigs))
     b.run_track_peaks(L.T_OCC, min_signal=0.0, sep=1, boundary=0, order=1)
     assert list(b.status()) == [2, 0]
-    # a search without overflow (order 3: at most 5000 / 4 + 1 maxima, lists sized for them) leaves the flag set
+    # a search without overflow (order 3: at most 5000 / 4 + 1 maxima, lists sized for them) drops the flag of the one before it
     cc, cp = b.run_track_peaks(L.T_OCC, min_signal=0.0, sep=1, boundary=0, order=3)
-    assert list(b.status()) == [2, 0]
+    assert not b.status().any()
     assert np.array_equal(cp[cc == 0], call_peaks_stable(sigs[0].copy(), min_signal=0.0, sep=1, boundary=0, order=3))
+    # ... and the overflowing search raises it again, for its chunk only
+    b.run_track_peaks(L.T_OCC, min_signal=0.0, sep=1, boundary=0, order=1)
+    assert list(b.status()) == [2, 0]
     b.release_outputs()
     assert not b.status().any()
     b.set_track(L.T_OCC, np.concatenate(sigs))
     b.run_track_peaks(L.T_OCC, min_signal=0.0, sep=1, boundary=0, order=3)
     assert not b.status().any()
     b.free()
-
