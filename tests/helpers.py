@@ -110,6 +110,48 @@ def assert_track(got, ref, name, exact=False, rtol=None, atol=None, scale=1.0, t
             name, int(bad.sum()), float(d.max()), float(np.abs(ref[m][np.argmax(d)])))
 
 
+def _assert_stat(got, ref, name, scale):
+    """the tight tier of helpers.assert_track with a per-value `scale` of the absolute floor; +-inf must match exactly"""
+    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    assert got.shape == ref.shape, name
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), "%s: NaN pattern differs" % name
+    inf = np.isinf(ref)
+    assert np.array_equal(got[inf], ref[inf]), "%s: infinities differ" % name
+    m = np.isfinite(ref)
+    d = np.abs(got[m] - ref[m])
+    bad = d > TIGHT_ATOL * np.broadcast_to(scale, ref.shape)[m] + TIGHT_RTOL * np.abs(ref[m])
+    assert not bad.any(), "%s: %d of %d values off, max |d| = %g" % (name, int(bad.sum()), int(m.sum()), float(d.max()))
+
+
+def _assert_stats(got, ref, scales, what):
+    for g, r, s, name in zip(got, ref, scales, ("lr", "var", "z")):
+        _assert_stat(g, r, "%s %s" % (what, name), s)
+
+
+def _reference_stats(nts, vm, lo, up, cc, cp):
+    """lr / var / z of Nucleosome.getLR / getZScore (oracle) at every candidate, and the scale of each one's absolute floor"""
+    from oracle import natac_oracle as O
+    w = vm.shape[1] // 2
+    n = len(cc)
+    lr, var, z = np.empty(n), np.empty(n), np.empty(n)
+    lr_scale, z_scale = np.ones(n), np.ones(n)
+    for j, (k, p) in enumerate(zip(cc, cp)):
+        nt, p = nts[k], int(p)
+        lr[j] = O.get_lr(nt["mat"], nt["mat_start"], nt["bmat"], nt["b0"], nt["b_start"], vm, lo, up, p)
+        pr = O.signal_distribution_probs(nt["bmat"], nt["b_start"], lo, up, w, p)
+        z[j], var[j] = O.z_score(nt["norm"][p], nt["nuc_cov"][p], pr, vm)
+        # lr = nuc_lik - null_lik: its absolute floor is relative to the two sums (cancel_scale), here the null model's
+        m = nt["mat"][lo:up, p - w - nt["mat_start"]:p + w + 1 - nt["mat_start"]]
+        null = nt["bmat"][lo:up, p - w - nt["b_start"]:p + w + 1 - nt["b_start"]]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            null_lik = np.sum(np.log(null / np.sum(null)) * m)
+        lr_scale[j] = cancel_scale([null_lik, null_lik + lr[j]])
+        # z = norm / sqrt(var): norm's floor is cancel_scale(raw, bg) (helpers.py), divided by sqrt(var) with it
+        if var[j] > 0:
+            z_scale[j] = cancel_scale(nt["raw"], nt["bg"]) / np.sqrt(var[j])
+    return (lr, var, z), (lr_scale, np.ones(n), z_scale)
+
+
 def expand_grid(vals, L, step=5):
     """per-grid-point values -> per-base track, as OccupancyTrack.calculateOccupancyMLE assigns them
     (nucleoatac/Occupancy.py:136-146): grid point k covers [k*step, min((k+1)*step, L)); the tail stays NaN."""

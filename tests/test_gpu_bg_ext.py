@@ -128,6 +128,13 @@ def test_extended_tiles_with_damaged_bias_match_oracle_and_direct():
     assert np.array_equal(np.isnan(bg_e), np.isnan(bg_d))
     ok = ~np.isnan(bg_d)
     np.testing.assert_allclose(bg_e[ok], bg_d[ok], rtol=1e-9, atol=1e-12)
+    # the candidates' lr / var / z of the same two runs (every third position of every chunk): NaNs at the same candidates, and where
+    # finite the agreement the undamaged batch has above
+    for k in ("lr", "var", "z"):
+        assert np.array_equal(np.isnan(ext[k]), np.isnan(direct[k])), k
+        fin = ~np.isnan(direct[k])
+        np.testing.assert_allclose(ext[k][fin], direct[k][fin], rtol=1e-9, atol=1e-11, err_msg=k)
+    assert np.isnan(ext["lr"]).sum() > np.isnan(ext["var"]).sum() > 0        # the zero's span has lr = NaN only, the NaN's all three
     pk, fr = _ragged_batch(LENGTHS, 7, "damaged")
     off = np.concatenate(([0], np.cumsum(LENGTHS)))
     for k in (0, 1, 8):

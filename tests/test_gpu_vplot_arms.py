@@ -25,7 +25,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import TIGHT_ATOL, TIGHT_RTOL, assert_track, cancel_scale, golden
+from helpers import _assert_stats, _reference_stats, assert_track, cancel_scale, golden
 from nucleoatac_amd import _lib as L
 from nucleoatac_amd.packing import PackedChunks
 from nucleoatac_amd.synth import synth_centres, synth_size_distribution, synth_sizes
@@ -103,48 +103,6 @@ def _batch(lens, up, seed):
     pk = PackedChunks(np.arange(len(lens)) * 20000, lens, off, np.concatenate([x[0] for x in fr]), np.concatenate([x[1] for x in fr]),
                       np.concatenate(([0], np.cumsum(nb))), bias, bias_left=BL, bias_right=BR)
     return pk, fr
-
-
-def _assert_stat(got, ref, name, scale):
-    """the tight tier of helpers.assert_track with a per-value `scale` of the absolute floor; +-inf must match exactly"""
-    got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)
-    assert got.shape == ref.shape, name
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), "%s: NaN pattern differs" % name
-    inf = np.isinf(ref)
-    assert np.array_equal(got[inf], ref[inf]), "%s: infinities differ" % name
-    m = np.isfinite(ref)
-    d = np.abs(got[m] - ref[m])
-    bad = d > TIGHT_ATOL * np.broadcast_to(scale, ref.shape)[m] + TIGHT_RTOL * np.abs(ref[m])
-    assert not bad.any(), "%s: %d of %d values off, max |d| = %g" % (name, int(bad.sum()), int(m.sum()), float(d.max()))
-
-
-def _assert_stats(got, ref, scales, what):
-    for g, r, s, name in zip(got, ref, scales, ("lr", "var", "z")):
-        _assert_stat(g, r, "%s %s" % (what, name), s)
-
-
-def _reference_stats(nts, vm, lo, up, cc, cp):
-    """lr / var / z of Nucleosome.getLR / getZScore (oracle) at every candidate, and the scale of each one's absolute floor"""
-    from oracle import natac_oracle as O
-    w = vm.shape[1] // 2
-    n = len(cc)
-    lr, var, z = np.empty(n), np.empty(n), np.empty(n)
-    lr_scale, z_scale = np.ones(n), np.ones(n)
-    for j, (k, p) in enumerate(zip(cc, cp)):
-        nt, p = nts[k], int(p)
-        lr[j] = O.get_lr(nt["mat"], nt["mat_start"], nt["bmat"], nt["b0"], nt["b_start"], vm, lo, up, p)
-        pr = O.signal_distribution_probs(nt["bmat"], nt["b_start"], lo, up, w, p)
-        z[j], var[j] = O.z_score(nt["norm"][p], nt["nuc_cov"][p], pr, vm)
-        # lr = nuc_lik - null_lik: its absolute floor is relative to the two sums (cancel_scale), here the null model's
-        m = nt["mat"][lo:up, p - w - nt["mat_start"]:p + w + 1 - nt["mat_start"]]
-        null = nt["bmat"][lo:up, p - w - nt["b_start"]:p + w + 1 - nt["b_start"]]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            null_lik = np.sum(np.log(null / np.sum(null)) * m)
-        lr_scale[j] = cancel_scale([null_lik, null_lik + lr[j]])
-        # z = norm / sqrt(var): norm's floor is cancel_scale(raw, bg) (helpers.py), divided by sqrt(var) with it
-        if var[j] > 0:
-            z_scale[j] = cancel_scale(nt["raw"], nt["bg"]) / np.sqrt(var[j])
-    return (lr, var, z), (lr_scale, np.ones(n), z_scale)
 
 
 @pytest.mark.parametrize("lo,up,w,zero", CASES)
