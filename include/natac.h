@@ -49,8 +49,9 @@ extern "C" {
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
  * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
  * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`;
- * 9: added natac_frag_open / natac_frag_open_device for fragment files); the binding refuses another version */
-#define NATAC_ABI_VERSION 9
+ * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device); the binding
+ * refuses another version */
+#define NATAC_ABI_VERSION 10
 
 enum {
     NATAC_OK = 0,
@@ -503,6 +504,38 @@ int natac_frag_open(const char *path, int n_threads, natac_bam **out);
  * member (so the message is natac_frag_open's by construction), a line longer than a window, more than 65,536 chromosome runs in a
  * window, or a HIP failure; *on_device (may be NULL) tells which one answered. */
 int natac_frag_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int *on_device);
+/* ---- a fragment file split by cell barcode: one pass, one handle per cell group (a cluster, a sample, a QC whitelist) ----
+ * THE SPLIT RULE (csrc/natac_fragfile.hpp: split_line is it; nucleoatac_amd/pyatac/fragments.py restates it).
+ * Validation: every line is classified exactly as by natac_frag_open (same checks, same order, same reasons, same line numbers); a data
+ *   line that passes them but has fewer than four fields is malformed: "no barcode field", checked last.
+ * Barcode: the bytes between the third TAB and the fourth, or the line's end (the '\r' before a '\n' dropped first; a last line without
+ *   '\n' keeps its '\r').  Compared byte for byte: no trimming, no case folding, a "-1" suffix is part of it.  A line whose barcode is
+ *   empty, longer than 255 bytes or not in the table is UNASSIGNED: validated, counted, in no group, and no error.
+ * Table: n_barcodes >= 1 distinct barcodes of 1-255 bytes, bc_bytes[bc_off[k] .. bc_off[k + 1]) (bc_off[0] == 0), each with a group
+ *   bc_group[k] in [0, n_groups), n_groups in [1, NATAC_SPLIT_MAX_GROUPS].  Two equal barcodes: NATAC_E_ARG naming both entries.  At most
+ *   NATAC_SPLIT_MAX_BARCODES barcodes (NATAC_E_ARG beyond); the device takes tables of up to 4,194,304, the host path answers for larger.
+ * Result: out[n_groups] handles.  Every group has the SAME chromosome list (first appearance over all data lines of the file, assigned
+ *   or not) and the same lengths (largest end over all data lines of the chromosome), so groups are comparable; a chromosome on which
+ *   a group has nothing is present and empty.  A group's records are its lines (pos = start - 4, tlen = end - start + 8) in file order
+ *   within each chromosome; a chromosome that comes back appends behind its earlier records; ties keep file order.  natac_bam_counts:
+ *   n_records = the file's data lines, n_kept = the group's.  bc_count[n_barcodes] (may be NULL) = data lines per listed barcode,
+ *   *n_unassigned (may be NULL) = data lines in no group.
+ * Lookup: a hash of the barcode into an open-addressing table built once; a slot matches only after its bytes compared equal; the table
+ *   always has an empty slot and the probe loop is bounded by the slot count.  NATAC_SPLIT_HASH_BITS=k keeps the low k bits of the hash
+ *   only (tests: k = 3 makes nearly every lookup walk a chain of equal hashes).
+ * Containers, windows (NATAC_BAM_WINDOW), slices and errors as natac_frag_open: the result and the first error do not depend on
+ * n_threads or the window.  On any error every out[g] is NULL. */
+#define NATAC_SPLIT_MAX_GROUPS 255
+#define NATAC_SPLIT_MAX_BARCODES 8388608
+int natac_frag_split(const char *path, int n_threads, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group,
+                     int32_t n_groups, natac_bam **out, int64_t *bc_count, int64_t *n_unassigned);
+/* The same with a BGZF file inflated, split into lines and parsed ON THE DEVICE as by natac_frag_open_device, every data line's barcode
+ * looked up and counted there, and each window's assigned lines partitioned by group there (stable; unassigned lines never come back to
+ * the host).  The host path answers inside this call for everything natac_frag_open_device hands over, for a line without a barcode
+ * field, for a table of more than 4,194,304 barcodes, and for a window in which groups x chromosome runs exceeds 1,048,576;
+ * *on_device (may be NULL) tells which one answered. */
+int natac_frag_split_device(natac_ctx *ctx, const char *path, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group,
+                            int32_t n_groups, natac_bam **out, int64_t *bc_count, int64_t *n_unassigned, int *on_device);
 /* test entry: the device's raw-deflate decoder run on the host (one BGZF member payload -> isize bytes); returns its error code */
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize);
 

@@ -3358,6 +3358,76 @@ int natac_frag_open_device(natac_ctx *c, const char *path, natac_bam **out, int 
     return NATAC_OK;
 }
 
+/* ---------------- a fragment file split by cell barcode into one handle per group ---------------- */
+
+static int frag_split_table(int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group, int32_t n_groups, natac_bam **out,
+                            natac_fragio::SplitTableHost &table) {
+    for (int32_t g = 0; g < n_groups && g < NATAC_SPLIT_MAX_GROUPS; ++g) out[g] = nullptr;
+    std::string err;
+    if (!table.build(n_barcodes, (const unsigned char *)bc_bytes, bc_off, bc_group, n_groups, NATAC_SPLIT_MAX_GROUPS, NATAC_SPLIT_MAX_BARCODES, err))
+        return fail(NATAC_E_ARG, "%s", err.c_str());
+    return NATAC_OK;
+}
+
+static int frag_split_host(const char *path, int n_threads, const natac_fragio::SplitTableHost &table, natac_bam **out, int64_t *bc_count,
+                           int64_t *n_unassigned) {
+    std::vector<natac_bamio::Bam *> impl((size_t)table.n_groups, nullptr);
+    std::string err;
+    if (!natac_fragio::decode_split(path, n_threads, table, impl.data(), bc_count, n_unassigned, err, frag_host_window()))
+        return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
+    for (int g = 0; g < table.n_groups; ++g) {
+        out[g] = new natac_bam();
+        out[g]->impl = impl[(size_t)g];
+    }
+    return NATAC_OK;
+}
+
+int natac_frag_split(const char *path, int n_threads, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group,
+                     int32_t n_groups, natac_bam **out, int64_t *bc_count, int64_t *n_unassigned) {
+    if (!path || !out || !bc_bytes || !bc_off || !bc_group) return fail(NATAC_E_ARG, "null argument");
+    natac_fragio::SplitTableHost table;
+    if (const int rc = frag_split_table(n_barcodes, bc_bytes, bc_off, bc_group, n_groups, out, table)) return rc;
+    return frag_split_host(path, n_threads, table, out, bc_count, n_unassigned);
+}
+
+int natac_frag_split_device(natac_ctx *c, const char *path, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group,
+                            int32_t n_groups, natac_bam **out, int64_t *bc_count, int64_t *n_unassigned, int *on_device) {
+    if (!c || !path || !out || !bc_bytes || !bc_off || !bc_group) return fail(NATAC_E_ARG, "null argument");
+    if (on_device) *on_device = 0;
+    natac_fragio::SplitTableHost table;
+    if (const int rc = frag_split_table(n_barcodes, bc_bytes, bc_off, bc_group, n_groups, out, table)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    bool bgzf = false;
+    if (FILE *f = std::fopen(path, "rb")) {
+        unsigned char magic[1040];
+        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
+        std::fclose(f);
+    }
+    if (bgzf && n_barcodes <= natac_fragdev::SPLIT_DEV_MAX_BARCODES) {      // other containers and larger tables are the host path's
+        size_t window = (size_t)1 << 30;
+        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+        natac_fragio::SplitBuilder sb(n_groups);
+        natac_fragdev::SplitJob job{&table, &sb, {}};
+        std::string why;
+        natac_bamio::Bam *token = natac_fragdev::decode_device(path, c->stream, why, window, &job);
+        if (token) {
+            delete token;
+            std::vector<natac_bamio::Bam *> impl((size_t)n_groups, nullptr);
+            sb.finish(impl.data());
+            for (int g = 0; g < n_groups; ++g) {
+                out[g] = new natac_bam();
+                out[g]->impl = impl[(size_t)g];
+            }
+            if (bc_count) std::copy(job.bc_count.begin(), job.bc_count.end(), bc_count);
+            if (n_unassigned) *n_unassigned = sb.n_records - sb.n_assigned;
+            if (on_device) *on_device = 1;
+            return NATAC_OK;
+        }
+    }
+    // everything natac_frag_open_device hands over, a line without a barcode field, too many groups x runs in a window: the host path answers
+    return frag_split_host(path, 0, table, out, bc_count, n_unassigned);
+}
+
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize) {
     if ((!src && csize) || (!out && isize) || csize > 0xffffffffull || isize > 0xffffffffull) return -1;
     std::vector<unsigned char> padded(csize + 32, 0);        // the bit reader takes whole words: 32 readable bytes behind the payload

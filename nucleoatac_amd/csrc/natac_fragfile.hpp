@@ -6,6 +6,8 @@
 // ATAC offsets (pyatac/fragments.pyx:26-31).  parse_line below IS that rule; it is __host__ __device__ so that the device decoder
 // (natac_fragfile_dev.hpp) classifies every line with the same code.
 // Container by magic bytes: BGZF (the window reader of natac_bam.hpp), any other gzip (zlib, several members allowed), plain text.
+// Splitting by cell barcode (natac_frag_split): split_line below IS the rule of include/natac.h -- parse_line, then the fourth field looked
+// up in a SplitTable -- and is __host__ __device__ for the same reason.
 #pragma once
 #include "natac_bam.hpp"
 
@@ -26,7 +28,8 @@ using natac_bamio::Bam;
 using natac_bamio::Ref;
 
 // what a line is: LINE_SKIP (empty or '#'), LINE_DATA, or a malformed data line (one value per fixed reason string)
-enum { LINE_SKIP = 0, LINE_DATA = 1, BAD_FIELDS = 2, BAD_NAME_EMPTY = 3, BAD_NAME_LONG = 4, BAD_NUMBER = 5, BAD_RANGE = 6, BAD_ORDER = 7 };
+enum { LINE_SKIP = 0, LINE_DATA = 1, BAD_FIELDS = 2, BAD_NAME_EMPTY = 3, BAD_NAME_LONG = 4, BAD_NUMBER = 5, BAD_RANGE = 6, BAD_ORDER = 7,
+       BAD_NO_BARCODE = 8 };        // (only when splitting by barcode: split_line)
 
 inline const char *reason_text(int kind) {
     switch (kind) {
@@ -36,6 +39,7 @@ inline const char *reason_text(int kind) {
         case BAD_NUMBER: return "start / end is not a number";
         case BAD_RANGE: return "start / end out of range (more than 2147483647)";
         case BAD_ORDER: return "end before start";
+        case BAD_NO_BARCODE: return "no barcode field";
     }
     return "";
 }
@@ -72,6 +76,63 @@ NATAC_FRAG_HD inline int parse_line(const unsigned char *p, size_t len, uint32_t
     if (rc != LINE_DATA) return rc;
     if (*end < *start) return BAD_ORDER;
     *name_len = (uint32_t)t1;
+    return LINE_DATA;
+}
+
+// ---- splitting by cell barcode: the lookup table and the rule ----
+// Open addressing, linear probing: slot[h & (n_slots - 1)] holds 1 + the index of a barcode, 0 = empty.  n_slots is a power of two of at
+// least twice n_barcodes, so an empty slot always exists; the probe loop is bounded by n_slots all the same.  A slot only matches after
+// its bytes compared equal.  hash_mask keeps the low bits of the hash (all of them unless NATAC_SPLIT_HASH_BITS says otherwise: tests).
+struct SplitTable {
+    const unsigned char *bytes;     // the barcodes, concatenated
+    const uint32_t *off;            // [n_barcodes + 1] into bytes
+    const int32_t *group;           // [n_barcodes]
+    const uint32_t *slot;           // [n_slots]
+    uint32_t n_barcodes, n_slots, hash_mask;
+};
+
+NATAC_FRAG_HD inline uint32_t barcode_hash(const unsigned char *p, size_t len) {      // FNV-1a and a final mix of the high bits into the low
+    uint32_t h = 2166136261u;
+    for (size_t i = 0; i < len; ++i) h = (h ^ (uint32_t)p[i]) * 16777619u;
+    h ^= h >> 15;
+    h *= 0x2c1b3c6du;
+    h ^= h >> 12;
+    return h;
+}
+
+// index of the barcode p[0, len) in the table, or -1 (an empty barcode and one longer than 255 bytes are never listed)
+NATAC_FRAG_HD inline int32_t barcode_lookup(const SplitTable &tb, const unsigned char *p, size_t len) {
+    if (len == 0 || len > 255) return -1;
+    uint32_t s = (barcode_hash(p, len) & tb.hash_mask) & (tb.n_slots - 1u);
+    for (uint32_t probe = 0; probe < tb.n_slots; ++probe, s = (s + 1u) & (tb.n_slots - 1u)) {
+        const uint32_t v = tb.slot[s];
+        if (v == 0) return -1;
+        const uint32_t k = v - 1u;
+        if (k >= tb.n_barcodes) continue;
+        const uint32_t a = tb.off[k], b = tb.off[k + 1];
+        if ((size_t)(b - a) != len) continue;
+        bool same = true;
+        for (size_t i = 0; i < len && same; ++i) same = tb.bytes[a + i] == p[i];
+        if (same) return (int32_t)k;
+    }
+    return -1;
+}
+
+// THE SPLIT RULE.  The line is classified by parse_line (same checks, same order); a data line without a fourth field is BAD_NO_BARCODE,
+// checked last.  The barcode is the bytes between the third TAB and the fourth (or the line's end), compared byte for byte.  *bc = its
+// index in the table, or -1: unassigned (empty, longer than 255 bytes or not listed), which is no error.
+NATAC_FRAG_HD inline int split_line(const unsigned char *p, size_t len, const SplitTable &tb, uint32_t *name_len, int32_t *start, int32_t *end,
+                                    int32_t *bc) {
+    const int kind = parse_line(p, len, name_len, start, end);
+    if (kind != LINE_DATA) return kind;
+    size_t t = 0;
+    for (int k = 0; k < 3; ++k, ++t) {                  // behind the third TAB
+        while (t < len && p[t] != '\t') ++t;
+        if (t >= len) return BAD_NO_BARCODE;
+    }
+    size_t e = t;
+    while (e < len && p[e] != '\t') ++e;
+    *bc = barcode_lookup(tb, p + t, e - t);
     return LINE_DATA;
 }
 
@@ -176,29 +237,28 @@ inline bool is_bgzf(const unsigned char *h, size_t have) {
 }
 
 // Streaming decode, bounded memory like natac_bamio::decode: ~window bytes of (compressed) input at a time, the bytes behind a window's
-// last '\n' carried to the front of the next.  returns nullptr + error text ("line N: reason" for a malformed line).
-inline Bam *decode(const char *path, int n_threads, std::string &err, size_t window = (size_t)48 << 20) {
+// last '\n' carried to the front of the next.  returns false + error text ("line N: reason" for a malformed line).
+// parse(p, n, open_end, n_threads, &lines, err) takes every window's complete lines (parse_text, or parse_text_split below).
+template <class Parse>
+inline bool stream_text(const char *path, int n_threads, std::string &err, size_t window, Parse &&parse) {
     FILE *f = std::fopen(path, "rb");
-    if (!f) { err = std::string("cannot open ") + path; return nullptr; }
+    if (!f) { err = std::string("cannot open ") + path; return false; }
     if (n_threads <= 0) n_threads = natac_cores::default_threads(64);
     window = std::max<size_t>(window, (size_t)4096);
     unsigned char magic[1040];
     const size_t have = std::fread(magic, 1, sizeof magic, f);
     std::rewind(f);
     const bool gz = have >= 2 && magic[0] == 0x1f && magic[1] == 0x8b, bgzf = is_bgzf(magic, have);
-    Bam *bam = new Bam();
-    Builder bd(bam);
     std::vector<unsigned char> data, in;
     std::unique_ptr<natac_bamio::BgzfWindows> z(bgzf ? new natac_bamio::BgzfWindows(f, n_threads, window) : nullptr);
     z_stream zs;
     std::memset(&zs, 0, sizeof zs);
     bool zs_open = false, in_member = false, file_end = false;
-    auto fail = [&](const std::string &msg) -> Bam * {
+    auto fail = [&](const std::string &msg) -> bool {
         err = msg;
-        delete bam;
         if (zs_open) inflateEnd(&zs);
         std::fclose(f);
-        return nullptr;
+        return false;
     };
     if (gz && !bgzf) {
         if (inflateInit2(&zs, 15 + 16) != Z_OK) return fail("zlib: inflateInit2 failed");
@@ -250,14 +310,194 @@ inline Bam *decode(const char *path, int n_threads, std::string &err, size_t win
         size_t last = n;                                   // behind the last '\n' of the window
         while (last > pend && data[last - 1] != '\n') --last;
         if (last == pend) { pend = n; continue; }           // no line ends in this window: a line longer than it
-        if (!parse_text(data.data(), last, false, n_threads, bd, &lines, err)) return fail(err);
+        if (!parse(data.data(), last, false, n_threads, &lines, err)) return fail(err);
         pend = n - last;
         std::memmove(data.data(), data.data() + last, pend);
     }
-    if (pend && !parse_text(data.data(), pend, true, 1, bd, &lines, err)) return fail(err);       // a last line without '\n' is a line
+    if (pend && !parse(data.data(), pend, true, 1, &lines, err)) return fail(err);                // a last line without '\n' is a line
     if (zs_open) inflateEnd(&zs);
     std::fclose(f);
+    return true;
+}
+
+inline Bam *decode(const char *path, int n_threads, std::string &err, size_t window = (size_t)48 << 20) {
+    Bam *bam = new Bam();
+    Builder bd(bam);
+    const bool ok = stream_text(path, n_threads, err, window, [&](const unsigned char *p, size_t n, bool open_end, int threads, unsigned long long *lines,
+                                                                  std::string &e) { return parse_text(p, n, open_end, threads, bd, lines, e); });
+    if (!ok) { delete bam; return nullptr; }
     return bam;
+}
+
+// ---- the split by barcode on the host ----
+// The table as the host owns it.  build() checks the caller's arrays and that the barcodes are distinct (false + err names both entries).
+struct SplitTableHost {
+    std::vector<unsigned char> bytes;
+    std::vector<uint32_t> off, slot;
+    std::vector<int32_t> group;
+    uint32_t hash_mask = 0xffffffffu;
+    int n_groups = 0;
+    SplitTable view() const { return SplitTable{bytes.data(), off.data(), group.data(), slot.data(), (uint32_t)group.size(), (uint32_t)slot.size(), hash_mask}; }
+    bool build(int64_t n_barcodes, const unsigned char *bc_bytes, const int64_t *bc_off, const int32_t *bc_group, int groups, int max_groups,
+               int64_t max_barcodes, std::string &err) {
+        if (n_barcodes < 1 || n_barcodes > max_barcodes) { err = "n_barcodes must be in [1, " + std::to_string(max_barcodes) + "]"; return false; }
+        if (groups < 1 || groups > max_groups) { err = "n_groups must be in [1, " + std::to_string(max_groups) + "]"; return false; }
+        if (bc_off[0] != 0) { err = "bc_off[0] must be 0"; return false; }
+        for (int64_t k = 0; k < n_barcodes; ++k) {
+            const int64_t len = bc_off[k + 1] - bc_off[k];
+            if (len < 1 || len > 255) { err = "barcode " + std::to_string(k) + " is not 1-255 bytes long"; return false; }
+            if (bc_group[k] < 0 || bc_group[k] >= groups) { err = "barcode " + std::to_string(k) + ": group out of range"; return false; }
+        }
+        n_groups = groups;
+        bytes.assign(bc_bytes, bc_bytes + bc_off[n_barcodes]);
+        off.resize((size_t)n_barcodes + 1);
+        for (int64_t k = 0; k <= n_barcodes; ++k) off[(size_t)k] = (uint32_t)bc_off[k];
+        group.assign(bc_group, bc_group + n_barcodes);
+        if (const char *e = getenv("NATAC_SPLIT_HASH_BITS")) { const int b = atoi(e); if (b >= 0 && b < 32) hash_mask = (1u << b) - 1u; }
+        uint32_t ns = 16;
+        while ((uint64_t)ns < 2ull * (uint64_t)n_barcodes) ns <<= 1;
+        slot.assign(ns, 0u);
+        for (int64_t k = 0; k < n_barcodes; ++k) {
+            const unsigned char *p = bytes.data() + off[(size_t)k];
+            const size_t len = off[(size_t)k + 1] - off[(size_t)k];
+            const int32_t seen = barcode_lookup(view(), p, len);
+            if (seen >= 0) { err = "barcodes " + std::to_string(seen) + " and " + std::to_string(k) + " are the same"; return false; }
+            uint32_t s = (barcode_hash(p, len) & hash_mask) & (ns - 1u);
+            while (slot[s] != 0) s = (s + 1u) & (ns - 1u);
+            slot[s] = (uint32_t)k + 1u;
+        }
+        return true;
+    }
+};
+
+// What both paths append to: ONE chromosome list (first appearance over all data lines, assigned or not) and one length per chromosome
+// (the largest end over all of its data lines) for every group; per group and chromosome the group's records in file order.
+struct SplitBuilder {
+    int G;
+    std::unordered_map<std::string, int> ids;
+    std::vector<std::string> names;
+    std::vector<int64_t> length, kept;
+    std::vector<std::vector<std::vector<int64_t>>> pos, tlen;        // [group][chromosome]
+    int64_t n_records = 0, n_assigned = 0;
+    explicit SplitBuilder(int groups) : G(groups), kept((size_t)groups, 0), pos((size_t)groups), tlen((size_t)groups) {}
+    int chrom(const std::string &name, int64_t max_end, int64_t n_lines) {      // a run of n_lines data lines on `name`
+        auto it = ids.find(name);
+        if (it == ids.end()) {
+            it = ids.emplace(name, (int)names.size()).first;
+            names.push_back(name);
+            length.push_back(0);
+        }
+        if (max_end > length[(size_t)it->second]) length[(size_t)it->second] = max_end;
+        n_records += n_lines;
+        return it->second;
+    }
+    void append(int g, int c, int64_t start, int64_t end) {
+        auto &p = pos[(size_t)g], &t = tlen[(size_t)g];
+        if (p.size() <= (size_t)c) { p.resize((size_t)c + 1); t.resize((size_t)c + 1); }
+        p[(size_t)c].push_back(start - 4);
+        t[(size_t)c].push_back(end - start + 8);
+        ++kept[(size_t)g];
+        ++n_assigned;
+    }
+    void finish(Bam **out) {                             // out[G]; the arrays move
+        for (int g = 0; g < G; ++g) {
+            Bam *b = new Bam();
+            b->refs.resize(names.size());
+            for (size_t c = 0; c < names.size(); ++c) {
+                b->refs[c].name = names[c];
+                b->refs[c].length = length[c];
+                if (c < pos[(size_t)g].size()) { b->refs[c].pos = std::move(pos[(size_t)g][c]); b->refs[c].tlen = std::move(tlen[(size_t)g][c]); }
+            }
+            b->n_records = n_records;
+            b->n_kept = kept[(size_t)g];
+            out[g] = b;
+        }
+    }
+};
+
+struct SplitRun {                   // consecutive data lines of one chromosome: all of them counted, the assigned ones kept
+    std::string name;
+    std::vector<int32_t> start, end, group;
+    int64_t max_end = 0, n_data = 0;
+};
+struct SplitSliceOut {
+    std::vector<SplitRun> runs;
+    size_t n_lines = 0;
+    int bad = 0;
+};
+
+// parse_slice with split_line.  bc_count (may be null) is shared by the slices: relaxed atomic adds, the sum does not depend on the order
+inline void parse_slice_split(const unsigned char *p, size_t a, size_t b, bool open_end, const SplitTable *tb, int64_t *bc_count, SplitSliceOut *out) {
+    SplitRun *run = nullptr;
+    while (a < b) {
+        const unsigned char *nl = (const unsigned char *)std::memchr(p + a, '\n', b - a);
+        size_t e = nl ? (size_t)(nl - p) : b;
+        const size_t next = nl ? e + 1 : b;
+        if (!nl && !open_end) break;
+        if (nl && e > a && p[e - 1] == '\r') --e;
+        ++out->n_lines;
+        uint32_t nlen = 0;
+        int32_t s = 0, t = 0, bc = -1;
+        const int kind = split_line(p + a, e - a, *tb, &nlen, &s, &t, &bc);
+        if (kind > LINE_DATA) { out->bad = kind; return; }
+        if (kind == LINE_DATA) {
+            if (!run || run->name.size() != nlen || std::memcmp(run->name.data(), p + a, nlen) != 0) {
+                out->runs.emplace_back();
+                run = &out->runs.back();
+                run->name.assign((const char *)p + a, nlen);
+            }
+            ++run->n_data;
+            if (t > run->max_end) run->max_end = t;
+            if (bc >= 0) {
+                run->start.push_back(s);
+                run->end.push_back(t);
+                run->group.push_back(tb->group[bc]);
+                if (bc_count) __atomic_fetch_add(&bc_count[bc], (int64_t)1, __ATOMIC_RELAXED);
+            }
+        }
+        a = next;
+    }
+}
+
+// parse_text with split_line: the same slices, merged in file order
+inline bool parse_text_split(const unsigned char *p, size_t n, bool open_end, int n_threads, const SplitTable &tb, int64_t *bc_count, SplitBuilder &sb,
+                             unsigned long long *lines, std::string &err) {
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_threads), n / 256));
+    std::vector<size_t> cut((size_t)T + 1, n);
+    cut[0] = 0;
+    for (int t = 1; t < T; ++t) {
+        const size_t at = std::max(cut[(size_t)t - 1], n * (size_t)t / (size_t)T);
+        const unsigned char *nl = at < n ? (const unsigned char *)std::memchr(p + at, '\n', n - at) : nullptr;
+        cut[(size_t)t] = nl ? (size_t)(nl - p) + 1 : n;
+    }
+    std::vector<SplitSliceOut> out((size_t)T);
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t) th.emplace_back(parse_slice_split, p, cut[(size_t)t], cut[(size_t)t + 1], open_end, &tb, bc_count, &out[(size_t)t]);
+    parse_slice_split(p, cut[0], cut[1], open_end, &tb, bc_count, &out[0]);
+    for (auto &x : th) x.join();
+    for (auto &so : out) {
+        *lines += so.n_lines;
+        if (so.bad) { err = "line " + std::to_string(*lines) + ": " + reason_text(so.bad); return false; }
+        for (auto &r : so.runs) {
+            const int c = sb.chrom(r.name, r.max_end, r.n_data);
+            for (size_t k = 0; k < r.start.size(); ++k) sb.append(r.group[k], c, r.start[k], r.end[k]);
+        }
+    }
+    return true;
+}
+
+// natac_frag_split's host path: out[n_groups] handles, or false + err and nothing
+inline bool decode_split(const char *path, int n_threads, const SplitTableHost &th, Bam **out, int64_t *bc_count, int64_t *n_unassigned, std::string &err,
+                         size_t window = (size_t)48 << 20) {
+    SplitBuilder sb(th.n_groups);
+    const SplitTable tb = th.view();
+    if (bc_count) std::fill(bc_count, bc_count + tb.n_barcodes, (int64_t)0);
+    const bool ok = stream_text(path, n_threads, err, window, [&](const unsigned char *p, size_t n, bool open_end, int threads, unsigned long long *lines,
+                                                                  std::string &e) { return parse_text_split(p, n, open_end, threads, tb, bc_count, sb, lines, e); });
+    if (!ok) return false;
+    sb.finish(out);
+    if (n_unassigned) *n_unassigned = sb.n_records - sb.n_assigned;
+    return true;
 }
 
 }  // namespace natac_fragio

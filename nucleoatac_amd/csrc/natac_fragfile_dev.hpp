@@ -12,8 +12,19 @@
 // The host reads the few run names back (frag_gather_names), maps them to chromosome ids with the host decoder's dictionary (this is
 // where a chromosome that comes back gets its old id) and appends.  The bytes behind a window's last '\n' are carried to the front
 // of the next window.  Every device read is bounded by the window's length n, whatever the text holds.
+// Splitting by cell barcode (natac_frag_split_device; decode_device with a SplitJob) keeps (a) and runs its own kernels behind it:
+//   (b') frag_split_parse: frag_parse with natac_fragio::split_line, so every data line also gets its group (or -1) from the barcode
+//        table, and the exact per-barcode counts grow by one integer atomic per set of lanes of a wave that share a barcode.
+//   (c') frag_split_compact: the run tables over ALL data lines as in (c), and every line's run instead of the compacted start / end.
+//   (d') frag_split_hist / frag_scan / frag_split_scatter: a stable partition of the window's assigned lines by group.  One wave owns a
+//        tile of PART_LINES consecutive lines; the per-tile counts, stored group-major, scan into every (group, tile)'s first output
+//        slot; the wave then walks its tile in file order, 64 lines a round, and gives the lanes of a group consecutive slots in lane
+//        order.  The counts of every (group, run) segment come from the same histogram.  Integers only: nothing depends on order.
+//   The host gets start / end of the assigned lines only, in group-major order, and the segment counts, and appends segment by segment.
 // The host decoder answers instead (the caller runs it) for: a malformed line or a damaged file (so both paths give the same message
-// by construction), a window without any line end, more than MAX_RUNS runs in a window, a HIP failure.
+// by construction), a window without any line end, more than MAX_RUNS runs in a window, a HIP failure;
+// when splitting also for a line without a barcode field (malformed), a table of more than SPLIT_DEV_MAX_BARCODES barcodes and more than
+// SPLIT_MAX_SEGMENTS groups x runs in a window.
 #pragma once
 #include "natac_bam_dev.hpp"
 #include "natac_fragfile.hpp"
@@ -28,6 +39,10 @@ typedef unsigned long long u64;
 constexpr int TILE_T = 256;                 // lanes per workgroup
 constexpr int TILE_B = 16 * TILE_T;         // text bytes per workgroup in (a)
 constexpr unsigned int MAX_RUNS = 65536;    // per window
+constexpr int PART_T = 64;                  // one wave per partition tile: no barrier between the waves of a tile is ever needed
+constexpr int PART_LINES = 8192;            // lines per partition tile: 10 M lines are ~1,200 tiles, x 255 groups ~311 k counters to scan
+constexpr u64 SPLIT_MAX_SEGMENTS = 1u << 20;            // groups x runs per window (include/natac.h states it)
+constexpr long long SPLIT_DEV_MAX_BARCODES = 1 << 22;   // the table on the device: <= 32 MiB of slots, <= 1 GiB of bytes
 
 // exclusive prefix sum of v over the workgroup (blockDim.x a multiple of 64, at most 1024); *total = the workgroup's sum
 __device__ __forceinline__ u64 block_excl_scan(u64 v, u64 *total) {
@@ -101,6 +116,21 @@ __device__ __forceinline__ void line_span(const unsigned char *__restrict__ data
     if (!(open_tail && i + 1 == n_lines) && *e > *a && data[*e - 1] == '\r') --*e;
 }
 
+// does data line i (at a, chromosome field of nlen bytes) start a run: is there no data line before it, or one of another chromosome
+__device__ __forceinline__ bool starts_run(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 i, u64 n_lines, int open_tail, u64 a,
+                                           uint32_t nlen) {
+    bool differs = true;
+    for (u64 j = i; j-- > 0;) {                          // the previous line that is not skipped
+        u64 pa, pe;
+        line_span(data, ls, j, n_lines, open_tail, &pa, &pe);
+        if (pe == pa || data[pa] == '#') continue;
+        differs = pe - pa <= nlen || data[pa + nlen] != '\t';
+        for (uint32_t k = 0; k < nlen && !differs; ++k) differs = data[pa + k] != data[a + k];
+        break;
+    }
+    return differs;
+}
+
 // code[i] = (is data) << 32 | (starts a run); status[0] |= 1 for a malformed line
 __global__ void __launch_bounds__(TILE_T) frag_parse(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 n_lines, int open_tail,
                                                      u64 *__restrict__ code, int *__restrict__ start, int *__restrict__ end, unsigned int *__restrict__ name_len,
@@ -115,15 +145,7 @@ __global__ void __launch_bounds__(TILE_T) frag_parse(const unsigned char *__rest
         const int kind = natac_fragio::parse_line(data + a, (size_t)(e - a), &nlen, &s, &t);
         if (kind > natac_fragio::LINE_DATA) atomicOr(&status[0], 1);
         if (kind == natac_fragio::LINE_DATA) {
-            bool differs = true;
-            for (u64 j = i; j-- > 0;) {                      // the previous line that is not skipped
-                u64 pa, pe;
-                line_span(data, ls, j, n_lines, open_tail, &pa, &pe);
-                if (pe == pa || data[pa] == '#') continue;
-                differs = pe - pa <= nlen || data[pa + nlen] != '\t';
-                for (uint32_t k = 0; k < nlen && !differs; ++k) differs = data[pa + k] != data[a + k];
-                break;
-            }
+            const bool differs = starts_run(data, ls, i, n_lines, open_tail, a, nlen);
             c = (1ull << 32) | (differs ? 1ull : 0ull);
             start[i] = s;
             end[i] = t;
@@ -137,11 +159,13 @@ __global__ void __launch_bounds__(TILE_T) frag_parse(const unsigned char *__rest
 }
 
 // block_off = the scanned block_sum.  Data line -> slot d (file order), run r; per run: first slot, name offset / length, largest end
-__global__ void __launch_bounds__(TILE_T) frag_compact(const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ code, const int *__restrict__ start,
-                                                       const int *__restrict__ end, const unsigned int *__restrict__ name_len, const u64 *__restrict__ block_off,
-                                                       u64 n_data, unsigned int n_runs, int *__restrict__ o_start, int *__restrict__ o_end,
-                                                       u64 *__restrict__ run_first, u64 *__restrict__ run_name, unsigned int *__restrict__ run_nlen,
-                                                       int *__restrict__ run_max) {
+// (SPLIT: line_run[i] = the run of line i, -1 for a line that is no data line, instead of o_start / o_end)
+template <bool SPLIT>
+__device__ __forceinline__ void compact_body(const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ code, const int *__restrict__ start,
+                                             const int *__restrict__ end, const unsigned int *__restrict__ name_len, const u64 *__restrict__ block_off,
+                                             u64 n_data, unsigned int n_runs, int *__restrict__ o_start, int *__restrict__ o_end,
+                                             u64 *__restrict__ run_first, u64 *__restrict__ run_name, unsigned int *__restrict__ run_nlen,
+                                             int *__restrict__ run_max, int *__restrict__ line_run) {
     const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
     const u64 c = i < n_lines ? code[i] : 0ull;
     u64 total;
@@ -150,10 +174,13 @@ __global__ void __launch_bounds__(TILE_T) frag_compact(const u64 *__restrict__ l
     const unsigned int r = (unsigned int)(ex & 0xffffffffull) + (unsigned int)(c & 1ull) - 1u;      // a data line's run (the first data line starts run 0)
     const bool is_data = (c >> 32) != 0 && d < n_data && r < n_runs;
     int en = 0;
+    if constexpr (SPLIT) { if (i < n_lines) line_run[i] = is_data ? (int)r : -1; }
     if (is_data) {
         en = end[i];
-        o_start[d] = start[i];
-        o_end[d] = en;
+        if constexpr (!SPLIT) {
+            o_start[d] = start[i];
+            o_end[d] = en;
+        }
         if (c & 1ull) { run_first[r] = d; run_name[r] = ls[i]; run_nlen[r] = name_len[i]; }
     }
     // largest end per run: one atomic per wave where the wave's data lines share a run (nearly every wave of a sorted file)
@@ -169,6 +196,148 @@ __global__ void __launch_bounds__(TILE_T) frag_compact(const u64 *__restrict__ l
     } else if (is_data) atomicMax(&run_max[r], en);
 }
 
+__global__ void __launch_bounds__(TILE_T) frag_compact(const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ code, const int *__restrict__ start,
+                                                       const int *__restrict__ end, const unsigned int *__restrict__ name_len, const u64 *__restrict__ block_off,
+                                                       u64 n_data, unsigned int n_runs, int *__restrict__ o_start, int *__restrict__ o_end,
+                                                       u64 *__restrict__ run_first, u64 *__restrict__ run_name, unsigned int *__restrict__ run_nlen,
+                                                       int *__restrict__ run_max) {
+    compact_body<false>(ls, n_lines, code, start, end, name_len, block_off, n_data, n_runs, o_start, o_end, run_first, run_name, run_nlen, run_max, nullptr);
+}
+
+// ---- the split by barcode ----
+// the lanes of this wave that are `valid` and hold the same key (its low nbits); 0 for a lane that is not valid.  Every lane of the wave calls it.
+__device__ __forceinline__ u64 wave_peers(unsigned int key, bool valid, int nbits) {
+    u64 m = __ballot(valid);
+    for (int b = 0; b < nbits; ++b) {
+        const bool bit = (key >> b) & 1u;
+        const u64 set = __ballot(bit);
+        m &= bit ? set : ~set;
+    }
+    return valid ? m : 0ull;
+}
+
+// frag_parse by natac_fragio::split_line.  grp[i] = the group of line i, -1 for a line that is no data line or is unassigned.  bc_count
+// lives across windows; bc_bits = the bits an index into the table takes.  Text is read inside the line's span (so inside [0, n)), the
+// table inside its sizes (barcode_lookup).
+__global__ void __launch_bounds__(TILE_T) frag_split_parse(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 n_lines, int open_tail,
+                                                           natac_fragio::SplitTable tb, int bc_bits, u64 *__restrict__ code, int *__restrict__ start,
+                                                           int *__restrict__ end, unsigned int *__restrict__ name_len, int *__restrict__ grp,
+                                                           u64 *__restrict__ bc_count, u64 *__restrict__ block_sum, int *__restrict__ status) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    u64 c = 0;
+    int32_t bc = -1;
+    if (i < n_lines) {
+        u64 a, e;
+        line_span(data, ls, i, n_lines, open_tail, &a, &e);
+        uint32_t nlen = 0;
+        int32_t s = 0, t = 0;
+        const int kind = natac_fragio::split_line(data + a, (size_t)(e - a), tb, &nlen, &s, &t, &bc);
+        if (kind > natac_fragio::LINE_DATA) atomicOr(&status[0], 1);
+        if (kind == natac_fragio::LINE_DATA) {
+            const bool differs = starts_run(data, ls, i, n_lines, open_tail, a, nlen);
+            c = (1ull << 32) | (differs ? 1ull : 0ull);
+            start[i] = s;
+            end[i] = t;
+            name_len[i] = nlen;
+        } else bc = -1;
+        if (bc >= (int32_t)tb.n_barcodes) bc = -1;
+        code[i] = c;
+        grp[i] = bc >= 0 ? tb.group[bc] : -1;
+    }
+    // one integer atomic per set of lanes that share a barcode (duplicate lines, one cell's neighbouring fragments)
+    const u64 peers = wave_peers((unsigned int)bc, bc >= 0, bc_bits);
+    if (bc >= 0 && (int)(threadIdx.x & 63) == __ffsll((long long)peers) - 1) atomicAdd(&bc_count[bc], (u64)__popcll(peers));
+    u64 total;
+    block_excl_scan(c, &total);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(TILE_T) frag_split_compact(const u64 *__restrict__ ls, u64 n_lines, const u64 *__restrict__ code, const int *__restrict__ end,
+                                                             const unsigned int *__restrict__ name_len, const u64 *__restrict__ block_off, u64 n_data,
+                                                             unsigned int n_runs, u64 *__restrict__ run_first, u64 *__restrict__ run_name,
+                                                             unsigned int *__restrict__ run_nlen, int *__restrict__ run_max, int *__restrict__ line_run) {
+    compact_body<true>(ls, n_lines, code, nullptr, end, name_len, block_off, n_data, n_runs, nullptr, nullptr, run_first, run_name, run_nlen, run_max, line_run);
+}
+
+// is line i an assigned data line: its group in g, its run in r
+__device__ __forceinline__ bool split_line_of(const int *__restrict__ grp, const int *__restrict__ line_run, u64 i, u64 hi, int G, unsigned int n_runs, int *g,
+                                              int *r) {
+    *g = -1;
+    *r = -1;
+    if (i >= hi) return false;
+    *g = grp[i];
+    *r = line_run[i];
+    return *g >= 0 && *g < G && *r >= 0 && (unsigned int)*r < n_runs;
+}
+
+// One wave per tile of PART_LINES lines.  tile_hist[g * n_tiles + tile] = the tile's lines of group g (group-major: its scan is the output
+// order); seg_cnt[g * n_runs + r] += the tile's lines of group g in run r -- from the histogram where the tile lies in one run (nearly
+// every tile of a sorted file), else one atomic per set of lanes that share (group, run).
+__global__ void __launch_bounds__(PART_T) frag_split_hist(const int *__restrict__ grp, const int *__restrict__ line_run, u64 n_lines, int G, unsigned int n_runs,
+                                                          u64 n_tiles, u64 *__restrict__ tile_hist, unsigned int *__restrict__ seg_cnt) {
+    __shared__ unsigned int hist[256];
+    const int lane = threadIdx.x;
+    for (int k = lane; k < 256; k += PART_T) hist[k] = 0u;
+    __syncthreads();
+    const u64 lo = (u64)blockIdx.x * PART_LINES, hi = min(n_lines, lo + (u64)PART_LINES);
+    int rmin = 0x7fffffff, rmax = -1;
+    for (u64 base = lo; base < hi; base += PART_T) {
+        int g, r;
+        if (split_line_of(grp, line_run, base + lane, hi, G, n_runs, &g, &r)) {
+            atomicAdd(&hist[g], 1u);
+            rmin = min(rmin, r);
+            rmax = max(rmax, r);
+        }
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        rmin = min(rmin, __shfl_xor(rmin, k, 64));
+        rmax = max(rmax, __shfl_xor(rmax, k, 64));
+    }
+    __syncthreads();
+    for (int k = lane; k < G; k += PART_T) tile_hist[(u64)k * n_tiles + blockIdx.x] = (u64)hist[k];
+    if (rmax < 0) return;                                // no assigned line in this tile
+    if (rmin == rmax) {
+        for (int k = lane; k < G; k += PART_T)
+            if (hist[k]) atomicAdd(&seg_cnt[(u64)k * n_runs + (unsigned int)rmin], hist[k]);
+        return;
+    }
+    for (u64 base = lo; base < hi; base += PART_T) {     // the tile spans runs: (group, run) is a key of 8 + 16 bits (MAX_RUNS)
+        int g, r;
+        const bool valid = split_line_of(grp, line_run, base + lane, hi, G, n_runs, &g, &r);
+        const u64 peers = wave_peers(((unsigned int)r << 8) | ((unsigned int)g & 0xffu), valid, 24);
+        if (valid && lane == __ffsll((long long)peers) - 1) atomicAdd(&seg_cnt[(u64)g * n_runs + (unsigned int)r], (unsigned int)__popcll(peers));
+    }
+}
+
+// tile_off = the scanned tile_hist.  The wave walks its tile in file order, 64 lines a round: the lanes of one group take consecutive
+// slots behind the group's running offset, in lane order, so every group keeps file order (a stable partition).
+__global__ void __launch_bounds__(PART_T) frag_split_scatter(const int *__restrict__ grp, const int *__restrict__ line_run, const int *__restrict__ start,
+                                                             const int *__restrict__ end, u64 n_lines, int G, unsigned int n_runs, u64 n_tiles,
+                                                             const u64 *__restrict__ tile_off, u64 n_assigned, int *__restrict__ o_start,
+                                                             int *__restrict__ o_end) {
+    __shared__ u64 next[256];
+    const int lane = threadIdx.x;
+    for (int k = lane; k < 256; k += PART_T) next[k] = k < G ? tile_off[(u64)k * n_tiles + blockIdx.x] : 0ull;
+    __syncthreads();
+    const u64 lo = (u64)blockIdx.x * PART_LINES, hi = min(n_lines, lo + (u64)PART_LINES);
+    for (u64 base = lo; base < hi; base += PART_T) {     // (the trip count is the same for every lane)
+        int g, r;
+        const bool valid = split_line_of(grp, line_run, base + lane, hi, G, n_runs, &g, &r);
+        const u64 peers = wave_peers((unsigned int)g, valid, 8);
+        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
+        const u64 off = valid ? next[g] : 0ull;
+        __syncthreads();
+        if (valid && rank == 0) next[g] = off + (u64)__popcll(peers);
+        __syncthreads();
+        const u64 d = off + (u64)rank;
+        if (valid && d < n_assigned) {
+            o_start[d] = start[base + lane];
+            o_end[d] = end[base + lane];
+        }
+    }
+}
+
 // names[r * 256 ...] = the name of run r (at most 255 bytes: parse_line's rule), read inside [0, n)
 __global__ void __launch_bounds__(64) frag_gather_names(const unsigned char *__restrict__ data, u64 n, const u64 *__restrict__ run_name,
                                                         const unsigned int *__restrict__ run_nlen, unsigned int n_runs, unsigned char *__restrict__ names) {
@@ -179,8 +348,17 @@ __global__ void __launch_bounds__(64) frag_gather_names(const unsigned char *__r
     for (unsigned int k = 0; k < len && a + k < n; ++k) names[(u64)r * 256 + k] = data[a + k];
 }
 
+// what a split adds to decode_device: the table, the builder both paths share and the per-barcode counts (table->group.size() of them)
+struct SplitJob {
+    const natac_fragio::SplitTableHost *table;
+    natac_fragio::SplitBuilder *sb;
+    std::vector<int64_t> bc_count;
+};
+
 // Returns the same object as natac_fragio::decode, or nullptr: the host decoder answers (`why` says what stopped the device path).
-inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std::string &why, size_t window_bytes = (size_t)1 << 30) {
+// With `split` the returned object is empty (a token of success): the groups are in split->sb, the counts in split->bc_count.
+inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std::string &why, size_t window_bytes = (size_t)1 << 30,
+                                       SplitJob *split = nullptr) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { why = std::string("cannot open ") + path; return nullptr; }
     struct stat sb;
@@ -193,7 +371,11 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
     natac_bamio::Bam *bam = new natac_bamio::Bam();
     natac_fragio::Builder bd(bam);
     DevBuf d_raw, d_mem, d_data[2], d_status, d_queue, d_crc, d_tile, d_ls, d_code, d_start, d_end, d_nlen, d_bsum, d_total, d_ostart, d_oend, d_rfirst,
-        d_rname, d_rnlen, d_rmax, d_names;
+        d_rname, d_rnlen, d_rmax, d_names, d_tb_bytes, d_tb_off, d_tb_group, d_tb_slot, d_bcc, d_grp, d_lrun, d_thist, d_seg;
+    natac_fragio::SplitTable dev_tb{};
+    int bc_bits = 1, G = 0;
+    std::vector<unsigned int> h_seg;
+    std::vector<int> run_chrom;
     hipStream_t aux[3] = {nullptr, nullptr, nullptr};
     std::vector<Member> mem;
     std::vector<int> h_start, h_end, h_rmax;
@@ -219,7 +401,25 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
     }
     for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
     FRAGDEV_HIP(d_status.reserve(4 * sizeof(int)));
-    FRAGDEV_HIP(d_total.reserve(2 * sizeof(u64)));
+    FRAGDEV_HIP(d_total.reserve(4 * sizeof(u64)));
+    if (split) {                                         // the table goes up once
+        const natac_fragio::SplitTableHost &t = *split->table;
+        G = t.n_groups;
+        while (bc_bits < 32 && ((size_t)1 << bc_bits) < t.group.size()) ++bc_bits;
+        FRAGDEV_HIP(d_tb_bytes.reserve(t.bytes.size()));
+        FRAGDEV_HIP(d_tb_off.reserve(t.off.size() * sizeof(uint32_t)));
+        FRAGDEV_HIP(d_tb_group.reserve(t.group.size() * sizeof(int32_t)));
+        FRAGDEV_HIP(d_tb_slot.reserve(t.slot.size() * sizeof(uint32_t)));
+        FRAGDEV_HIP(d_bcc.reserve(t.group.size() * sizeof(u64)));
+        FRAGDEV_HIP(hipMemcpyAsync(d_tb_bytes.p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipMemcpyAsync(d_tb_off.p, t.off.data(), t.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipMemcpyAsync(d_tb_group.p, t.group.data(), t.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipMemcpyAsync(d_tb_slot.p, t.slot.data(), t.slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        FRAGDEV_HIP(hipMemsetAsync(d_bcc.p, 0, t.group.size() * sizeof(u64), stream));
+        FRAGDEV_HIP(hipStreamSynchronize(stream));
+        dev_tb = natac_fragio::SplitTable{(const unsigned char *)d_tb_bytes.p, (const uint32_t *)d_tb_off.p, (const int32_t *)d_tb_group.p,
+                                          (const uint32_t *)d_tb_slot.p, (uint32_t)t.group.size(), (uint32_t)t.slot.size(), t.hash_mask};
+    }
     {
         std::vector<unsigned int> t8(8 * 256);
         natac_bamdev::crc32_slice8_tables(t8.data());
@@ -358,8 +558,15 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
                 FRAGDEV_HIP(d_end.reserve((size_t)n_lines * sizeof(int)));
                 FRAGDEV_HIP(d_nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
                 FRAGDEV_HIP(d_bsum.reserve((size_t)blocks * sizeof(u64)));
-                hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines, open_tail,
-                                   (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p, (int *)d_status.p);
+                if (split) {
+                    FRAGDEV_HIP(d_grp.reserve((size_t)n_lines * sizeof(int)));
+                    hipLaunchKernelGGL(frag_split_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
+                                       open_tail, dev_tb, bc_bits, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (int *)d_grp.p,
+                                       (u64 *)d_bcc.p, (u64 *)d_bsum.p, (int *)d_status.p);
+                } else
+                    hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
+                                       open_tail, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p,
+                                       (int *)d_status.p);
                 hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_bsum.p, blocks, (u64 *)d_total.p + 1);
                 u64 packed = 0;
                 FRAGDEV_HIP(hipMemcpyAsync(&packed, (u64 *)d_total.p + 1, sizeof packed, hipMemcpyDeviceToHost, stream));
@@ -369,10 +576,70 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
                 const u64 n_data = packed >> 32, n_runs = packed & 0xffffffffull;
                 if (n_data > n_lines || n_runs > n_data || cur > n) return give_up("counts out of range");
                 if (n_runs > MAX_RUNS) return give_up("more than 65,536 chromosome runs in a window");
+                if (split && n_runs * (u64)G > SPLIT_MAX_SEGMENTS) return give_up("more than 1,048,576 groups x chromosome runs in a window");
                 if (open_tail) cur = n;
                 lap(t_parse);
                 // ---- (c) compaction, the run names, and the append on the host
-                if (n_data) {
+                if (n_data && split) {
+                    FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
+                    FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
+                    FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
+                    FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
+                    FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
+                    FRAGDEV_HIP(d_lrun.reserve((size_t)n_lines * sizeof(int)));
+                    const u64 n_tiles = (n_lines + PART_LINES - 1) / PART_LINES, n_seg = n_runs * (u64)G;
+                    FRAGDEV_HIP(d_thist.reserve((size_t)(n_tiles * (u64)G) * sizeof(u64)));
+                    FRAGDEV_HIP(d_seg.reserve((size_t)n_seg * sizeof(unsigned int)));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                    FRAGDEV_HIP(hipMemsetAsync(d_seg.p, 0, (size_t)n_seg * sizeof(unsigned int), stream));
+                    hipLaunchKernelGGL(frag_split_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
+                                       (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data, (unsigned int)n_runs,
+                                       (u64 *)d_rfirst.p, (u64 *)d_rname.p, (unsigned int *)d_rnlen.p, (int *)d_rmax.p, (int *)d_lrun.p);
+                    hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
+                                       (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
+                    hipLaunchKernelGGL(frag_split_hist, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p, n_lines, G,
+                                       (unsigned int)n_runs, n_tiles, (u64 *)d_thist.p, (unsigned int *)d_seg.p);
+                    hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_thist.p, n_tiles * (u64)G, (u64 *)d_total.p + 2);
+                    u64 n_assigned = 0;
+                    FRAGDEV_HIP(hipMemcpyAsync(&n_assigned, (u64 *)d_total.p + 2, sizeof n_assigned, hipMemcpyDeviceToHost, stream));
+                    h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256); h_seg.resize((size_t)n_seg);
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(h_seg.data(), d_seg.p, (size_t)n_seg * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipStreamSynchronize(stream));
+                    if (n_assigned > n_data) return give_up("counts out of range");
+                    if (n_assigned) {                    // unassigned lines stay on the device
+                        FRAGDEV_HIP(d_ostart.reserve((size_t)n_assigned * sizeof(int)));
+                        FRAGDEV_HIP(d_oend.reserve((size_t)n_assigned * sizeof(int)));
+                        hipLaunchKernelGGL(frag_split_scatter, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p,
+                                           (const int *)d_start.p, (const int *)d_end.p, n_lines, G, (unsigned int)n_runs, n_tiles, (const u64 *)d_thist.p,
+                                           n_assigned, (int *)d_ostart.p, (int *)d_oend.p);
+                        h_start.resize(n_assigned); h_end.resize(n_assigned);
+                        FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipStreamSynchronize(stream));
+                    }
+                    run_chrom.resize(n_runs);
+                    for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                        const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
+                        if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
+                        run_chrom[r] = split->sb->chrom(std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), h_rmax[r], (int64_t)(b - a));
+                    }
+                    u64 at = 0;                          // the segments, group-major as the partition wrote them
+                    for (int g = 0; g < G; ++g)
+                        for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                            const u64 cnt = h_seg[(size_t)g * (size_t)n_runs + r];
+                            if (cnt > n_assigned - at) return give_up("segment table out of range");
+                            for (u64 k = at; k < at + cnt; ++k) split->sb->append(g, run_chrom[r], h_start[(size_t)k], h_end[(size_t)k]);
+                            at += cnt;
+                        }
+                    if (at != n_assigned) return give_up("segment table out of range");
+                } else if (n_data) {
                     FRAGDEV_HIP(d_ostart.reserve((size_t)n_data * sizeof(int)));
                     FRAGDEV_HIP(d_oend.reserve((size_t)n_data * sizeof(int)));
                     FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
@@ -428,6 +695,13 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
                      t_read, t_scan, t_inflate, t_lines, t_parse, t_out);
 #undef FRAGDEV_HIP
     if (pend != 0) return give_up("bytes left behind the last window");
+    if (split) {
+        std::vector<u64> h_bcc(split->table->group.size());
+        split->bc_count.resize(h_bcc.size());
+        const hipError_t e_ = hipMemcpy(h_bcc.data(), d_bcc.p, h_bcc.size() * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e_ != hipSuccess) { (void)hipGetLastError(); return give_up(std::string("hipMemcpy of the barcode counts: ") + hipGetErrorString(e_)); }
+        for (size_t k = 0; k < h_bcc.size(); ++k) split->bc_count[k] = (int64_t)h_bcc[k];
+    }
     cleanup();
     return bam;
 }

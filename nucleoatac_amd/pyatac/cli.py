@@ -1,9 +1,11 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | split` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
 (for one, the nucpos.bed.gz of `nucleoatac nuc`) and `signal` the values of an indexed bedGraph track (any of the tracks written here)
-around such sites, per site and summed.  The other pyatac tools (vplot, bias_vplot) are not part of this package."""
+around such sites, per site and summed.  `split` is this package's own: it splits a single-cell fragment file by cell barcode into one
+store per cell group (a cluster, a sample, a whitelist) in one pass, each written as .npz or as a fragment file that every command above
+takes through --bam.  The other pyatac tools (vplot, bias_vplot) are not part of this package."""
 import argparse
 import sys
 
@@ -114,6 +116,17 @@ def add_signal_parser(sub):
     p.add_argument("--norm", action="store_true", default=False, help="normalize aggregate track by number of intervals")
 
 
+def add_split_parser(sub):
+    p = sub.add_parser("split", help="split a single-cell fragment file by cell barcode into one store per cell group")
+    p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
+    p.add_argument("--groups", metavar="table", required=True,
+                   help="TAB-separated: barcode, group (without a second column every barcode listed is in the group 'selected')")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the fragment file's name without its suffixes")
+    p.add_argument("--format", choices=("npz", "fragments"), default="npz",
+                   help="Write every group as BASE.<group>.npz (default) or as BASE.<group>.tsv.gz with its .tbi")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
@@ -130,6 +143,7 @@ def pyatac_parser():
     add_counts_parser(sub)
     add_nucleotide_parser(sub)
     add_signal_parser(sub)
+    add_split_parser(sub)
     return parser
 
 
@@ -195,6 +209,15 @@ def pyatac_main(args):
             get_signal(args)
         except (SignalError, BedColumnError) as e:
             sys.stderr.write("pyatac signal: %s\n" % e)
+            return 1
+    elif args.call == "split":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError, split_cells
+        print("---------Splitting fragments by cell group---------------------------------------")
+        try:
+            split_cells(args)
+        except (CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac split: %s\n" % e)
             return 1
     return 0
 

@@ -19,7 +19,8 @@ FRAGMENT_SUFFIXES = (".tsv", ".tsv.gz", ".bed", ".bed.gz")      # names Fragment
 # the fixed reason per cause of a malformed fragment line (csrc/natac_fragfile.hpp: reason_text)
 _FRAG_REASONS = dict(fields="fewer than three tab-separated fields", empty="empty chromosome name",
                      long="chromosome name longer than 255 bytes", number="start / end is not a number",
-                     range="start / end out of range (more than 2147483647)", order="end before start")
+                     range="start / end out of range (more than 2147483647)", order="end before start",
+                     barcode="no barcode field")      # (only when splitting by barcode)
 
 
 class FragmentStore(object):
@@ -166,7 +167,7 @@ class FragmentStore(object):
         return FragmentStore(names, lens, pos, tl)
 
     @staticmethod
-    def from_fragments(path, n_threads=0, device=None):
+    def from_fragments(path, n_threads=0, device=None, barcodes=None):
         """A fragment file (fragments.tsv.gz of Cell Ranger ATAC, the ENCODE pipeline, chromap, sinto, SnapATAC / ArchR) read by the
         native decoder.  The format rule (include/natac.h states it, csrc/natac_fragfile.hpp: parse_line is it):
 
@@ -192,7 +193,13 @@ class FragmentStore(object):
         inflate and parse over line-aligned slices on the host cores.  Both give the same arrays.
         Measured on the MI355X box (tools/bench_bam.py 20000000 --fragments, one box): a 20 M-record BAM's 10.0 M kept reads as a fragment
         file (436 MB of text, 129 MB BGZF): device 0.15 s; host 0.26 s with 16 threads, 0.50 s with 4; the device decode of the BAM itself
-        (1.25 GB) 0.28 s."""
+        (1.25 GB) 0.28 s.
+
+        With `barcodes` (an iterable of cell barcodes) only the lines of those cells are kept: the one-group case of split_fragments,
+        under its rule (every data line then needs a fourth field)."""
+        if barcodes is not None:
+            barcodes = list(barcodes)
+            return FragmentStore.split_fragments(path, barcodes, [0] * len(barcodes), 1, n_threads=n_threads, device=device)[0][0]
         import ctypes as C
         from .. import _lib as L
         lib = L.load()
@@ -211,8 +218,71 @@ class FragmentStore(object):
         return FragmentStore._from_handle(lib, h)
 
     @staticmethod
-    def from_fragments_python(path):
-        """pure-Python restatement of the format rule of from_fragments, kept as an independent check of the native decoders"""
+    def split_fragments(path, barcodes, group_of, n_groups, n_threads=0, device=None):
+        """One pass over a fragment file that yields one FragmentStore per cell group (a cluster, a sample, a QC whitelist): per-cluster
+        pseudo-bulk without filtering the text once per cluster.  barcodes[k] (bytes or str, 1-255 bytes, distinct) belongs to group
+        group_of[k] in [0, n_groups).  Returns (stores, bc_count, n_unassigned): n_groups stores, the data lines per listed barcode
+        (int64) and the data lines in no group.  The split rule (include/natac.h states it, csrc/natac_fragfile.hpp: split_line is it):
+
+        - every line is validated exactly as by from_fragments; a data line with fewer than four fields is malformed as well
+          ("no barcode field", checked last);
+        - the barcode is the fourth field, compared byte for byte (no trimming, no case folding, a "-1" suffix is part of it); a line
+          whose barcode is empty, longer than 255 bytes or not listed is unassigned: validated, counted, in no group, no error;
+        - every store has the same chromosome list (first appearance over ALL data lines) and the same lengths (largest end over all
+          data lines), so groups are comparable; a chromosome on which a group has nothing is present and empty;
+        - a group's records are its lines in file order within each chromosome (then sorted stably by the FragmentStore, like any).
+
+        On a GPU box a BGZF file goes through natac_frag_split_device (csrc/natac_fragfile_dev.hpp): the barcode of every data line is
+        hashed, looked up and counted on the device and each window's assigned lines are partitioned by group there;
+        FragmentStore.last_frag_on_device tells whether the device answered (the host path answers inside the call for everything
+        from_fragments hands over, a line without a barcode field, a table of more than 4,194,304 barcodes and more than 1,048,576
+        groups x chromosome runs in a window).  Both paths give the same arrays.
+        Measured on the MI355X box (tools/bench_bam.py 20000000 --split, one run): 10.0 M lines, 9,000 of 10,000 cells listed, 127 MB BGZF,
+        into 1 / 16 / 255 groups: device 0.20 / 0.16 / 0.15 s; host 0.51 / 0.48 / 0.53 s with 16 threads, 1.06 / 1.17 / 1.27 s with 4; the
+        plain device decode of the same file 0.15 / 0.15 / 0.13 s."""
+        import ctypes as C
+        from .. import _lib as L
+        lib = L.load()
+        bcs = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+        group_of = np.ascontiguousarray(group_of, dtype=np.int32)
+        n_groups = int(n_groups)
+        if len(group_of) != len(bcs):
+            raise ValueError("barcodes and group_of differ in length")
+        if not 1 <= n_groups <= 255:                              # NATAC_SPLIT_MAX_GROUPS: the handle array below is sized by it
+            raise ValueError("n_groups must be in [1, 255]")
+        off = np.zeros(len(bcs) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in bcs], out=off[1:])
+        blob = np.frombuffer(b"".join(bcs) + b"\0", dtype=np.uint8)
+        handles = (C.c_void_p * n_groups)()
+        bc_count = np.zeros(len(bcs), dtype=np.int64)
+        n_un = C.c_int64(0)
+        table = (len(bcs), blob.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), group_of.ctypes.data_as(C.c_void_p), n_groups,
+                 C.cast(handles, C.c_void_p), bc_count.ctypes.data_as(C.c_void_p), C.cast(C.pointer(n_un), C.c_void_p))
+        if device is None:
+            from ..device import Context
+            device = os.environ.get("NATAC_DEVICE_BAM", "1") != "0" and Context.device_count() > 0
+        if device:
+            from .. import get_context
+            on_dev = C.c_int(0)
+            L.check(lib.natac_frag_split_device(get_context()._h, str(path).encode(), *table, C.byref(on_dev)))
+            FragmentStore.last_frag_on_device = bool(on_dev.value)
+        else:
+            L.check(lib.natac_frag_split(str(path).encode(), int(n_threads), *table))
+            FragmentStore.last_frag_on_device = False
+        stores, failed = [], None
+        for g in range(n_groups):                                 # (_from_handle closes its handle, also when it raises)
+            try:
+                stores.append(FragmentStore._from_handle(lib, C.c_void_p(handles[g])))
+            except BaseException as e:      # noqa: BLE001 -- the other handles are still closed, then it is raised
+                failed = failed or e
+        if failed is not None:
+            raise failed
+        return stores, bc_count, int(n_un.value)
+
+    @staticmethod
+    def _python_lines(path, need_barcode=False):
+        """the data lines of a fragment file by the format rule, restated in pure Python: (chrom, start, end, barcode) per data line;
+        barcode is None unless need_barcode (the split rule: a data line then needs a fourth field, checked last)"""
         with open(path, "rb") as fh:
             zipped = fh.read(2) == b"\x1f\x8b"
         with (gzip.open if zipped else open)(path, "rb") as fh:
@@ -220,7 +290,6 @@ class FragmentStore(object):
         open_end = lines[-1] != b""          # the last line has no "\n" (and keeps a "\r")
         if not open_end:
             lines.pop()
-        names, pos, tl, length = [], {}, {}, {}
 
         def bad(no, why):
             return ValueError("%s: line %d: %s" % (path, no, _FRAG_REASONS[why]))
@@ -247,7 +316,15 @@ class FragmentStore(object):
             end = coord(no, f[2])
             if end < start:
                 raise bad(no, "order")
-            c = f[0].decode()
+            if need_barcode and len(f) < 4:
+                raise bad(no, "barcode")
+            yield f[0].decode(), start, end, f[3] if need_barcode else None
+
+    @staticmethod
+    def from_fragments_python(path):
+        """pure-Python restatement of the format rule of from_fragments, kept as an independent check of the native decoders"""
+        names, pos, tl, length = [], {}, {}, {}
+        for c, start, end, _ in FragmentStore._python_lines(path):
             if c not in pos:
                 names.append(c)
                 pos[c], tl[c], length[c] = [], [], 0
@@ -256,6 +333,35 @@ class FragmentStore(object):
             length[c] = max(length[c], end)
         return FragmentStore(names, [length[c] for c in names], {c: np.array(pos[c], np.int64) for c in names},
                              {c: np.array(tl[c], np.int64) for c in names})
+
+    @staticmethod
+    def split_fragments_python(path, barcodes, group_of, n_groups):
+        """pure-Python restatement of the split rule of split_fragments, kept as an independent check of the native paths"""
+        bcs = [b.encode() if isinstance(b, str) else bytes(b) for b in barcodes]
+        index = {b: k for k, b in enumerate(bcs)}
+        if len(index) != len(bcs):
+            raise ValueError("a barcode is listed twice")
+        names, length = [], {}
+        pos = [{} for _ in range(n_groups)]
+        tl = [{} for _ in range(n_groups)]
+        bc_count = np.zeros(len(bcs), dtype=np.int64)
+        n_unassigned = 0
+        for c, start, end, bc in FragmentStore._python_lines(path, need_barcode=True):
+            if c not in length:
+                names.append(c)
+                length[c] = 0
+            length[c] = max(length[c], end)
+            k = index.get(bc)              # (an empty barcode and one longer than 255 bytes cannot be listed)
+            if k is None:
+                n_unassigned += 1
+                continue
+            bc_count[k] += 1
+            g = int(group_of[k])
+            pos[g].setdefault(c, []).append(start - 4)
+            tl[g].setdefault(c, []).append(end - start + 8)
+        stores = [FragmentStore(names, [length[c] for c in names], {c: np.array(pos[g].get(c, []), np.int64) for c in names},
+                                {c: np.array(tl[g].get(c, []), np.int64) for c in names}) for g in range(n_groups)]
+        return stores, bc_count, n_unassigned
 
     def save_fragments(self, path):
         """write the store as a fragment file (chrom, start = pos + 4, end = pos + tlen - 4 per line, in the store's order: chromosome

@@ -2,7 +2,10 @@
 proper pairs) on a synthetic coordinate-sorted BAM of N paired-end records with realistic record sizes (50-base reads, names of
 ~20 characters, one 50M cigar; BGZF members of 0xff00 bytes at zlib level 6 like samtools):  python tools/bench_bam.py 4000000
 With --fragments, after the BAM run: the fragment file of the same BAM's kept reads (chrom, start, end, a 16-base barcode, a count; the
-same members and level) through natac_frag_open_device and through natac_frag_open at 16 and at 4 threads, on the same box."""
+same members and level) through natac_frag_open_device and through natac_frag_open at 16 and at 4 threads, on the same box.
+With --split, after the BAM run: the same kept reads as a single-cell fragment file (barcodes drawn from a pool of 10,000 cells, 90 % of
+them listed, assigned round-robin to G = 1, 16 and 255 groups) through natac_frag_split_device, natac_frag_split at 16 and at 4 threads,
+and the plain device decode of that same file, in the same run."""
 import os
 import struct
 import sys
@@ -91,8 +94,51 @@ def bench_fragments(d, store):
               % (threads, n, same, dt, n / dt / 1e6, size / dt / 1e6, len(text) / dt / 1e6))
 
 
+def bench_split(d, store):
+    """per G four times: device split, host split at 16 and at 4 threads, the plain device decode of the same file"""
+    from nucleoatac_amd.device import Context
+    from nucleoatac_amd.pyatac.fragments import FragmentStore
+    rng = np.random.default_rng(2)
+    pool = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, (10000, 16), dtype=np.uint8)].view("S16").ravel()
+    pool = np.unique(pool)
+    cells = [c + b"-1" for c in pool.tolist()]
+    listed = cells[:len(cells) * 9 // 10]
+    parts = [b"# id=bench\n"]
+    for c in store.references:
+        start, end = (store.pos[c] + 4).tolist(), (store.pos[c] + store.tlen[c] - 4).tolist()
+        bc = pool[rng.integers(0, len(pool), len(start))].tolist()
+        row = c.encode() + b"\t%d\t%d\t%s-1\t1\n"
+        parts.append(b"".join([row % t for t in zip(start, end, bc)]))
+    text = b"".join(parts)
+    path = os.path.join(d, "cells.tsv.gz")
+    bgzf_write(path, text)
+    size, n = os.path.getsize(path), sum(len(store.pos[c]) for c in store.references)
+    print("single-cell fragment file: %d lines, %d cells (%d listed), %.0f MB of text, %.0f MB compressed" % (n, len(cells), len(listed), len(text) / 1e6, size / 1e6))
+    gpu = Context.device_count() > 0
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return out, time.perf_counter() - t0
+    if gpu:
+        FragmentStore.from_fragments(path, device=True)          # (the first call pays the first launches)
+    for G in (1, 16, 255):
+        group_of = [k % G for k in range(len(listed))]
+        row, ref = [], None
+        for threads, device in ([(0, True)] if gpu else []) + [(16, False), (4, False)]:
+            (stores, bc_count, n_un), dt = timed(lambda: FragmentStore.split_fragments(path, listed, group_of, G, n_threads=threads, device=device))
+            tag = ("device" if FragmentStore.last_frag_on_device else "device->host") if device else "host %d threads" % threads
+            sig = (n_un, int(bc_count.sum()), [sum(int(st.pos[c].sum()) for c in st.references) for st in stores])
+            ref = ref or sig
+            row.append("%s %.3f s%s" % (tag, dt, "" if sig == ref else " (DIFFERS)"))
+        if gpu:
+            _, dt = timed(lambda: FragmentStore.from_fragments(path, device=True))
+            row.append("plain device decode %.3f s" % dt)
+        print("split G=%d  %d lines, %d unassigned: %s" % (G, n, ref[0], ", ".join(row)))
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--fragments"]
+    args = [a for a in sys.argv[1:] if a not in ("--fragments", "--split")]
     n = int(args[0]) if args else 4_000_000
     from nucleoatac_amd.pyatac.fragments import FragmentStore
     d = tempfile.mkdtemp(prefix="natac_bam_")
@@ -120,6 +166,8 @@ def main():
                   % (threads or "auto", n, total, kept, dt, n / dt / 1e6, size / dt / 1e6, raw / dt / 1e6))
         if "--fragments" in sys.argv:
             bench_fragments(d, st)
+        if "--split" in sys.argv:
+            bench_split(d, st)
     finally:
         import shutil
         shutil.rmtree(d, ignore_errors=True)
