@@ -49,9 +49,10 @@ extern "C" {
  * 4: added natac_insertion_seq_counts / natac_base_counts for `pyatac pwm`; 5: added natac_run_ins_smooth / natac_run_center_cov and their
  * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
  * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`;
- * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device); the binding
+ * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device; 11: added
+ * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`); the binding
  * refuses another version */
-#define NATAC_ABI_VERSION 10
+#define NATAC_ABI_VERSION 11
 
 enum {
     NATAC_OK = 0,
@@ -326,6 +327,23 @@ int natac_base_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int32_t n_r
  * range search and the counting kernels. */
 int natac_region_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, int64_t n_regions, const int64_t *start,
                         const int64_t *end, int lower, int upper, int atac, int64_t *counts, double *kernel_ms);
+/* ---- the cell-by-region count matrix of one chromosome (this library's own; `pyatac cellcounts`) ----
+ * pos / tlen as natac_region_counts takes them, cell[n_frags] in [0, n_cells) the cell of every record (natac_bam_ref_cells), n_cells in
+ * [1, NATAC_SPLIT_MAX_BARCODES].  A record counts for a region EXACTLY by natac_region_counts' rule.  The result is CSR with one row per
+ * region, in the given order: row_ptr[n_regions + 1] is always written; within a row col (the cell index) is strictly ascending and val
+ * is the number of counting records of that cell, exact.  col == val == NULL with cap == 0 is a sizing call that writes row_ptr only;
+ * otherwise cap >= row_ptr[n_regions] entries of col and val must exist, and a smaller cap returns NATAC_E_ARG with col and val untouched
+ * (the sum of natac_region_counts bounds nnz, and so does the number of candidate records).  A row of more than 2^31 - 1 counting records
+ * is refused (NATAC_E_ARG).  The operands are checked on the host (NATAC_E_ARG names the record or region): pos non-decreasing, cell in
+ * range, end >= start.  n_regions == 0 or n_frags == 0 gives zeros and launches nothing.  Only integer atomics: the result is a pure
+ * function of the inputs.  Rows go by their number of counting records h (csrc/natac_cellcounts.hpp): h <= NATAC_CELLCOUNT_WAVE_MAX is
+ * sorted in the registers of one wave, h <= NATAC_CELLCOUNT_SHORT_MAX in the LDS of one workgroup, a longer row is counted into a dense
+ * array of n_cells counters, one such row at a time.  kernel_ms (may be NULL): device time of all kernels of the call. */
+#define NATAC_CELLCOUNT_WAVE_MAX 64
+#define NATAC_CELLCOUNT_SHORT_MAX 4096
+int natac_region_cell_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells,
+                             int64_t n_regions, const int64_t *start, const int64_t *end, int lower, int upper, int atac, int64_t *row_ptr,
+                             int64_t cap, int32_t *col, int32_t *val, double *kernel_ms);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows
@@ -536,6 +554,17 @@ int natac_frag_split(const char *path, int n_threads, int64_t n_barcodes, const 
  * *on_device (may be NULL) tells which one answered. */
 int natac_frag_split_device(natac_ctx *ctx, const char *path, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, const int32_t *bc_group,
                             int32_t n_groups, natac_bam **out, int64_t *bc_count, int64_t *n_unassigned, int *on_device);
+/* ---- a cell-tagged read: the one-group case of THE SPLIT RULE that also keeps which cell every kept record belongs to ----
+ * The table is natac_frag_split's without groups (the same limits, NATAC_SPLIT_MAX_BARCODES, and the same error for two equal barcodes).
+ * Every line is validated by split_line, with natac_frag_split's reasons and line numbers; a line whose barcode is empty, longer than
+ * 255 bytes or unlisted is unassigned and dropped (no error); every data line counts towards its chromosome's length.  *out is ONE handle
+ * (NULL on any error) whose kept records carry cell = the index of their barcode in the table: natac_bam_ref_cells copies the
+ * n_reads cell indices of a reference, in the order of natac_bam_ref_reads (file order within the chromosome).  bc_count / n_unassigned
+ * as natac_frag_split.  Host path only: the result does not depend on n_threads or NATAC_BAM_WINDOW.  natac_bam_ref_cells on a handle of
+ * any other open call is NATAC_E_ARG. */
+int natac_frag_open_cells(const char *path, int n_threads, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, natac_bam **out,
+                          int64_t *bc_count, int64_t *n_unassigned);
+int natac_bam_ref_cells(natac_bam *bam, int32_t ref, int32_t *cell);
 /* test entry: the device's raw-deflate decoder run on the host (one BGZF member payload -> isize bytes); returns its error code */
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize);
 

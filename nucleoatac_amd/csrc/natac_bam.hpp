@@ -24,11 +24,13 @@ struct Ref {
     std::string name;
     int64_t length = 0;
     std::vector<int64_t> pos, tlen;
+    std::vector<int32_t> cell;      // per record, only in a cell-tagged read of a fragment file (natac_frag_open_cells); empty otherwise
 };
 
 struct Bam {
     std::vector<Ref> refs;
     int64_t n_records = 0, n_kept = 0;
+    bool tagged = false;            // refs[].cell is filled (natac_frag_open_cells)
     std::string error;
 };
 

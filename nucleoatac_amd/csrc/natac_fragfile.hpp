@@ -8,6 +8,7 @@
 // Container by magic bytes: BGZF (the window reader of natac_bam.hpp), any other gzip (zlib, several members allowed), plain text.
 // Splitting by cell barcode (natac_frag_split): split_line below IS the rule of include/natac.h -- parse_line, then the fourth field looked
 // up in a SplitTable -- and is __host__ __device__ for the same reason.
+// The cell-tagged read (natac_frag_open_cells) is the one-group split that keeps, per kept record, the index of its barcode in the table.
 #pragma once
 #include "natac_bam.hpp"
 
@@ -372,14 +373,18 @@ struct SplitTableHost {
 
 // What both paths append to: ONE chromosome list (first appearance over all data lines, assigned or not) and one length per chromosome
 // (the largest end over all of its data lines) for every group; per group and chromosome the group's records in file order.
+// With `cells` (one group only) a third array per chromosome holds the table index of every kept record's barcode.
 struct SplitBuilder {
     int G;
+    bool cells;
+    std::vector<std::vector<int32_t>> cell;                          // [chromosome]
     std::unordered_map<std::string, int> ids;
     std::vector<std::string> names;
     std::vector<int64_t> length, kept;
     std::vector<std::vector<std::vector<int64_t>>> pos, tlen;        // [group][chromosome]
     int64_t n_records = 0, n_assigned = 0;
-    explicit SplitBuilder(int groups) : G(groups), kept((size_t)groups, 0), pos((size_t)groups), tlen((size_t)groups) {}
+    explicit SplitBuilder(int groups, bool keep_cells = false)
+        : G(groups), cells(keep_cells), kept((size_t)groups, 0), pos((size_t)groups), tlen((size_t)groups) {}
     int chrom(const std::string &name, int64_t max_end, int64_t n_lines) {      // a run of n_lines data lines on `name`
         auto it = ids.find(name);
         if (it == ids.end()) {
@@ -391,11 +396,15 @@ struct SplitBuilder {
         n_records += n_lines;
         return it->second;
     }
-    void append(int g, int c, int64_t start, int64_t end) {
+    void append(int g, int c, int64_t start, int64_t end, int32_t bc = 0) {
         auto &p = pos[(size_t)g], &t = tlen[(size_t)g];
         if (p.size() <= (size_t)c) { p.resize((size_t)c + 1); t.resize((size_t)c + 1); }
         p[(size_t)c].push_back(start - 4);
         t[(size_t)c].push_back(end - start + 8);
+        if (cells) {
+            if (cell.size() <= (size_t)c) cell.resize((size_t)c + 1);
+            cell[(size_t)c].push_back(bc);
+        }
         ++kept[(size_t)g];
         ++n_assigned;
     }
@@ -407,6 +416,7 @@ struct SplitBuilder {
                 b->refs[c].name = names[c];
                 b->refs[c].length = length[c];
                 if (c < pos[(size_t)g].size()) { b->refs[c].pos = std::move(pos[(size_t)g][c]); b->refs[c].tlen = std::move(tlen[(size_t)g][c]); }
+                if (cells && c < cell.size()) b->refs[c].cell = std::move(cell[c]);
             }
             b->n_records = n_records;
             b->n_kept = kept[(size_t)g];
@@ -417,7 +427,7 @@ struct SplitBuilder {
 
 struct SplitRun {                   // consecutive data lines of one chromosome: all of them counted, the assigned ones kept
     std::string name;
-    std::vector<int32_t> start, end, group;
+    std::vector<int32_t> start, end, group;      // group: the record's group, or (a cell-tagged read) the index of its barcode
     int64_t max_end = 0, n_data = 0;
 };
 struct SplitSliceOut {
@@ -426,8 +436,10 @@ struct SplitSliceOut {
     int bad = 0;
 };
 
-// parse_slice with split_line.  bc_count (may be null) is shared by the slices: relaxed atomic adds, the sum does not depend on the order
-inline void parse_slice_split(const unsigned char *p, size_t a, size_t b, bool open_end, const SplitTable *tb, int64_t *bc_count, SplitSliceOut *out) {
+// parse_slice with split_line.  bc_count (may be null) is shared by the slices: relaxed atomic adds, the sum does not depend on the order.
+// keep_bc: a run keeps the barcode's index where it keeps the barcode's group otherwise.
+inline void parse_slice_split(const unsigned char *p, size_t a, size_t b, bool open_end, const SplitTable *tb, int64_t *bc_count, bool keep_bc,
+                              SplitSliceOut *out) {
     SplitRun *run = nullptr;
     while (a < b) {
         const unsigned char *nl = (const unsigned char *)std::memchr(p + a, '\n', b - a);
@@ -451,7 +463,7 @@ inline void parse_slice_split(const unsigned char *p, size_t a, size_t b, bool o
             if (bc >= 0) {
                 run->start.push_back(s);
                 run->end.push_back(t);
-                run->group.push_back(tb->group[bc]);
+                run->group.push_back(keep_bc ? bc : tb->group[bc]);
                 if (bc_count) __atomic_fetch_add(&bc_count[bc], (int64_t)1, __ATOMIC_RELAXED);
             }
         }
@@ -472,24 +484,26 @@ inline bool parse_text_split(const unsigned char *p, size_t n, bool open_end, in
     }
     std::vector<SplitSliceOut> out((size_t)T);
     std::vector<std::thread> th;
-    for (int t = 1; t < T; ++t) th.emplace_back(parse_slice_split, p, cut[(size_t)t], cut[(size_t)t + 1], open_end, &tb, bc_count, &out[(size_t)t]);
-    parse_slice_split(p, cut[0], cut[1], open_end, &tb, bc_count, &out[0]);
+    for (int t = 1; t < T; ++t)
+        th.emplace_back(parse_slice_split, p, cut[(size_t)t], cut[(size_t)t + 1], open_end, &tb, bc_count, sb.cells, &out[(size_t)t]);
+    parse_slice_split(p, cut[0], cut[1], open_end, &tb, bc_count, sb.cells, &out[0]);
     for (auto &x : th) x.join();
     for (auto &so : out) {
         *lines += so.n_lines;
         if (so.bad) { err = "line " + std::to_string(*lines) + ": " + reason_text(so.bad); return false; }
         for (auto &r : so.runs) {
             const int c = sb.chrom(r.name, r.max_end, r.n_data);
-            for (size_t k = 0; k < r.start.size(); ++k) sb.append(r.group[k], c, r.start[k], r.end[k]);
+            if (sb.cells) for (size_t k = 0; k < r.start.size(); ++k) sb.append(0, c, r.start[k], r.end[k], r.group[k]);
+            else for (size_t k = 0; k < r.start.size(); ++k) sb.append(r.group[k], c, r.start[k], r.end[k]);
         }
     }
     return true;
 }
 
-// natac_frag_split's host path: out[n_groups] handles, or false + err and nothing
+// natac_frag_split's host path: out[n_groups] handles, or false + err and nothing.  cells: natac_frag_open_cells (a table of one group)
 inline bool decode_split(const char *path, int n_threads, const SplitTableHost &th, Bam **out, int64_t *bc_count, int64_t *n_unassigned, std::string &err,
-                         size_t window = (size_t)48 << 20) {
-    SplitBuilder sb(th.n_groups);
+                         size_t window = (size_t)48 << 20, bool cells = false) {
+    SplitBuilder sb(th.n_groups, cells);
     const SplitTable tb = th.view();
     if (bc_count) std::fill(bc_count, bc_count + tb.n_barcodes, (int64_t)0);
     const bool ok = stream_text(path, n_threads, err, window, [&](const unsigned char *p, size_t n, bool open_end, int threads, unsigned long long *lines,

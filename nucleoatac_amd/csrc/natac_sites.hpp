@@ -57,19 +57,22 @@ __global__ void __launch_bounds__(RC_BLOCK) natac_region_ranges(const long long 
     }
 }
 
+// THE COUNTING RULE for one record (natac_cellcounts.hpp asks the same function)
+__device__ __forceinline__ bool region_record_hit(long long p, long long t, long long s, long long e, int lower, int upper, int shift,
+                                                  int trim) {
+    const long long n = t - trim;
+    const long long l = p + shift;
+    const long long r = l + n - 1;
+    return n >= lower && n < upper && ((l >= s && l < e) || (r >= s && r < e));
+}
+
 // the records [f0, f1) that count for [s, e), over the lanes of one wave: every lane returns the wave's total
 __device__ __forceinline__ unsigned long long region_slice_count(const long long *__restrict__ pos, const long long *__restrict__ tlen,
                                                                  long long f0, long long f1, long long s, long long e, int lower,
                                                                  int upper, int shift, int trim, int lane) {
     unsigned long long total = 0;
     for (long long f = f0; f < f1; f += 64) {           // f0, f1 are wave-uniform: every lane takes part in every ballot
-        bool hit = false;
-        if (f + lane < f1) {
-            const long long n = tlen[f + lane] - trim;
-            const long long l = pos[f + lane] + shift;
-            const long long r = l + n - 1;
-            hit = n >= lower && n < upper && ((l >= s && l < e) || (r >= s && r < e));
-        }
+        const bool hit = f + lane < f1 && region_record_hit(pos[f + lane], tlen[f + lane], s, e, lower, upper, shift, trim);
         total += (unsigned long long)__popcll(__ballot(hit));
     }
     return total;

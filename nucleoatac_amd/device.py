@@ -359,6 +359,36 @@ class Context(object):
                                               int(upper), 1 if atac else 0, _ptr(out), C.byref(ms)))
         return (out, ms.value) if with_kernel_ms else out
 
+    def region_cell_counts(self, pos, tlen, cell, n_cells, starts, ends, lower=0, upper=500, atac=True, with_kernel_ms=False):
+        """the cell-by-region count matrix of one chromosome (natac_region_cell_counts) as CSR with one row per region, in the given
+        order: (indptr int64[n_regions + 1], indices int32[nnz], data int32[nnz]); within a row the cell indices ascend, data is the
+        number of records of that cell that count for the region by region_counts' rule, exact.  pos (sorted) / tlen / cell are the
+        chromosome's records as a cell-tagged FragmentStore holds them (FragmentStore.from_fragments_cells), cell in [0, n_cells).
+        with_kernel_ms: also return the device time of the call's kernels."""
+        p = np.ascontiguousarray(pos, dtype=np.int64)
+        t = np.ascontiguousarray(tlen, dtype=np.int64)
+        ce = np.ascontiguousarray(cell, dtype=np.int32)
+        st = np.ascontiguousarray(starts, dtype=np.int64)
+        en = np.ascontiguousarray(ends, dtype=np.int64)
+        if p.ndim != 1 or p.shape != t.shape or p.shape != ce.shape or st.ndim != 1 or st.shape != en.shape:
+            raise ValueError("pos / tlen / cell and starts / ends must be 1-d arrays of one length each")
+        # room for the entries: a row has at most as many as it has candidate records (the kernels' own search, natac_region_ranges:
+        # every record that can count lies in that range of the sorted pos) and at most n_cells
+        shift = 4 if atac else 0
+        a = np.searchsorted(p, st - max(int(upper), 1) - shift, "right")
+        b = np.searchsorted(p, en + max(0, 1 - int(lower)) - shift, "left")
+        cap = int(np.minimum(np.maximum(b - a, 0), max(int(n_cells), 1)).sum())
+        indptr = np.zeros(st.shape[0] + 1, dtype=np.int64)
+        col = np.empty(max(cap, 1), dtype=np.int32)
+        val = np.empty(max(cap, 1), dtype=np.int32)
+        ms = C.c_double(0)
+        L.check(self._lib.natac_region_cell_counts(self._h, p.shape[0], _ptr(p), _ptr(t), _ptr(ce), int(n_cells), st.shape[0], _ptr(st),
+                                                   _ptr(en), int(lower), int(upper), 1 if atac else 0, _ptr(indptr), col.shape[0],
+                                                   _ptr(col), _ptr(val), C.byref(ms)))
+        nnz = int(indptr[-1])
+        out = (indptr, col[:nnz].copy(), val[:nnz].copy())
+        return out + (ms.value,) if with_kernel_ms else out
+
     def site_seq_counts(self, seq, centers, minus, up, down, word=1, with_kernel_ms=False):
         """word counts of `pyatac nucleotide` (_nucleotideHelper, pyatac/get_nucleotide.py:19-38) around the sites of one chromosome:
         (M int64[4 or 16, up + down + 1], n = the sites whose window lies inside the chromosome), exact.  seq: the chromosome's bytes,

@@ -1,11 +1,13 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | split` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | split | cellcounts` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
 (for one, the nucpos.bed.gz of `nucleoatac nuc`) and `signal` the values of an indexed bedGraph track (any of the tracks written here)
 around such sites, per site and summed.  `split` is this package's own: it splits a single-cell fragment file by cell barcode into one
 store per cell group (a cluster, a sample, a whitelist) in one pass, each written as .npz or as a fragment file that every command above
-takes through --bam.  The other pyatac tools (vplot, bias_vplot) are not part of this package."""
+takes through --bam.  `cellcounts` is this package's own too: the cell-by-window count matrix of a single-cell fragment file (rows the BED
+windows, columns the barcodes of a table), sparse, as MatrixMarket text or .npz.  The other pyatac tools (vplot, bias_vplot) are not part of
+this package."""
 import argparse
 import sys
 
@@ -127,11 +129,28 @@ def add_split_parser(sub):
                    help="Write every group as BASE.<group>.npz (default) or as BASE.<group>.tsv.gz with its .tbi")
 
 
+def add_cellcounts_parser(sub):
+    p = sub.add_parser("cellcounts", help="cell-by-window fragment count matrix of a single-cell fragment file")
+    p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
+    p.add_argument("--bed", metavar="bed_file", required=True, help="Windows in which to compute counts: the rows of the matrix")
+    p.add_argument("--cells", metavar="table", required=True,
+                   help="TAB-separated table whose first column lists the barcodes: the columns of the matrix, in order of first appearance "
+                        "(the table `split --groups` takes; a group column is not used).  Barcodes are not discovered from the fragment "
+                        "file: lines of a barcode the table does not list are left out")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--lower", metavar="int", default=0, type=int, help="lower limit on insert size. Default is 0")
+    p.add_argument("--upper", metavar="int", default=500, type=int, help="upper limit on insert size.  Default is 500")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the bed file's name without its last extension")
+    p.add_argument("--format", choices=("mtx", "npz"), default="mtx",
+                   help="BASE.cellcounts.mtx.gz with .barcodes.tsv and .regions.bed (default) or BASE.cellcounts.npz (CSR arrays)")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
                                                                 "insertion, coverage and Tn5 bias tracks, fragment counts per window, "
-                                                                "nucleotide content and track signal around sites")
+                                                                "nucleotide content and track signal around sites; a single-cell fragment file "
+                                                                "split by cell group, and its cell-by-window count matrix")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -144,6 +163,7 @@ def pyatac_parser():
     add_nucleotide_parser(sub)
     add_signal_parser(sub)
     add_split_parser(sub)
+    add_cellcounts_parser(sub)
     return parser
 
 
@@ -218,6 +238,18 @@ def pyatac_main(args):
             split_cells(args)
         except (CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac split: %s\n" % e)
+            return 1
+    elif args.call == "cellcounts":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .chunk import BedColumnError
+        from .get_cellcounts import get_cellcounts
+        from .get_counts import CountsError
+        print("---------Getting the cell-by-window count matrix---------------------------------------")
+        try:
+            get_cellcounts(args)
+        except (CountsError, BedColumnError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac cellcounts: %s\n" % e)
             return 1
     return 0
 
