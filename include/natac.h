@@ -50,9 +50,10 @@ extern "C" {
  * tracks and profile slots for `pyatac ins` / `cov`; 6: added natac_run_pwm_track, its track and profile slot for `pyatac bias`; 7: added natac_region_counts
  * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`;
  * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device; 11: added
- * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`); the binding
+ * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
+ * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability); the binding
  * refuses another version */
-#define NATAC_ABI_VERSION 11
+#define NATAC_ABI_VERSION 12
 
 enum {
     NATAC_OK = 0,
@@ -151,9 +152,17 @@ int natac_set_vmat(natac_ctx *ctx, const double *mat, int lower, int upper, int 
 /* global insert-size distribution over [0, upper) used by BiasMat2D.normByInsertDist (chunkmat2d.py:154-156). */
 int natac_set_sizes(natac_ctx *ctx, const double *sizes, int upper);
 /* OccupancyCalcParams + OccupancyParameters (Occupancy.py:89-102, 175-193): nuc_probs / nfr_probs over
- * [0, upper) (already normalised), the alpha grid (np.linspace(0,1,101)), the chi2 cutoff, step (odd), flank. */
+ * [0, upper) (already normalised), the alpha grid (np.linspace(0,1,101)), the chi2 cutoff, step (odd), flank.
+ * With a model that has an nfr_prob of 0, a grid whose smallest positive alpha is below 2^-500 is refused (NATAC_E_ARG): the product
+ * alpha * probability of such a size could leave the fp64 range. */
 int natac_set_occ_model(natac_ctx *ctx, const double *nuc_probs, const double *nfr_probs, int upper,
                         const double *alphas, int n_alpha, double cutoff, int step, int flank);
+/* Which occupancy kernels the model of the last natac_set_occ_model takes (reads context fields, launches nothing).  *fast: 1 when the
+ * block-sum kernels natac_occ_gsum / natac_occ_decide run (the model qualifies and NATAC_OCC_GENERAL does not force natac_occ_mle), else 0;
+ * *rn: factors between two renormalisations in natac_occ_decide, 16 or 4, 0 when not fast; *zero_flags: the flags word natac_occ_decide
+ * gets (bit 0: some nuc_prob == 0, bit 1: some nfr_prob == 0 and the fast path treats such sizes).  Tests use it to assert that a model
+ * reaches the arm they are written for. */
+int natac_ctx_occ_route(natac_ctx *ctx, int32_t *fast, int32_t *rn, int32_t *zero_flags);
 
 /* ---- batches of packed chunks ---------------------------------------------------------- */
 /* Upload one batch (layout: nucleoatac_amd/packing.py).  bias_off/bias_log may be NULL (no FASTA: bias

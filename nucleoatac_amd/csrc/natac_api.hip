@@ -935,6 +935,15 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
     if (upper > 256) return fail(NATAC_E_ARG, "occupancy kernel supports upper <= 256 (got %d)", upper);
     if (step < 1 || flank < 0) return fail(NATAC_E_ARG, "bad step/flank");
     if (step % 2 == 0) step -= 1; /* Occupancy.py:190-191 */
+    double apos = 1.0;               // smallest positive alpha
+    for (int a = 0; a < n_alpha; ++a)
+        if (alphas[a] > 0.0 && alphas[a] < apos) apos = alphas[a];
+    // a fragment whose size has nfr_prob 0 contributes the factor alpha * probability: natac_occ_mle (which renormalises after every such
+    // factor) is exact while that product is >= 2^-1021, so with such a model alphas below 2^-500 are refused (probabilities >= 2^-500 remain)
+    if (apos < std::ldexp(1.0, -500))
+        for (int j = 0; j < upper; ++j)
+            if (nfr_probs[j] == 0.0)
+                return fail(NATAC_E_ARG, "occupancy model with a zero nfr probability: the smallest positive alpha must be >= 2^-500 (got %g)", apos);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
     c->d_nucp.reset(); c->d_nfrp.reset(); c->d_alphas.reset();
@@ -994,6 +1003,9 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
         // a zero probability excludes alpha = 1 (nuc) or alpha = 0 (nfr) for every window (Occupancy.py:112-114); with an alpha strictly
         // between them the likelihood is positive somewhere, so the all-(-inf) case (the reference raises) cannot reach these kernels
         if ((zero_nfr || (c->occ_zero_flags & 1)) && n_alpha < 3) ok = false;
+        // the factor alpha of a zero-nfr size: four of them between two renormalisations (occ_eval, RN = 4) stay normal numbers only for
+        // alpha >= 2^-255.  A grid with a smaller positive alpha goes to natac_occ_mle, which renormalises after every factor of such a fragment
+        if ((c->occ_zero_flags & 2) && apos < std::ldexp(1.0, -250)) ok = false;
         c->occ_zero_nfr = ok && zero_nfr;
         c->occ_fast_ok = ok;
         // a likelihood factor 1 + alpha (rho kappa - 1) lies in [1 - alpha, 1 + rmax / rmin] with 1 - alpha >= the grid's
@@ -1020,6 +1032,16 @@ int natac_set_occ_model(natac_ctx *c, const double *nuc_probs, const double *nfr
         }
     }
     c->have_occ = true;
+    return NATAC_OK;
+}
+
+int natac_ctx_occ_route(natac_ctx *c, int32_t *fast, int32_t *rn, int32_t *zero_flags) {
+    if (!c || !fast || !rn || !zero_flags) return fail(NATAC_E_ARG, "null argument");
+    if (!c->have_occ) return fail(NATAC_E_STATE, "natac_set_occ_model has not been called");
+    const bool f = c->occ_fast_ok && !c->occ_force_general;
+    *fast = f ? 1 : 0;
+    *rn = f ? (c->occ_rn16 ? 16 : 4) : 0;
+    *zero_flags = (c->occ_zero_flags & 1) | (c->occ_zero_nfr ? 2 : 0);     // OccFastDev::flags of occ_launch
     return NATAC_OK;
 }
 

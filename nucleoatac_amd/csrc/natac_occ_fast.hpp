@@ -18,10 +18,13 @@
 //     point in five rounds instead of 101), one LANE per grid point: no cross-lane reductions at all.
 // The arithmetic differs from the reference's sum of logs at the 1e-15 relative level (as did the product-domain kernel it
 // replaces); the alpha indices are identical on every golden vector and on 848,000 grid points of the configs[2] batch
-// (tests/test_gpu_properties.py).  Tiles the fast path cannot treat exactly like the reference -- exp(bias) values that
+// (tests/test_gpu_properties.py).  tests/test_gpu_occ_decide_arms.py holds the arms those models never select to a long-double reference
+// at every decided grid point: RN = 4 (probability ratios up to 2^181, alphas within 2^-52 of 1 / 2^-60 of 0) with and without ZF at every
+// STEP, the global-memory arm with ZF and at every STEP, the edge at exactly OD_FM / OD_FM + 1 valid fragments among invalid ones, and
+// natac_occ_mle under models this path refuses.  Tiles the fast path cannot treat exactly like the reference -- exp(bias) values that
 // are not finite or could make a probability under- / overflow -- are handed to the general kernel natac_occ_mle through a
 // device-side list; models with an insert size of probability zero under BOTH distributions, alpha grids that are not increasing or
-// longer than 101 values, or steps beyond 9 use natac_occ_mle for everything.  Any odd step up to 9 (the CLI's --step) and any flank (--flank) stay here.
+// longer than 101 values, zero-nfr models with a positive alpha below 2^-250 (four factors alpha would underflow), or steps beyond 9 use natac_occ_mle for everything.  Any odd step up to 9 (the CLI's --step) and any flank (--flank) stay here.
 #pragma once
 #include "natac_kernels.hpp"
 

@@ -206,6 +206,13 @@ class Context(object):
         self.occ_step = step - 1 if step % 2 == 0 else step
         self.occ_upper = nuc_probs.shape[0]
 
+    def occ_route(self):
+        """(fast, rn, zero_flags) of the last set_occ_model (natac_ctx_occ_route): whether natac_occ_decide runs, its renormalisation
+        period (16 or 4; 0 when the general kernel takes everything) and its zero-probability flags."""
+        fast, rn, zf = C.c_int32(), C.c_int32(), C.c_int32()
+        L.check(self._lib.natac_ctx_occ_route(self._h, C.byref(fast), C.byref(rn), C.byref(zf)))
+        return bool(fast.value), rn.value, zf.value
+
     # ---- Cython-function drop-ins ------------------------------------------------------------
     def make_fragment_mat(self, l, n, start, end, lower, upper):
         """makeFragmentMat (pyatac/fragments.pyx:17-40) on packed fragments (l = pos+4, n = |tlen|-8)."""
