@@ -51,9 +51,10 @@ extern "C" {
  * for `pyatac counts` and natac_site_seq_counts for `pyatac nucleotide`; 8: added natac_site_signal and NATAC_SIGNAL_SEG for `pyatac signal`;
  * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device; 11: added
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
- * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability); the binding
+ * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
+ * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`); the binding
  * refuses another version */
-#define NATAC_ABI_VERSION 12
+#define NATAC_ABI_VERSION 13
 
 enum {
     NATAC_OK = 0,
@@ -574,6 +575,41 @@ int natac_frag_split_device(natac_ctx *ctx, const char *path, int64_t n_barcodes
 int natac_frag_open_cells(const char *path, int n_threads, int64_t n_barcodes, const void *bc_bytes, const int64_t *bc_off, natac_bam **out,
                           int64_t *bc_count, int64_t *n_unassigned);
 int natac_bam_ref_cells(natac_bam *bam, int32_t ref, int32_t *cell);
+/* ---- the cells of a fragment file: which barcodes it holds, in order of first appearance, with per-cell QC counts ----
+ * THE CELLS RULE (csrc/natac_fragfile.hpp: barcode_line is it; nucleoatac_amd/pyatac/fragments.py restates it).
+ * Validation and the barcode: every line is validated exactly as by natac_frag_split (the same checks, order, reasons and line numbers,
+ *   "no barcode field" checked last), and the barcode is the fourth field as THE SPLIT RULE defines it (the '\r' before a '\n' dropped
+ *   first, a last line without '\n' keeps its '\r'; compared byte for byte).
+ * Cells: a data line whose barcode is 1-255 bytes long belongs to the cell of that barcode.  Cells are numbered in order of first
+ *   appearance over the file's data lines: file order, not hash or thread order.  A data line whose barcode is empty or longer than 255
+ *   bytes is UNASSIGNED: validated, counted in n_unassigned, and no error.
+ * Counters: with ilen = end - start of the line, cell k has three exact int64 counters: n_frag[k] = its data lines, n_nfr[k] = those with
+ *   ilen < nfr_upper, n_mono[k] = those with nfr_upper <= ilen < mono_upper.  0 < nfr_upper < mono_upper, NATAC_E_ARG otherwise (147 and
+ *   294 are the binding's defaults: the usual nucleosome-free and mono-nucleosome classes).  One line is one fragment whatever its fifth
+ *   column says.
+ * Limits: more than NATAC_SPLIT_MAX_BARCODES distinct barcodes fails the call with "<path>: line <N>: more than 8388608 distinct
+ *   barcodes", N the line on which the limit was passed.
+ * Invariance: the result is a function of the file's bytes and the two bounds only: not of n_threads, NATAC_BAM_WINDOW,
+ *   NATAC_FRAG_DEV_WINDOW, the BGZF member size, the container, or which path answered.
+ * Containers, windows, slices and the first error as natac_frag_split.  *out is a handle (NULL on any error):
+ *   natac_cells_counts: n_cells, the total barcode bytes, n_data (the file's data lines) and n_unassigned (each may be NULL);
+ *   natac_cells_read: bc_bytes[total bytes] and bc_off[n_cells + 1] (cell k is bc_bytes[bc_off[k] .. bc_off[k + 1])), n_frag / n_nfr /
+ *     n_mono[n_cells]; n_cells and n_bytes must be the handle's (NATAC_E_ARG otherwise), any array may be NULL;
+ *   natac_cells_close. */
+typedef struct natac_cells natac_cells;
+int natac_frag_cells(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, natac_cells **out);
+/* The same with a BGZF file inflated and split into lines ON THE DEVICE as by natac_frag_open_device, and the barcode table built there
+ * from the file itself (csrc/natac_fragfile_dev.hpp: an open-addressing table in device memory that lives across windows; a slot is
+ * claimed by the smallest line of a window, and only matches after the bytes compared equal; NATAC_SPLIT_HASH_BITS applies).  The table
+ * has a FIXED size: 8,388,608 slots (NATAC_CELLS_DEV_SLOTS=<power of two> sets another: tests), of which at most half are taken.  The
+ * host path answers inside this call for everything natac_frag_open_device hands over, for a line without a barcode field, for a full
+ * table (more than slots / 2 barcodes: more than 4,194,304 by default), for more than 268,435,455 lines in a window and for a HIP
+ * failure; *on_device (may be NULL) tells which one answered. */
+int natac_frag_cells_device(natac_ctx *ctx, const char *path, int32_t nfr_upper, int32_t mono_upper, natac_cells **out, int *on_device);
+int natac_cells_counts(natac_cells *cells, int64_t *n_cells, int64_t *n_bytes, int64_t *n_data, int64_t *n_unassigned);
+int natac_cells_read(natac_cells *cells, int64_t n_cells, int64_t n_bytes, void *bc_bytes, int64_t *bc_off, int64_t *n_frag, int64_t *n_nfr,
+                     int64_t *n_mono);
+void natac_cells_close(natac_cells *cells);
 /* test entry: the device's raw-deflate decoder run on the host (one BGZF member payload -> isize bytes); returns its error code */
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize);
 

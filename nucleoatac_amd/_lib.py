@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 12     # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 13     # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -127,6 +127,11 @@ SIGNATURES = {
     "natac_frag_split": (C.c_int, [C.c_char_p, C.c_int, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "natac_frag_split_device": (C.c_int, [_vp, C.c_char_p, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(C.c_int)]),
     "natac_frag_open_cells": (C.c_int, [C.c_char_p, C.c_int, _i64, _vp, _vp, _pp, _vp, _vp]),
+    "natac_frag_cells": (C.c_int, [C.c_char_p, C.c_int, _i32, _i32, _pp]),
+    "natac_frag_cells_device": (C.c_int, [_vp, C.c_char_p, _i32, _i32, _pp, C.POINTER(C.c_int)]),
+    "natac_cells_counts": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "natac_cells_read": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "natac_cells_close": (None, [_vp]),
     "natac_bam_ref_cells": (C.c_int, [_vp, _i32, _vp]),
     "natac_inflate_raw_host": (C.c_int, [_vp, C.c_size_t, _vp, C.c_size_t]),
     "natac_fuzz_evaluate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

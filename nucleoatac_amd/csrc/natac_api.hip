@@ -158,6 +158,10 @@ struct natac_bam {
     natac_bamio::Bam *impl = nullptr;
 };
 
+struct natac_cells {
+    natac_fragio::Cells table;
+};
+
 // What each output of a batch holds and who wrote it: the stages and natac_batch_set_track write it, every reader asks need_track().
 // PENDING: formed on the first request from what the stage left (BACKGROUND from d_bnum / d_bcov, OCC_PREFILL from the grids).
 enum TrackState : unsigned char { TS_EMPTY = 0, TS_PENDING, TS_RUN /* a natac_run_* stage */, TS_HOST /* natac_batch_set_track */ };
@@ -3605,6 +3609,83 @@ int natac_frag_split_device(natac_ctx *c, const char *path, int64_t n_barcodes, 
     // everything natac_frag_open_device hands over, a line without a barcode field, too many groups x runs in a window: the host path answers
     return frag_split_host(path, 0, table, out, bc_count, n_unassigned);
 }
+
+/* ---------------- the cells of a fragment file ---------------- */
+
+static int frag_cells_host(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, natac_cells **out) {
+    std::unique_ptr<natac_cells> h(new natac_cells());
+    std::string err;
+    if (!natac_fragio::decode_cells(path, n_threads, nfr_upper, mono_upper, NATAC_SPLIT_MAX_BARCODES, &h->table, err, frag_host_window()))
+        return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
+    *out = h.release();
+    return NATAC_OK;
+}
+
+int natac_frag_cells(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, natac_cells **out) {
+    if (!path || !out) return fail(NATAC_E_ARG, "null argument");
+    *out = nullptr;
+    if (!(0 < nfr_upper && nfr_upper < mono_upper)) return fail(NATAC_E_ARG, "0 < nfr_upper < mono_upper does not hold (got %d and %d)", nfr_upper, mono_upper);
+    return frag_cells_host(path, n_threads, nfr_upper, mono_upper, out);
+}
+
+int natac_frag_cells_device(natac_ctx *c, const char *path, int32_t nfr_upper, int32_t mono_upper, natac_cells **out, int *on_device) {
+    if (!c || !path || !out) return fail(NATAC_E_ARG, "null argument");
+    *out = nullptr;
+    if (on_device) *on_device = 0;
+    if (!(0 < nfr_upper && nfr_upper < mono_upper)) return fail(NATAC_E_ARG, "0 < nfr_upper < mono_upper does not hold (got %d and %d)", nfr_upper, mono_upper);
+    HIPCHK(hipSetDevice(c->device));
+    bool bgzf = false;
+    if (FILE *f = std::fopen(path, "rb")) {
+        unsigned char magic[1040];
+        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
+        std::fclose(f);
+    }
+    if (bgzf) {                                       // other containers are the host path's
+        size_t window = (size_t)1 << 30;
+        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+        std::unique_ptr<natac_cells> h(new natac_cells());
+        natac_fragdev::CellsJob job;
+        job.nfr_upper = nfr_upper;
+        job.mono_upper = mono_upper;
+        job.out = &h->table;
+        std::string why;
+        natac_bamio::Bam *token = natac_fragdev::decode_device(path, c->stream, why, window, nullptr, &job);
+        if (token) {
+            delete token;
+            *out = h.release();
+            if (on_device) *on_device = 1;
+            return NATAC_OK;
+        }
+    }
+    // everything natac_frag_open_device hands over, a line without a barcode field, a full table, a HIP failure: the host path answers
+    return frag_cells_host(path, 0, nfr_upper, mono_upper, out);
+}
+
+int natac_cells_counts(natac_cells *cells, int64_t *n_cells, int64_t *n_bytes, int64_t *n_data, int64_t *n_unassigned) {
+    if (!cells) return fail(NATAC_E_ARG, "cells is NULL");
+    if (n_cells) *n_cells = (int64_t)cells->table.n_frag.size();
+    if (n_bytes) *n_bytes = (int64_t)cells->table.bytes.size();
+    if (n_data) *n_data = cells->table.n_data;
+    if (n_unassigned) *n_unassigned = cells->table.n_unassigned;
+    return NATAC_OK;
+}
+
+int natac_cells_read(natac_cells *cells, int64_t n_cells, int64_t n_bytes, void *bc_bytes, int64_t *bc_off, int64_t *n_frag, int64_t *n_nfr,
+                     int64_t *n_mono) {
+    if (!cells) return fail(NATAC_E_ARG, "cells is NULL");
+    const natac_fragio::Cells &t = cells->table;
+    if (n_cells != (int64_t)t.n_frag.size() || n_bytes != (int64_t)t.bytes.size())
+        return fail(NATAC_E_ARG, "the handle holds %zu cells of %zu bytes, buffers are for %lld of %lld", t.n_frag.size(), t.bytes.size(), (long long)n_cells,
+                    (long long)n_bytes);
+    if (bc_bytes && n_bytes) std::memcpy(bc_bytes, t.bytes.data(), (size_t)n_bytes);
+    if (bc_off) std::memcpy(bc_off, t.off.data(), ((size_t)n_cells + 1) * sizeof(int64_t));
+    if (n_frag && n_cells) std::memcpy(n_frag, t.n_frag.data(), (size_t)n_cells * sizeof(int64_t));
+    if (n_nfr && n_cells) std::memcpy(n_nfr, t.n_nfr.data(), (size_t)n_cells * sizeof(int64_t));
+    if (n_mono && n_cells) std::memcpy(n_mono, t.n_mono.data(), (size_t)n_cells * sizeof(int64_t));
+    return NATAC_OK;
+}
+
+void natac_cells_close(natac_cells *cells) { delete cells; }
 
 int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isize) {
     if ((!src && csize) || (!out && isize) || csize > 0xffffffffull || isize > 0xffffffffull) return -1;

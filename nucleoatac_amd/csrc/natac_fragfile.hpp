@@ -9,11 +9,14 @@
 // Splitting by cell barcode (natac_frag_split): split_line below IS the rule of include/natac.h -- parse_line, then the fourth field looked
 // up in a SplitTable -- and is __host__ __device__ for the same reason.
 // The cell-tagged read (natac_frag_open_cells) is the one-group split that keeps, per kept record, the index of its barcode in the table.
+// Discovering the cells (natac_frag_cells): the cells rule of include/natac.h is barcode_line below, split_line's own line without a table: the
+// barcodes are numbered as the file's data lines bring them up, each with its three fragment counters.
 #pragma once
 #include "natac_bam.hpp"
 
 #include <memory>
 #include <string>
+#include <string_view>
 #include <unordered_map>
 #include <vector>
 
@@ -119,11 +122,10 @@ NATAC_FRAG_HD inline int32_t barcode_lookup(const SplitTable &tb, const unsigned
     return -1;
 }
 
-// THE SPLIT RULE.  The line is classified by parse_line (same checks, same order); a data line without a fourth field is BAD_NO_BARCODE,
-// checked last.  The barcode is the bytes between the third TAB and the fourth (or the line's end), compared byte for byte.  *bc = its
-// index in the table, or -1: unassigned (empty, longer than 255 bytes or not listed), which is no error.
-NATAC_FRAG_HD inline int split_line(const unsigned char *p, size_t len, const SplitTable &tb, uint32_t *name_len, int32_t *start, int32_t *end,
-                                    int32_t *bc) {
+// A data line and its barcode, for THE SPLIT RULE and THE CELLS RULE alike.  The line is classified by parse_line (same checks, same order); a
+// data line without a fourth field is BAD_NO_BARCODE, checked last.  The barcode is p[*bc_at, *bc_at + *bc_len): the bytes between the
+// third TAB and the fourth (or the line's end), whatever their number.
+NATAC_FRAG_HD inline int barcode_line(const unsigned char *p, size_t len, uint32_t *name_len, int32_t *start, int32_t *end, size_t *bc_at, size_t *bc_len) {
     const int kind = parse_line(p, len, name_len, start, end);
     if (kind != LINE_DATA) return kind;
     size_t t = 0;
@@ -133,7 +135,19 @@ NATAC_FRAG_HD inline int split_line(const unsigned char *p, size_t len, const Sp
     }
     size_t e = t;
     while (e < len && p[e] != '\t') ++e;
-    *bc = barcode_lookup(tb, p + t, e - t);
+    *bc_at = t;
+    *bc_len = e - t;
+    return LINE_DATA;
+}
+
+// THE SPLIT RULE.  barcode_line, and the barcode compared byte for byte: *bc = its index in the table, or -1: unassigned (empty, longer than
+// 255 bytes or not listed), which is no error.
+NATAC_FRAG_HD inline int split_line(const unsigned char *p, size_t len, const SplitTable &tb, uint32_t *name_len, int32_t *start, int32_t *end,
+                                    int32_t *bc) {
+    size_t at = 0, bc_len = 0;
+    const int kind = barcode_line(p, len, name_len, start, end, &at, &bc_len);
+    if (kind != LINE_DATA) return kind;
+    *bc = barcode_lookup(tb, p + at, bc_len);
     return LINE_DATA;
 }
 
@@ -512,6 +526,132 @@ inline bool decode_split(const char *path, int n_threads, const SplitTableHost &
     sb.finish(out);
     if (n_unassigned) *n_unassigned = sb.n_records - sb.n_assigned;
     return true;
+}
+
+// ---- discovering the cells of a fragment file (natac_frag_cells) ----
+// THE CELLS RULE's line is barcode_line: a data line whose barcode is 1-255 bytes long belongs to the cell of that barcode, any other data
+// line is unassigned (the callers' business: parse_slice_cells here, cells_parse on the device).
+// the size class of a data line: 0 ilen < nfr_upper, 1 nfr_upper <= ilen < mono_upper, 2 neither
+NATAC_FRAG_HD inline int cells_size_class(int32_t start, int32_t end, int32_t nfr_upper, int32_t mono_upper) {
+    const int32_t ilen = end - start;                   // (0 <= start <= end <= 2^31 - 1: no overflow)
+    return ilen < nfr_upper ? 0 : ilen < mono_upper ? 1 : 2;
+}
+
+// the result of both paths: the cells in order of first appearance over the file's data lines
+struct Cells {
+    std::vector<unsigned char> bytes;                   // the barcodes, concatenated
+    std::vector<int64_t> off{0};                        // [n_cells + 1] into bytes
+    std::vector<int64_t> n_frag, n_nfr, n_mono;         // [n_cells]
+    int64_t n_data = 0, n_unassigned = 0;
+};
+
+struct CellsSliceOut {                                  // the cells of one slice in order of first appearance IN THE SLICE
+    std::unordered_map<std::string_view, uint32_t> ids; // (views into the window's text: the slice outputs do not outlive parse_text_cells)
+    std::vector<std::string_view> bc;
+    std::vector<size_t> first_line;                     // the slice's line (1-based) on which the cell first appears
+    std::vector<int64_t> cnt;                           // [3 * cells]: n_frag, n_nfr, n_mono
+    int64_t n_data = 0, n_unassigned = 0;
+    size_t n_lines = 0;
+    int bad = 0;
+};
+
+inline void parse_slice_cells(const unsigned char *p, size_t a, size_t b, bool open_end, int32_t nfr_upper, int32_t mono_upper, CellsSliceOut *out) {
+    while (a < b) {
+        const unsigned char *nl = (const unsigned char *)std::memchr(p + a, '\n', b - a);
+        size_t e = nl ? (size_t)(nl - p) : b;
+        const size_t next = nl ? e + 1 : b;
+        if (!nl && !open_end) break;
+        if (nl && e > a && p[e - 1] == '\r') --e;
+        ++out->n_lines;
+        int32_t s = 0, t = 0;
+        size_t at = 0, len = 0;
+        uint32_t nlen = 0;
+        const int kind = barcode_line(p + a, e - a, &nlen, &s, &t, &at, &len);
+        if (kind > LINE_DATA) { out->bad = kind; return; }
+        if (kind == LINE_DATA) {
+            ++out->n_data;
+            if (len < 1 || len > 255) ++out->n_unassigned;
+            else {
+                const std::string_view key((const char *)p + a + at, len);
+                auto it = out->ids.find(key);
+                if (it == out->ids.end()) {
+                    it = out->ids.emplace(key, (uint32_t)out->bc.size()).first;
+                    out->bc.push_back(key);
+                    out->first_line.push_back(out->n_lines);
+                    out->cnt.insert(out->cnt.end(), 3, (int64_t)0);
+                }
+                int64_t *c = out->cnt.data() + 3 * (size_t)it->second;
+                ++c[0];
+                const int cls = cells_size_class(s, t, nfr_upper, mono_upper);
+                if (cls < 2) ++c[1 + cls];
+            }
+        }
+        a = next;
+    }
+}
+
+// What the slices merge into.  The slices discover in parallel; merged in file order, a cell new to the file is first met in the earliest slice
+// that holds it, and within that slice in the slice's own order of first appearance: the file's order of first appearance.
+struct CellsBuilder {
+    Cells *out;
+    int64_t max_cells;
+    std::unordered_map<std::string, int64_t> ids;
+    CellsBuilder(Cells *o, int64_t limit) : out(o), max_cells(limit) {}
+};
+
+// parse_text with barcode_line: the same slices.  An error is the first in file order: the line that passes the limit of distinct barcodes, or
+// a malformed line.
+inline bool parse_text_cells(const unsigned char *p, size_t n, bool open_end, int n_threads, int32_t nfr_upper, int32_t mono_upper, CellsBuilder &cb,
+                             unsigned long long *lines, std::string &err) {
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, n_threads), n / 256));
+    std::vector<size_t> cut((size_t)T + 1, n);
+    cut[0] = 0;
+    for (int t = 1; t < T; ++t) {
+        const size_t at = std::max(cut[(size_t)t - 1], n * (size_t)t / (size_t)T);
+        const unsigned char *nl = at < n ? (const unsigned char *)std::memchr(p + at, '\n', n - at) : nullptr;
+        cut[(size_t)t] = nl ? (size_t)(nl - p) + 1 : n;
+    }
+    std::vector<CellsSliceOut> out((size_t)T);
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t) th.emplace_back(parse_slice_cells, p, cut[(size_t)t], cut[(size_t)t + 1], open_end, nfr_upper, mono_upper, &out[(size_t)t]);
+    parse_slice_cells(p, cut[0], cut[1], open_end, nfr_upper, mono_upper, &out[0]);
+    for (auto &x : th) x.join();
+    Cells &res = *cb.out;
+    for (auto &so : out) {
+        const unsigned long long before = *lines;
+        *lines += so.n_lines;
+        for (size_t k = 0; k < so.bc.size(); ++k) {
+            auto it = cb.ids.find(std::string(so.bc[k]));
+            if (it == cb.ids.end()) {
+                if ((int64_t)res.n_frag.size() >= cb.max_cells) {
+                    err = "line " + std::to_string(before + so.first_line[k]) + ": more than " + std::to_string(cb.max_cells) + " distinct barcodes";
+                    return false;
+                }
+                it = cb.ids.emplace(std::string(so.bc[k]), (int64_t)res.n_frag.size()).first;
+                res.bytes.insert(res.bytes.end(), so.bc[k].begin(), so.bc[k].end());
+                res.off.push_back((int64_t)res.bytes.size());
+                res.n_frag.push_back(0);
+                res.n_nfr.push_back(0);
+                res.n_mono.push_back(0);
+            }
+            const size_t c = (size_t)it->second;
+            res.n_frag[c] += so.cnt[3 * k];
+            res.n_nfr[c] += so.cnt[3 * k + 1];
+            res.n_mono[c] += so.cnt[3 * k + 2];
+        }
+        if (so.bad) { err = "line " + std::to_string(*lines) + ": " + reason_text(so.bad); return false; }
+        res.n_data += so.n_data;
+        res.n_unassigned += so.n_unassigned;
+    }
+    return true;
+}
+
+// natac_frag_cells' host path: containers, windows, slices and the first error as decode_split
+inline bool decode_cells(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, int64_t max_cells, Cells *out, std::string &err,
+                         size_t window = (size_t)48 << 20) {
+    CellsBuilder cb(out, max_cells);
+    return stream_text(path, n_threads, err, window, [&](const unsigned char *p, size_t n, bool open_end, int threads, unsigned long long *lines,
+                                                         std::string &e) { return parse_text_cells(p, n, open_end, threads, nfr_upper, mono_upper, cb, lines, e); });
 }
 
 }  // namespace natac_fragio

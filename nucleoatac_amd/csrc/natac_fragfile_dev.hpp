@@ -21,10 +21,13 @@
 //        slot; the wave then walks its tile in file order, 64 lines a round, and gives the lanes of a group consecutive slots in lane
 //        order.  The counts of every (group, run) segment come from the same histogram.  Integers only: nothing depends on order.
 //   The host gets start / end of the assigned lines only, in group-major order, and the segment counts, and appends segment by segment.
+// Discovering the cells (natac_frag_cells_device; decode_device with a CellsJob) keeps (a) too and needs no runs: cells_parse, rounds of
+// cells_claim / cells_verify, cells_number / cells_adopt and cells_count build the barcode table from the file itself (see CellsJob below).
 // The host decoder answers instead (the caller runs it) for: a malformed line or a damaged file (so both paths give the same message
 // by construction), a window without any line end, more than MAX_RUNS runs in a window, a HIP failure;
 // when splitting also for a line without a barcode field (malformed), a table of more than SPLIT_DEV_MAX_BARCODES barcodes and more than
-// SPLIT_MAX_SEGMENTS groups x runs in a window.
+// SPLIT_MAX_SEGMENTS groups x runs in a window; when discovering cells for a line without a barcode field, a full table (more than half
+// the slots taken: more than SPLIT_DEV_MAX_BARCODES cells with the default size) and more than 268,435,455 lines in a window.
 #pragma once
 #include "natac_bam_dev.hpp"
 #include "natac_fragfile.hpp"
@@ -348,6 +351,316 @@ __global__ void __launch_bounds__(64) frag_gather_names(const unsigned char *__r
     for (unsigned int k = 0; k < len && a + k < n; ++k) names[(u64)r * 256 + k] = data[a + k];
 }
 
+// ---- discovering the cells (natac_frag_cells_device) ----
+// The table is built from the file, on the device, and lives across windows: slot[n_slots] (64-bit words), the arena of the known cells'
+// barcodes with off[n_cells + 1] into it, and cnt[n_cells][3] (n_frag, n_nfr, n_mono).  A slot word is
+//   CELLS_EMPTY;  or k < 2^32: the slot belongs to cell k (its bytes are in the arena);  or CELLS_CLAIM | round << 32 | line: claimed in
+//   THIS window by that line of the window, whose barcode lies in the window's text.
+// atomicMin orders them: a cell's word is below every claim (it is never displaced), a claim of an earlier round is below every claim of
+// a later one (a slot that was won stays won), and inside a round the smallest line wins, whatever the dispatch order.
+// Per window, behind (a):
+//   cells_parse: one lane per line runs natac_fragio::barcode_line and takes the barcode's span, length, size class and home slot.
+//   rounds of cells_claim / cells_verify, two launches each, until the device counter of unresolved lines reads zero.  In round r every
+//     unresolved line stands at the r-th slot of its probe sequence.  cells_claim: it claims the slot unless a cell or a smaller claim
+//     holds it.  cells_verify (behind the kernel boundary every claim of the round is in): it compares its barcode, byte for byte, with
+//     the slot's owner's -- in the arena, or in the text of the winning line -- and is resolved to the slot when they are equal (the
+//     winner itself is), else it moves one slot on.  Nothing waits inside a kernel; the rounds are bounded by CELLS_MAX_ROUNDS and by the
+//     slot count (then the host path answers: the table is full).
+//   cells_number / frag_scan / cells_adopt: the winners are the first lines of the barcodes new in this window; a scan over that flag in
+//     line order gives cell = cells known before + rank (first appearance in FILE order, no sort) and the barcode's place in the arena;
+//     the winner copies its bytes there and turns its slot's word into the cell.
+//   cells_count: every resolved line reads its cell from its slot; the three counters grow by one integer atomic per set of lanes of a
+//     wave that share a cell.
+// FIXED SIZE: the table does not grow.  It has 2^23 slots (NATAC_CELLS_DEV_SLOTS = another power of two: tests) and holds at most half as
+// many cells -- 4,194,304, SPLIT_DEV_MAX_BARCODES -- so an empty slot always exists and probe sequences stay short; beyond that the host
+// path answers.  Every read of the text lies inside a line's span (so inside [0, n)), every read of the arena inside its fill.
+constexpr u64 CELLS_EMPTY = ~0ull, CELLS_CLAIM = 1ull << 60;
+constexpr unsigned int CELLS_NONE = 0xffffffffu, CELLS_FAILED = 0xfffffffeu, CELLS_RESOLVED = 0x80000000u;      // probe[i] below n_slots: unresolved, at that slot
+constexpr unsigned int CELLS_MAX_ROUNDS = 4096;         // (the longest probe sequence of 4 M keys in 8 M slots is a few dozen slots)
+constexpr u64 CELLS_MAX_LINES = 1ull << 28;             // per window: a line fits the 32 bits of a claim, new cells and their bytes one packed scan
+constexpr int CELLS_F_MALFORMED = 1, CELLS_F_FULL = 2, CELLS_F_BROKEN = 4;
+enum { CELLS_S_DATA = 0, CELLS_S_UNASSIGNED = 1, CELLS_S_UNRESOLVED = 2, CELLS_S_NEW = 3, CELLS_S_FLAGS = 4, CELLS_S_WORDS = 8 };      // words of the state block
+
+// meta[i] = the barcode's length (1-255; 0: no data line of a cell) | size class << 9; probe[i] = its home slot, or CELLS_NONE
+__global__ void __launch_bounds__(TILE_T) cells_parse(const unsigned char *__restrict__ data, const u64 *__restrict__ ls, u64 n_lines, int open_tail,
+                                                      int nfr_upper, int mono_upper, unsigned int home_mask, u64 *__restrict__ bc_at,
+                                                      unsigned int *__restrict__ meta, unsigned int *__restrict__ probe, u64 *__restrict__ state) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    u64 c = 0;                                           // (is data) << 32 | (is unassigned)
+    if (i < n_lines) {
+        u64 a, e;
+        line_span(data, ls, i, n_lines, open_tail, &a, &e);
+        int32_t s = 0, t = 0;
+        size_t at = 0, len = 0;
+        uint32_t nlen = 0;
+        const int kind = natac_fragio::barcode_line(data + a, (size_t)(e - a), &nlen, &s, &t, &at, &len);
+        if (kind > natac_fragio::LINE_DATA) atomicOr(&state[CELLS_S_FLAGS], (u64)CELLS_F_MALFORMED);
+        unsigned int m = 0, pr = CELLS_NONE;
+        if (kind == natac_fragio::LINE_DATA) {
+            const bool cell = len >= 1 && len <= 255;
+            c = (1ull << 32) | (cell ? 0ull : 1ull);
+            if (cell) {
+                m = (unsigned int)len | ((unsigned int)natac_fragio::cells_size_class(s, t, nfr_upper, mono_upper) << 9);
+                pr = natac_fragio::barcode_hash(data + a + at, len) & home_mask;
+            }
+        }
+        bc_at[i] = a + (u64)at;
+        meta[i] = m;
+        probe[i] = pr;
+    }
+    u64 total;
+    block_excl_scan(c, &total);
+    if (threadIdx.x == 0 && total) {
+        atomicAdd(&state[CELLS_S_DATA], total >> 32);
+        if (total & 0xffffffffull) atomicAdd(&state[CELLS_S_UNASSIGNED], total & 0xffffffffull);
+    }
+}
+
+// One atomicMin per set of lanes of a wave that stand at the same slot (its lowest lane holds the smallest line), and none where the word
+// already is a cell or a smaller claim: the word only ever decreases, so a stale look costs an atomic and never a claim.
+__global__ void __launch_bounds__(TILE_T) cells_claim(const unsigned int *__restrict__ probe, u64 n_lines, u64 *slot, unsigned int n_slots, int slot_bits,
+                                                      unsigned int round) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    const unsigned int s = i < n_lines ? probe[i] : CELLS_NONE;
+    const u64 mine = CELLS_CLAIM | ((u64)round << 32) | i;
+    bool want = false;
+    if (s < n_slots) want = __hip_atomic_load(&slot[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > mine;
+    if (__ballot(want) == 0) return;                     // (the same for every lane of the wave)
+    const u64 peers = wave_peers(s, want, slot_bits);
+    if (want && (int)(threadIdx.x & 63) == __ffsll((long long)peers) - 1) atomicMin(&slot[s], mine);
+}
+
+// is the barcode of line i (len bytes at `at` of the text) the slot's owner's: 1 yes, 0 no, -1 the word or the tables are out of range
+__device__ __forceinline__ int cells_same(const unsigned char *__restrict__ data, u64 n, const u64 *__restrict__ bc_at, const unsigned int *__restrict__ meta,
+                                          u64 n_lines, u64 i, u64 at, unsigned int len, u64 v, const unsigned char *__restrict__ arena,
+                                          const u64 *__restrict__ off, u64 n_known, u64 fill) {
+    const unsigned char *q;
+    u64 qlen;
+    if (v < (1ull << 32)) {                              // a cell known before this window
+        if (v >= n_known) return -1;
+        const u64 a = off[v], b = off[v + 1];
+        if (a > b || b > fill) return -1;
+        q = arena + a;
+        qlen = b - a;
+    } else {                                             // a line of this window
+        const u64 j = v & 0xffffffffull;
+        if (v == CELLS_EMPTY || !(v & CELLS_CLAIM) || j >= n_lines) return -1;
+        if (j == i) return 1;
+        qlen = meta[j] & 0x1ffu;
+        if (qlen == 0 || bc_at[j] + qlen > n) return -1;
+        q = data + bc_at[j];
+    }
+    if (qlen != len) return 0;
+    for (unsigned int k = 0; k < len; ++k)
+        if (q[k] != data[at + k]) return 0;
+    return 1;
+}
+
+__global__ void __launch_bounds__(TILE_T) cells_verify(const unsigned char *__restrict__ data, u64 n, const u64 *__restrict__ bc_at,
+                                                       const unsigned int *__restrict__ meta, unsigned int *__restrict__ probe, u64 n_lines,
+                                                       const u64 *__restrict__ slot, unsigned int n_slots, const unsigned char *__restrict__ arena,
+                                                       const u64 *__restrict__ off, u64 n_known, u64 fill, unsigned int round, u64 *__restrict__ state) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    bool again = false;
+    if (i < n_lines) {
+        const unsigned int s = probe[i];
+        if (s < n_slots) {
+            const int same = cells_same(data, n, bc_at, meta, n_lines, i, bc_at[i], meta[i] & 0x1ffu, slot[s], arena, off, n_known, fill);
+            if (same == 1) probe[i] = CELLS_RESOLVED | s;
+            else if (same == 0 && round + 1u < n_slots && round + 1u < CELLS_MAX_ROUNDS) {
+                probe[i] = (s + 1u) & (n_slots - 1u);
+                again = true;
+            } else {
+                probe[i] = CELLS_FAILED;
+                atomicOr(&state[CELLS_S_FLAGS], (u64)(same == 0 ? CELLS_F_FULL : CELLS_F_BROKEN));
+            }
+        }
+    }
+    const u64 m = __ballot(again);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(&state[CELLS_S_UNRESOLVED], (u64)__popcll(m));
+}
+
+// (is the first line of a barcode new in this window) << 36 | its barcode's length: 2^28 lines of 255 bytes fit the low 36 bits
+__device__ __forceinline__ u64 cells_new_code(const unsigned int *__restrict__ probe, const unsigned int *__restrict__ meta, const u64 *slot,
+                                              unsigned int n_slots, u64 n_lines, u64 i, unsigned int *s) {
+    if (i >= n_lines) return 0;
+    const unsigned int p = probe[i];
+    *s = p & ~CELLS_RESOLVED;
+    if (!(p & CELLS_RESOLVED) || *s >= n_slots) return 0;
+    const u64 v = __hip_atomic_load(&slot[*s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (v == CELLS_EMPTY || !(v & CELLS_CLAIM) || (v & 0xffffffffull) != i) return 0;
+    return (1ull << 36) | (u64)(meta[i] & 0x1ffu);
+}
+
+__global__ void __launch_bounds__(TILE_T) cells_number(const unsigned int *__restrict__ probe, const unsigned int *__restrict__ meta, const u64 *slot,
+                                                       unsigned int n_slots, u64 n_lines, u64 *__restrict__ block_sum) {
+    unsigned int s;
+    u64 total;
+    block_excl_scan(cells_new_code(probe, meta, slot, n_slots, n_lines, (u64)blockIdx.x * TILE_T + threadIdx.x, &s), &total);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
+}
+
+// block_off = the scanned block_sum.  The winner of a slot is cell n_known + its rank: its bytes go to the arena behind `fill`, and its
+// slot's word becomes the cell.  Only the winner writes its slot; another line of the barcode that looks at the word sees the claim or the
+// cell, and neither names it.
+__global__ void __launch_bounds__(TILE_T) cells_adopt(const unsigned char *__restrict__ data, const u64 *__restrict__ bc_at, const unsigned int *__restrict__ probe,
+                                                      const unsigned int *__restrict__ meta, u64 *slot, unsigned int n_slots, u64 n_lines,
+                                                      const u64 *__restrict__ block_off, u64 n_known, u64 n_new, u64 fill, u64 new_bytes,
+                                                      unsigned char *__restrict__ arena, u64 *__restrict__ off) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    unsigned int s = 0;
+    const u64 c = cells_new_code(probe, meta, slot, n_slots, n_lines, i, &s);
+    u64 total;
+    const u64 ex = block_off[blockIdx.x] + block_excl_scan(c, &total);
+    const u64 rank = ex >> 36, at = ex & ((1ull << 36) - 1ull), len = c & 0x1ffull;
+    if (c == 0 || rank >= n_new || at + len > new_bytes) return;
+    for (u64 k = 0; k < len; ++k) arena[fill + at + k] = data[bc_at[i] + k];
+    off[n_known + rank + 1] = fill + at + len;
+    __hip_atomic_store(&slot[s], n_known + rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(TILE_T) cells_count(const unsigned int *__restrict__ probe, const unsigned int *__restrict__ meta, const u64 *__restrict__ slot,
+                                                      unsigned int n_slots, u64 n_lines, u64 n_cells, int cell_bits, u64 *__restrict__ cnt,
+                                                      u64 *__restrict__ state) {
+    const u64 i = (u64)blockIdx.x * TILE_T + threadIdx.x;
+    u64 cell = 0;
+    int cls = 2;
+    bool valid = false;
+    if (i < n_lines && (probe[i] & CELLS_RESOLVED) && probe[i] < CELLS_FAILED) {
+        const unsigned int s = probe[i] & ~CELLS_RESOLVED;
+        if (s < n_slots) {
+            cell = slot[s];
+            cls = (int)(meta[i] >> 9);
+            valid = cell < n_cells;
+        }
+        if (!valid) atomicOr(&state[CELLS_S_FLAGS], (u64)CELLS_F_BROKEN);
+    }
+    const u64 peers = wave_peers((unsigned int)cell, valid, cell_bits), nfr = __ballot(valid && cls == 0), mono = __ballot(valid && cls == 1);
+    if (valid && (int)(threadIdx.x & 63) == __ffsll((long long)peers) - 1) {
+        atomicAdd(&cnt[3 * cell], (u64)__popcll(peers));
+        if (peers & nfr) atomicAdd(&cnt[3 * cell + 1], (u64)__popcll(peers & nfr));
+        if (peers & mono) atomicAdd(&cnt[3 * cell + 2], (u64)__popcll(peers & mono));
+    }
+}
+
+// What a discovery adds to decode_device: the table on the device and the per-window work behind the line index.
+struct CellsJob {
+    int nfr_upper = 147, mono_upper = 294;
+    natac_fragio::Cells *out = nullptr;
+    unsigned int n_slots = 1u << 23, hash_mask = 0xffffffffu;
+    int slot_bits = 23;
+    u64 n_cells = 0, fill = 0;
+    DevBuf slot, arena, off, cnt, state, bc_at, meta, probe, bsum;
+
+    void configure() {
+        if (const char *e = getenv("NATAC_CELLS_DEV_SLOTS")) {
+            const long long v = atoll(e);
+            if (v >= 16 && v <= (1ll << 26) && (v & (v - 1)) == 0) n_slots = (unsigned int)v;
+        }
+        slot_bits = 0;
+        while ((1u << slot_bits) < n_slots) ++slot_bits;
+        if (const char *e = getenv("NATAC_SPLIT_HASH_BITS")) { const int b = atoi(e); if (b >= 0 && b < 32) hash_mask = (1u << b) - 1u; }
+    }
+
+#define CELLS_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return std::string(#expr) + ": " + hipGetErrorString(e_); } } while (0)
+    // "" or what stops the device path
+    std::string start(hipStream_t stream) {
+        configure();
+        CELLS_HIP(slot.reserve((size_t)n_slots * sizeof(u64)));
+        CELLS_HIP(state.reserve(CELLS_S_WORDS * sizeof(u64)));
+        CELLS_HIP(off.reserve(4096 * sizeof(u64)));
+        CELLS_HIP(arena.reserve(65536));
+        CELLS_HIP(cnt.reserve(3 * 4096 * sizeof(u64)));
+        CELLS_HIP(hipMemsetAsync(slot.p, 0xff, (size_t)n_slots * sizeof(u64), stream));          // CELLS_EMPTY
+        CELLS_HIP(hipMemsetAsync(state.p, 0, CELLS_S_WORDS * sizeof(u64), stream));
+        CELLS_HIP(hipMemsetAsync(off.p, 0, sizeof(u64), stream));                                 // off[0]
+        return std::string();
+    }
+
+    // the lines of one window (ls[n_lines + 1] into data[0, n))
+    std::string window(const unsigned char *data, u64 n, const u64 *ls, u64 n_lines, int open_tail, hipStream_t stream) {
+        if (n_lines >= CELLS_MAX_LINES) return "more than 268,435,455 lines in a window";
+        const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
+        CELLS_HIP(bc_at.reserve((size_t)n_lines * sizeof(u64)));
+        CELLS_HIP(meta.reserve((size_t)n_lines * sizeof(unsigned int)));
+        CELLS_HIP(probe.reserve((size_t)n_lines * sizeof(unsigned int)));
+        CELLS_HIP(bsum.reserve((size_t)blocks * sizeof(u64)));
+        u64 *st = (u64 *)state.p;
+        CELLS_HIP(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, 2 * sizeof(u64), stream));          // (the flags stay: any of them ends the device path)
+        hipLaunchKernelGGL(cells_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, ls, n_lines, open_tail, nfr_upper, mono_upper,
+                           hash_mask & (n_slots - 1u), (u64 *)bc_at.p, (unsigned int *)meta.p, (unsigned int *)probe.p, st);
+        u64 h[3] = {0, 0, 0};                            // unresolved, new, flags
+        for (unsigned int round = 0;; ++round) {
+            if (round) CELLS_HIP(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, sizeof(u64), stream));
+            hipLaunchKernelGGL(cells_claim, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, n_lines, (u64 *)slot.p, n_slots,
+                               slot_bits, round);
+            hipLaunchKernelGGL(cells_verify, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, n, (const u64 *)bc_at.p, (const unsigned int *)meta.p,
+                               (unsigned int *)probe.p, n_lines, (const u64 *)slot.p, n_slots, (const unsigned char *)arena.p, (const u64 *)off.p, n_cells,
+                               fill, round, st);
+            CELLS_HIP(hipMemcpyAsync(h, st + CELLS_S_UNRESOLVED, sizeof h, hipMemcpyDeviceToHost, stream));
+            CELLS_HIP(hipStreamSynchronize(stream));
+            if (h[2] & CELLS_F_MALFORMED) return "a malformed line";
+            if (h[2] & CELLS_F_BROKEN) return "the cell table is out of range";
+            if (h[2] & CELLS_F_FULL) return "the cell table is full";
+            if (h[0] == 0) break;
+            if (h[0] > n_lines || round + 1u >= CELLS_MAX_ROUNDS) return "the cell table is full";
+        }
+        hipLaunchKernelGGL(cells_number, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, (const unsigned int *)meta.p,
+                           (const u64 *)slot.p, n_slots, n_lines, (u64 *)bsum.p);
+        hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)bsum.p, blocks, st + CELLS_S_NEW);
+        CELLS_HIP(hipMemcpyAsync(h, st + CELLS_S_NEW, sizeof(u64), hipMemcpyDeviceToHost, stream));
+        CELLS_HIP(hipStreamSynchronize(stream));
+        const u64 n_new = h[0] >> 36, new_bytes = h[0] & ((1ull << 36) - 1ull);
+        if (n_new > n_lines || new_bytes > 255 * n_new) return "counts out of range";
+        if (n_cells + n_new > n_slots / 2) return "the cell table is full";
+        if (n_new) {
+            CELLS_HIP(arena.reserve((size_t)(fill + new_bytes), (size_t)fill, stream));
+            CELLS_HIP(off.reserve((size_t)(n_cells + n_new + 1) * sizeof(u64), (size_t)(n_cells + 1) * sizeof(u64), stream));
+            CELLS_HIP(cnt.reserve((size_t)(n_cells + n_new) * 3 * sizeof(u64), (size_t)n_cells * 3 * sizeof(u64), stream));
+            CELLS_HIP(hipMemsetAsync((u64 *)cnt.p + 3 * n_cells, 0, (size_t)n_new * 3 * sizeof(u64), stream));
+            hipLaunchKernelGGL(cells_adopt, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, (const u64 *)bc_at.p, (const unsigned int *)probe.p,
+                               (const unsigned int *)meta.p, (u64 *)slot.p, n_slots, n_lines, (const u64 *)bsum.p, n_cells, n_new, fill, new_bytes,
+                               (unsigned char *)arena.p, (u64 *)off.p);
+            n_cells += n_new;
+            fill += new_bytes;
+        }
+        int cell_bits = 1;
+        while (cell_bits < 32 && (1ull << cell_bits) < n_cells) ++cell_bits;
+        hipLaunchKernelGGL(cells_count, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, (const unsigned int *)meta.p,
+                           (const u64 *)slot.p, n_slots, n_lines, n_cells, cell_bits, (u64 *)cnt.p, st);
+        CELLS_HIP(hipGetLastError());
+        return std::string();
+    }
+
+    // the table comes to the host once, behind the last window
+    std::string finish(hipStream_t stream) {
+        u64 h[CELLS_S_WORDS];
+        std::vector<u64> h_off((size_t)n_cells + 1), h_cnt((size_t)n_cells * 3);
+        out->bytes.resize((size_t)fill);
+        CELLS_HIP(hipMemcpyAsync(h, state.p, sizeof h, hipMemcpyDeviceToHost, stream));
+        CELLS_HIP(hipMemcpyAsync(h_off.data(), off.p, h_off.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (n_cells) CELLS_HIP(hipMemcpyAsync(h_cnt.data(), cnt.p, h_cnt.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (fill) CELLS_HIP(hipMemcpyAsync(out->bytes.data(), arena.p, (size_t)fill, hipMemcpyDeviceToHost, stream));
+        CELLS_HIP(hipStreamSynchronize(stream));
+        if (h[CELLS_S_FLAGS] != 0) return "the cell table is out of range";
+        out->off.assign(h_off.begin(), h_off.end());
+        out->n_frag.resize((size_t)n_cells); out->n_nfr.resize((size_t)n_cells); out->n_mono.resize((size_t)n_cells);
+        u64 assigned = 0;
+        for (size_t k = 0; k < (size_t)n_cells; ++k) {
+            if (h_off[k + 1] <= h_off[k] || h_off[k + 1] - h_off[k] > 255 || h_off[k + 1] > fill) return "the cell table is out of range";
+            out->n_frag[k] = (int64_t)h_cnt[3 * k];
+            out->n_nfr[k] = (int64_t)h_cnt[3 * k + 1];
+            out->n_mono[k] = (int64_t)h_cnt[3 * k + 2];
+            assigned += h_cnt[3 * k];
+        }
+        if (h_off[(size_t)n_cells] != fill || assigned + h[CELLS_S_UNASSIGNED] != h[CELLS_S_DATA]) return "the cell table is out of range";
+        out->n_data = (int64_t)h[CELLS_S_DATA];
+        out->n_unassigned = (int64_t)h[CELLS_S_UNASSIGNED];
+        return std::string();
+    }
+#undef CELLS_HIP
+};
+
 // what a split adds to decode_device: the table, the builder both paths share and the per-barcode counts (table->group.size() of them)
 struct SplitJob {
     const natac_fragio::SplitTableHost *table;
@@ -357,8 +670,9 @@ struct SplitJob {
 
 // Returns the same object as natac_fragio::decode, or nullptr: the host decoder answers (`why` says what stopped the device path).
 // With `split` the returned object is empty (a token of success): the groups are in split->sb, the counts in split->bc_count.
+// With `cells` likewise: the table is in cells->out.
 inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std::string &why, size_t window_bytes = (size_t)1 << 30,
-                                       SplitJob *split = nullptr) {
+                                       SplitJob *split = nullptr, CellsJob *cells = nullptr) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) { why = std::string("cannot open ") + path; return nullptr; }
     struct stat sb;
@@ -402,6 +716,7 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
     for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
     FRAGDEV_HIP(d_status.reserve(4 * sizeof(int)));
     FRAGDEV_HIP(d_total.reserve(4 * sizeof(u64)));
+    if (cells) { const std::string stop = cells->start(stream); if (!stop.empty()) return give_up(stop); }
     if (split) {                                         // the table goes up once
         const natac_fragio::SplitTableHost &t = *split->table;
         G = t.n_groups;
@@ -551,132 +866,141 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
                 if (open_tail) FRAGDEV_HIP(hipMemcpyAsync(ls + n_lines, &behind, sizeof behind, hipMemcpyHostToDevice, stream));
                 FRAGDEV_HIP(hipMemcpyAsync(&cur, ls + n_nl, sizeof cur, hipMemcpyDeviceToHost, stream));
                 lap(t_lines);
-                // ---- (b) parse
-                const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
-                FRAGDEV_HIP(d_code.reserve((size_t)n_lines * sizeof(u64)));
-                FRAGDEV_HIP(d_start.reserve((size_t)n_lines * sizeof(int)));
-                FRAGDEV_HIP(d_end.reserve((size_t)n_lines * sizeof(int)));
-                FRAGDEV_HIP(d_nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
-                FRAGDEV_HIP(d_bsum.reserve((size_t)blocks * sizeof(u64)));
-                if (split) {
-                    FRAGDEV_HIP(d_grp.reserve((size_t)n_lines * sizeof(int)));
-                    hipLaunchKernelGGL(frag_split_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
-                                       open_tail, dev_tb, bc_bits, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (int *)d_grp.p,
-                                       (u64 *)d_bcc.p, (u64 *)d_bsum.p, (int *)d_status.p);
-                } else
-                    hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
-                                       open_tail, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p,
-                                       (int *)d_status.p);
-                hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_bsum.p, blocks, (u64 *)d_total.p + 1);
-                u64 packed = 0;
-                FRAGDEV_HIP(hipMemcpyAsync(&packed, (u64 *)d_total.p + 1, sizeof packed, hipMemcpyDeviceToHost, stream));
-                FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
-                FRAGDEV_HIP(hipStreamSynchronize(stream));
-                if (st[0] != 0) return give_up("a malformed line");
-                const u64 n_data = packed >> 32, n_runs = packed & 0xffffffffull;
-                if (n_data > n_lines || n_runs > n_data || cur > n) return give_up("counts out of range");
-                if (n_runs > MAX_RUNS) return give_up("more than 65,536 chromosome runs in a window");
-                if (split && n_runs * (u64)G > SPLIT_MAX_SEGMENTS) return give_up("more than 1,048,576 groups x chromosome runs in a window");
-                if (open_tail) cur = n;
-                lap(t_parse);
-                // ---- (c) compaction, the run names, and the append on the host
-                if (n_data && split) {
-                    FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
-                    FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
-                    FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
-                    FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
-                    FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
-                    FRAGDEV_HIP(d_lrun.reserve((size_t)n_lines * sizeof(int)));
-                    const u64 n_tiles = (n_lines + PART_LINES - 1) / PART_LINES, n_seg = n_runs * (u64)G;
-                    FRAGDEV_HIP(d_thist.reserve((size_t)(n_tiles * (u64)G) * sizeof(u64)));
-                    FRAGDEV_HIP(d_seg.reserve((size_t)n_seg * sizeof(unsigned int)));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_seg.p, 0, (size_t)n_seg * sizeof(unsigned int), stream));
-                    hipLaunchKernelGGL(frag_split_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
-                                       (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data, (unsigned int)n_runs,
-                                       (u64 *)d_rfirst.p, (u64 *)d_rname.p, (unsigned int *)d_rnlen.p, (int *)d_rmax.p, (int *)d_lrun.p);
-                    hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
-                                       (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
-                    hipLaunchKernelGGL(frag_split_hist, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p, n_lines, G,
-                                       (unsigned int)n_runs, n_tiles, (u64 *)d_thist.p, (unsigned int *)d_seg.p);
-                    hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_thist.p, n_tiles * (u64)G, (u64 *)d_total.p + 2);
-                    u64 n_assigned = 0;
-                    FRAGDEV_HIP(hipMemcpyAsync(&n_assigned, (u64 *)d_total.p + 2, sizeof n_assigned, hipMemcpyDeviceToHost, stream));
-                    h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256); h_seg.resize((size_t)n_seg);
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_seg.data(), d_seg.p, (size_t)n_seg * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                if (cells) {                             // ---- discovery: the table grows by this window's lines (CellsJob)
                     FRAGDEV_HIP(hipStreamSynchronize(stream));
-                    if (n_assigned > n_data) return give_up("counts out of range");
-                    if (n_assigned) {                    // unassigned lines stay on the device
-                        FRAGDEV_HIP(d_ostart.reserve((size_t)n_assigned * sizeof(int)));
-                        FRAGDEV_HIP(d_oend.reserve((size_t)n_assigned * sizeof(int)));
-                        hipLaunchKernelGGL(frag_split_scatter, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p,
-                                           (const int *)d_start.p, (const int *)d_end.p, n_lines, G, (unsigned int)n_runs, n_tiles, (const u64 *)d_thist.p,
-                                           n_assigned, (int *)d_ostart.p, (int *)d_oend.p);
-                        h_start.resize(n_assigned); h_end.resize(n_assigned);
-                        FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+                    if (cur > n) return give_up("counts out of range");
+                    const std::string stop = cells->window((const unsigned char *)data, n, (const u64 *)ls, n_lines, open_tail, stream);
+                    if (!stop.empty()) return give_up(stop);
+                    if (open_tail) cur = n;
+                    lap(t_parse);
+                } else {
+                    // ---- (b) parse
+                    const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
+                    FRAGDEV_HIP(d_code.reserve((size_t)n_lines * sizeof(u64)));
+                    FRAGDEV_HIP(d_start.reserve((size_t)n_lines * sizeof(int)));
+                    FRAGDEV_HIP(d_end.reserve((size_t)n_lines * sizeof(int)));
+                    FRAGDEV_HIP(d_nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
+                    FRAGDEV_HIP(d_bsum.reserve((size_t)blocks * sizeof(u64)));
+                    if (split) {
+                        FRAGDEV_HIP(d_grp.reserve((size_t)n_lines * sizeof(int)));
+                        hipLaunchKernelGGL(frag_split_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
+                                           open_tail, dev_tb, bc_bits, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (int *)d_grp.p,
+                                           (u64 *)d_bcc.p, (u64 *)d_bsum.p, (int *)d_status.p);
+                    } else
+                        hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
+                                           open_tail, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p,
+                                           (int *)d_status.p);
+                    hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_bsum.p, blocks, (u64 *)d_total.p + 1);
+                    u64 packed = 0;
+                    FRAGDEV_HIP(hipMemcpyAsync(&packed, (u64 *)d_total.p + 1, sizeof packed, hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
+                    FRAGDEV_HIP(hipStreamSynchronize(stream));
+                    if (st[0] != 0) return give_up("a malformed line");
+                    const u64 n_data = packed >> 32, n_runs = packed & 0xffffffffull;
+                    if (n_data > n_lines || n_runs > n_data || cur > n) return give_up("counts out of range");
+                    if (n_runs > MAX_RUNS) return give_up("more than 65,536 chromosome runs in a window");
+                    if (split && n_runs * (u64)G > SPLIT_MAX_SEGMENTS) return give_up("more than 1,048,576 groups x chromosome runs in a window");
+                    if (open_tail) cur = n;
+                    lap(t_parse);
+                    // ---- (c) compaction, the run names, and the append on the host
+                    if (n_data && split) {
+                        FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
+                        FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
+                        FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
+                        FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
+                        FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
+                        FRAGDEV_HIP(d_lrun.reserve((size_t)n_lines * sizeof(int)));
+                        const u64 n_tiles = (n_lines + PART_LINES - 1) / PART_LINES, n_seg = n_runs * (u64)G;
+                        FRAGDEV_HIP(d_thist.reserve((size_t)(n_tiles * (u64)G) * sizeof(u64)));
+                        FRAGDEV_HIP(d_seg.reserve((size_t)n_seg * sizeof(unsigned int)));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_seg.p, 0, (size_t)n_seg * sizeof(unsigned int), stream));
+                        hipLaunchKernelGGL(frag_split_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
+                                           (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data, (unsigned int)n_runs,
+                                           (u64 *)d_rfirst.p, (u64 *)d_rname.p, (unsigned int *)d_rnlen.p, (int *)d_rmax.p, (int *)d_lrun.p);
+                        hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
+                                           (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
+                        hipLaunchKernelGGL(frag_split_hist, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p, n_lines, G,
+                                           (unsigned int)n_runs, n_tiles, (u64 *)d_thist.p, (unsigned int *)d_seg.p);
+                        hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_thist.p, n_tiles * (u64)G, (u64 *)d_total.p + 2);
+                        u64 n_assigned = 0;
+                        FRAGDEV_HIP(hipMemcpyAsync(&n_assigned, (u64 *)d_total.p + 2, sizeof n_assigned, hipMemcpyDeviceToHost, stream));
+                        h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256); h_seg.resize((size_t)n_seg);
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_seg.data(), d_seg.p, (size_t)n_seg * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
                         FRAGDEV_HIP(hipStreamSynchronize(stream));
-                    }
-                    run_chrom.resize(n_runs);
-                    for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                        const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
-                        if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
-                        run_chrom[r] = split->sb->chrom(std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), h_rmax[r], (int64_t)(b - a));
-                    }
-                    u64 at = 0;                          // the segments, group-major as the partition wrote them
-                    for (int g = 0; g < G; ++g)
+                        if (n_assigned > n_data) return give_up("counts out of range");
+                        if (n_assigned) {                    // unassigned lines stay on the device
+                            FRAGDEV_HIP(d_ostart.reserve((size_t)n_assigned * sizeof(int)));
+                            FRAGDEV_HIP(d_oend.reserve((size_t)n_assigned * sizeof(int)));
+                            hipLaunchKernelGGL(frag_split_scatter, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p,
+                                               (const int *)d_start.p, (const int *)d_end.p, n_lines, G, (unsigned int)n_runs, n_tiles, (const u64 *)d_thist.p,
+                                               n_assigned, (int *)d_ostart.p, (int *)d_oend.p);
+                            h_start.resize(n_assigned); h_end.resize(n_assigned);
+                            FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+                            FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+                            FRAGDEV_HIP(hipStreamSynchronize(stream));
+                        }
+                        run_chrom.resize(n_runs);
                         for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                            const u64 cnt = h_seg[(size_t)g * (size_t)n_runs + r];
-                            if (cnt > n_assigned - at) return give_up("segment table out of range");
-                            for (u64 k = at; k < at + cnt; ++k) split->sb->append(g, run_chrom[r], h_start[(size_t)k], h_end[(size_t)k]);
-                            at += cnt;
+                            const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
+                            if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
+                            run_chrom[r] = split->sb->chrom(std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), h_rmax[r], (int64_t)(b - a));
                         }
-                    if (at != n_assigned) return give_up("segment table out of range");
-                } else if (n_data) {
-                    FRAGDEV_HIP(d_ostart.reserve((size_t)n_data * sizeof(int)));
-                    FRAGDEV_HIP(d_oend.reserve((size_t)n_data * sizeof(int)));
-                    FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
-                    FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
-                    FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
-                    FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
-                    FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
-                    FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                    hipLaunchKernelGGL(frag_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
-                                       (const int *)d_start.p, (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data,
-                                       (unsigned int)n_runs, (int *)d_ostart.p, (int *)d_oend.p, (u64 *)d_rfirst.p, (u64 *)d_rname.p,
-                                       (unsigned int *)d_rnlen.p, (int *)d_rmax.p);
-                    hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
-                                       (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
-                    h_start.resize(n_data); h_end.resize(n_data);
-                    h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256);
-                    FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipStreamSynchronize(stream));
-                    for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                        const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
-                        if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
-                        pos.resize((size_t)(b - a));
-                        tlen.resize((size_t)(b - a));
-                        for (u64 i = a; i < b; ++i) {
-                            pos[(size_t)(i - a)] = (int64_t)h_start[(size_t)i] - 4;
-                            tlen[(size_t)(i - a)] = (int64_t)h_end[(size_t)i] - (int64_t)h_start[(size_t)i] + 8;
+                        u64 at = 0;                          // the segments, group-major as the partition wrote them
+                        for (int g = 0; g < G; ++g)
+                            for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                                const u64 cnt = h_seg[(size_t)g * (size_t)n_runs + r];
+                                if (cnt > n_assigned - at) return give_up("segment table out of range");
+                                for (u64 k = at; k < at + cnt; ++k) split->sb->append(g, run_chrom[r], h_start[(size_t)k], h_end[(size_t)k]);
+                                at += cnt;
+                            }
+                        if (at != n_assigned) return give_up("segment table out of range");
+                    } else if (n_data) {
+                        FRAGDEV_HIP(d_ostart.reserve((size_t)n_data * sizeof(int)));
+                        FRAGDEV_HIP(d_oend.reserve((size_t)n_data * sizeof(int)));
+                        FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
+                        FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
+                        FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
+                        FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
+                        FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
+                        FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
+                        hipLaunchKernelGGL(frag_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
+                                           (const int *)d_start.p, (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data,
+                                           (unsigned int)n_runs, (int *)d_ostart.p, (int *)d_oend.p, (u64 *)d_rfirst.p, (u64 *)d_rname.p,
+                                           (unsigned int *)d_rnlen.p, (int *)d_rmax.p);
+                        hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
+                                           (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
+                        h_start.resize(n_data); h_end.resize(n_data);
+                        h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256);
+                        FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
+                        FRAGDEV_HIP(hipStreamSynchronize(stream));
+                        for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                            const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
+                            if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
+                            pos.resize((size_t)(b - a));
+                            tlen.resize((size_t)(b - a));
+                            for (u64 i = a; i < b; ++i) {
+                                pos[(size_t)(i - a)] = (int64_t)h_start[(size_t)i] - 4;
+                                tlen[(size_t)(i - a)] = (int64_t)h_end[(size_t)i] - (int64_t)h_start[(size_t)i] + 8;
+                            }
+                            natac_fragio::append_run(bd, std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), pos.data(), tlen.data(), (size_t)(b - a),
+                                                     h_rmax[r]);
                         }
-                        natac_fragio::append_run(bd, std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), pos.data(), tlen.data(), (size_t)(b - a),
-                                                 h_rmax[r]);
                     }
                 }
             }
@@ -695,6 +1019,7 @@ inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std
                      t_read, t_scan, t_inflate, t_lines, t_parse, t_out);
 #undef FRAGDEV_HIP
     if (pend != 0) return give_up("bytes left behind the last window");
+    if (cells) { const std::string stop = cells->finish(stream); if (!stop.empty()) return give_up(stop); }
     if (split) {
         std::vector<u64> h_bcc(split->table->group.size());
         split->bc_count.resize(h_bcc.size());

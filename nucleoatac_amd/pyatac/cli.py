@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | split | cellcounts` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | split | cellcounts` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -6,7 +6,9 @@ write the per-base insertion and fragment-centre coverage tracks, `bias` the per
 around such sites, per site and summed.  `split` is this package's own: it splits a single-cell fragment file by cell barcode into one
 store per cell group (a cluster, a sample, a whitelist) in one pass, each written as .npz or as a fragment file that every command above
 takes through --bam.  `cellcounts` is this package's own too: the cell-by-window count matrix of a single-cell fragment file (rows the BED
-windows, columns the barcodes of a table), sparse, as MatrixMarket text or .npz.  The other pyatac tools (vplot, bias_vplot) are not part of
+windows, columns the barcodes of a table), sparse, as MatrixMarket text or .npz.  `cells`, this package's own as well, comes before both: it
+discovers the barcodes of a single-cell fragment file with per-cell fragment counts and writes the table of those that pass the user's
+thresholds, which `split --groups` and `cellcounts --cells` take unchanged.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -129,14 +131,26 @@ def add_split_parser(sub):
                    help="Write every group as BASE.<group>.npz (default) or as BASE.<group>.tsv.gz with its .tbi")
 
 
+def add_cells_parser(sub):
+    p = sub.add_parser("cells", help="discover the cell barcodes of a single-cell fragment file, with per-cell QC counts")
+    p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
+    p.add_argument("--min_fragments", metavar="int", default=1000, type=int, help="A cell passes with at least this many fragments. Default is 1000")
+    p.add_argument("--max_nucleosome_signal", metavar="float", default=None, type=float,
+                   help="A cell passes only if mono-nucleosomal / nucleosome-free fragments is at most this. Default is no such test")
+    p.add_argument("--nfr_upper", metavar="int", default=147, type=int, help="Fragments shorter than this are nucleosome-free. Default is 147")
+    p.add_argument("--mono_upper", metavar="int", default=294, type=int,
+                   help="Fragments from --nfr_upper up to this (exclusive) are mono-nucleosomal. Default is 294")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the fragment file's name without its suffixes")
+
+
 def add_cellcounts_parser(sub):
     p = sub.add_parser("cellcounts", help="cell-by-window fragment count matrix of a single-cell fragment file")
     p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
     p.add_argument("--bed", metavar="bed_file", required=True, help="Windows in which to compute counts: the rows of the matrix")
     p.add_argument("--cells", metavar="table", required=True,
                    help="TAB-separated table whose first column lists the barcodes: the columns of the matrix, in order of first appearance "
-                        "(the table `split --groups` takes; a group column is not used).  Barcodes are not discovered from the fragment "
-                        "file: lines of a barcode the table does not list are left out")
+                        "(the table `split --groups` takes and `cells` writes; a group column is not used).  Barcodes are not discovered "
+                        "from the fragment file here: lines of a barcode the table does not list are left out")
     p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
     p.add_argument("--lower", metavar="int", default=0, type=int, help="lower limit on insert size. Default is 0")
     p.add_argument("--upper", metavar="int", default=500, type=int, help="upper limit on insert size.  Default is 500")
@@ -150,7 +164,8 @@ def pyatac_parser():
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
                                                                 "insertion, coverage and Tn5 bias tracks, fragment counts per window, "
                                                                 "nucleotide content and track signal around sites; a single-cell fragment file "
-                                                                "split by cell group, and its cell-by-window count matrix")
+                                                                "split by cell group, its cell-by-window count matrix, and the discovery "
+                                                                "of its cells")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -162,6 +177,7 @@ def pyatac_parser():
     add_counts_parser(sub)
     add_nucleotide_parser(sub)
     add_signal_parser(sub)
+    add_cells_parser(sub)
     add_split_parser(sub)
     add_cellcounts_parser(sub)
     return parser
@@ -229,6 +245,15 @@ def pyatac_main(args):
             get_signal(args)
         except (SignalError, BedColumnError) as e:
             sys.stderr.write("pyatac signal: %s\n" % e)
+            return 1
+    elif args.call == "cells":
+        from .._lib import NatacError
+        from .get_cells import CellsError, get_cells
+        print("---------Discovering cells---------------------------------------")
+        try:
+            get_cells(args)
+        except (CellsError, NatacError) as e:
+            sys.stderr.write("pyatac cells: %s\n" % e)
             return 1
     elif args.call == "split":
         from .._lib import NatacError

@@ -23,6 +23,19 @@ _FRAG_REASONS = dict(fields="fewer than three tab-separated fields", empty="empt
                      barcode="no barcode field")      # (only when splitting by barcode)
 
 
+class CellTable(object):
+    """the cells of a fragment file in order of first appearance (FragmentStore.discover_cells): barcodes (list of bytes), n_frag / n_nfr /
+    n_mono (int64 arrays, one entry per cell), n_data (the file's data lines) and n_unassigned (those of no cell)"""
+
+    def __init__(self, barcodes, n_frag, n_nfr, n_mono, n_data, n_unassigned):
+        self.barcodes = list(barcodes)
+        self.n_frag, self.n_nfr, self.n_mono = (np.ascontiguousarray(a, dtype=np.int64) for a in (n_frag, n_nfr, n_mono))
+        self.n_data, self.n_unassigned = int(n_data), int(n_unassigned)
+
+    def __len__(self):
+        return len(self.barcodes)
+
+
 class FragmentStore(object):
     """per-chromosome arrays of forward proper-pair reads: pos (leftmost coordinate, sorted), tlen (|template length|)"""
 
@@ -433,6 +446,87 @@ class FragmentStore(object):
         stores = [FragmentStore(names, [length[c] for c in names], {c: np.array(pos[g].get(c, []), np.int64) for c in names},
                                 {c: np.array(tl[g].get(c, []), np.int64) for c in names}) for g in range(n_groups)]
         return stores, bc_count, n_unassigned
+
+    @staticmethod
+    def discover_cells(path, nfr_upper=147, mono_upper=294, n_threads=0, device=None):
+        """Which cells a fragment file holds, with per-cell QC counts, in one pass: the barcode table that split_fragments and
+        from_fragments_cells take, built from the file itself.  Returns a CellTable.  The cells rule (include/natac.h states it,
+        csrc/natac_fragfile.hpp: barcode_line is it):
+
+        - every line is validated exactly as by split_fragments (the same checks, order, reasons and line numbers, "no barcode field"
+          checked last), and the barcode is the fourth field as the split rule defines it, byte for byte;
+        - a data line whose barcode is 1-255 bytes long belongs to the cell of that barcode; cells are numbered in order of first
+          appearance over the file's data lines (file order, not hash or thread order); a data line whose barcode is empty or longer
+          than 255 bytes is unassigned: validated, counted in n_unassigned, no error;
+        - with ilen = end - start, cell k has three exact int64 counters: n_frag[k] its data lines, n_nfr[k] those with
+          ilen < nfr_upper, n_mono[k] those with nfr_upper <= ilen < mono_upper; 0 < nfr_upper < mono_upper (the defaults, 147 and
+          294, are the usual nucleosome-free and mono-nucleosome classes of single-cell ATAC QC: defaults of a flag, not measured
+          values); one line is one fragment whatever its fifth column says;
+        - more than 8,388,608 distinct barcodes fail the call with a message naming the line at which the limit was passed;
+        - the result is a function of the file's bytes and the two bounds only: not of n_threads, the windows, the BGZF member size, the
+          container, or which path answered.
+
+        With device=True a BGZF file goes through natac_frag_cells_device (csrc/natac_fragfile_dev.hpp): the text is inflated and split
+        into lines on the device, and the table is built there from the file itself -- an open-addressing table of FIXED size (8,388,608
+        slots, at most half of them taken) in device memory that lives across windows; a slot is claimed by the smallest line of a window
+        and only matches after the bytes compared equal.  FragmentStore.last_frag_on_device tells whether the device answered (the host
+        path answers inside the call for everything from_fragments hands over, a line without a barcode field, a full table -- more
+        than 4,194,304 barcodes --, more than 268,435,455 lines in a window and a HIP failure).  Both paths give the same table.
+        Measured on the MI355X box (tools/bench_bam.py 20000000 --cells, one box, one run): the 10.0 M lines and 10,000 cells of the
+        split's file, 127 MB BGZF: device 0.094 s and, called again, 0.088 s; host 0.47 s with 16 threads, 0.76 s with 4; the plain
+        device decode of the same file 0.13 s (it brings every record back, this call only the table).  The device is the faster
+        path there, so device=None takes it on a GPU box as split_fragments does (NATAC_DEVICE_BAM=0: the host)."""
+        import ctypes as C
+        from .. import _lib as L
+        lib = L.load()
+        h = C.c_void_p()
+        if device is None:
+            from ..device import Context
+            device = os.environ.get("NATAC_DEVICE_BAM", "1") != "0" and Context.device_count() > 0
+        if device:
+            from .. import get_context
+            on_dev = C.c_int(0)
+            L.check(lib.natac_frag_cells_device(get_context()._h, str(path).encode(), int(nfr_upper), int(mono_upper), C.byref(h), C.byref(on_dev)))
+            FragmentStore.last_frag_on_device = bool(on_dev.value)
+        else:
+            L.check(lib.natac_frag_cells(str(path).encode(), int(n_threads), int(nfr_upper), int(mono_upper), C.byref(h)))
+            FragmentStore.last_frag_on_device = False
+        try:
+            n, nb, nd, nu = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+            L.check(lib.natac_cells_counts(h, C.byref(n), C.byref(nb), C.byref(nd), C.byref(nu)))
+            blob = np.zeros(nb.value + 1, dtype=np.uint8)
+            off = np.zeros(n.value + 1, dtype=np.int64)
+            counts = [np.zeros(n.value, dtype=np.int64) for _ in range(3)]
+            L.check(lib.natac_cells_read(h, n.value, nb.value, blob.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p),
+                                         *[a.ctypes.data_as(C.c_void_p) for a in counts]))
+        finally:
+            lib.natac_cells_close(h)
+        raw, o = blob.tobytes(), off.tolist()
+        return CellTable([raw[a:b] for a, b in zip(o[:-1], o[1:])], counts[0], counts[1], counts[2], nd.value, nu.value)
+
+    @staticmethod
+    def discover_cells_python(path, nfr_upper=147, mono_upper=294):
+        """pure-Python restatement of the cells rule of discover_cells, kept as an independent check of the native paths"""
+        if not 0 < nfr_upper < mono_upper:
+            raise ValueError("0 < nfr_upper < mono_upper does not hold")
+        index, counts = {}, []
+        n_data = n_unassigned = 0
+        for _, start, end, bc in FragmentStore._python_lines(path, need_barcode=True):
+            n_data += 1
+            if not 1 <= len(bc) <= 255:
+                n_unassigned += 1
+                continue
+            k = index.setdefault(bc, len(counts))
+            if k == len(counts):
+                counts.append([0, 0, 0])
+            ilen = end - start
+            counts[k][0] += 1
+            if ilen < nfr_upper:
+                counts[k][1] += 1
+            elif ilen < mono_upper:
+                counts[k][2] += 1
+        c = np.array(counts, dtype=np.int64).reshape(-1, 3)
+        return CellTable(list(index), c[:, 0].copy(), c[:, 1].copy(), c[:, 2].copy(), n_data, n_unassigned)
 
     def save_fragments(self, path):
         """write the store as a fragment file (chrom, start = pos + 4, end = pos + tlen - 4 per line, in the store's order: chromosome

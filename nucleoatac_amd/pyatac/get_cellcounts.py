@@ -13,7 +13,8 @@ if lower <= ilen < upper and its left or its right end lies in the window.  Wind
 them, rows stay in BED order; overlapping, repeated and unsorted windows are counted independently.  A fragment file has no sequence
 dictionary, so a window on a chromosome the file never mentions is an empty row, not an error.  The matrix columns are the barcodes of
 the --cells table (the table `split --groups` takes; its group column is not used) in order of first appearance; lines of other barcodes
-are unassigned and only counted in the summary.  Discovering the barcodes from the file is not part of the command.
+are unassigned and only counted in the summary.  Discovering the barcodes from the file is not part of the command: `pyatac cells`
+(get_cells.py) does that and writes the table this command takes.
 
 Measured on the MI355X box (tools/bench_cellcounts.py, one box, one run: 10 M fragments in 10,000 cells, 99 MB BGZF, 100,000
 non-overlapping 500-base windows on 4 chromosomes, 3.13 M entries at 31 hits per row): the tagged read 0.56 s, the four device calls

@@ -5,7 +5,9 @@ With --fragments, after the BAM run: the fragment file of the same BAM's kept re
 same members and level) through natac_frag_open_device and through natac_frag_open at 16 and at 4 threads, on the same box.
 With --split, after the BAM run: the same kept reads as a single-cell fragment file (barcodes drawn from a pool of 10,000 cells, 90 % of
 them listed, assigned round-robin to G = 1, 16 and 255 groups) through natac_frag_split_device, natac_frag_split at 16 and at 4 threads,
-and the plain device decode of that same file, in the same run."""
+and the plain device decode of that same file, in the same run.
+With --cells, after the BAM run: that same single-cell file (10,000 cells) through natac_frag_cells_device, natac_frag_cells at 16 and at
+4 threads, and the plain device decode of the same file, in the same run."""
 import os
 import struct
 import sys
@@ -94,10 +96,8 @@ def bench_fragments(d, store):
               % (threads, n, same, dt, n / dt / 1e6, size / dt / 1e6, len(text) / dt / 1e6))
 
 
-def bench_split(d, store):
-    """per G four times: device split, host split at 16 and at 4 threads, the plain device decode of the same file"""
-    from nucleoatac_amd.device import Context
-    from nucleoatac_amd.pyatac.fragments import FragmentStore
+def single_cell_file(d, store):
+    """the kept reads of `store` as a single-cell fragment file -> (path, lines, cells, the 90 % of them a split lists)"""
     rng = np.random.default_rng(2)
     pool = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, (10000, 16), dtype=np.uint8)].view("S16").ravel()
     pool = np.unique(pool)
@@ -114,12 +114,42 @@ def bench_split(d, store):
     bgzf_write(path, text)
     size, n = os.path.getsize(path), sum(len(store.pos[c]) for c in store.references)
     print("single-cell fragment file: %d lines, %d cells (%d listed), %.0f MB of text, %.0f MB compressed" % (n, len(cells), len(listed), len(text) / 1e6, size / 1e6))
-    gpu = Context.device_count() > 0
+    return path, n, cells, listed
 
-    def timed(fn):
-        t0 = time.perf_counter()
-        out = fn()
-        return out, time.perf_counter() - t0
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()
+    return out, time.perf_counter() - t0
+
+
+def bench_cells(d, store):
+    """device discovery twice (the first call pays the first launches), host discovery at 16 and at 4 threads, the plain device decode"""
+    from nucleoatac_amd.device import Context
+    from nucleoatac_amd.pyatac.fragments import FragmentStore
+    path, n, cells, _ = single_cell_file(d, store)
+    gpu = Context.device_count() > 0
+    if gpu:
+        FragmentStore.from_fragments(path, device=True)          # (the first call pays the first launches)
+    row, ref = [], None
+    for threads, device in ([(0, True), (0, True)] if gpu else []) + [(16, False), (4, False)]:
+        table, dt = timed(lambda: FragmentStore.discover_cells(path, n_threads=threads, device=device))
+        tag = ("device" if FragmentStore.last_frag_on_device else "device->host") if device else "host %d threads" % threads
+        sig = (table.barcodes, table.n_frag.tolist(), table.n_nfr.tolist(), table.n_mono.tolist(), table.n_data, table.n_unassigned)
+        ref = ref or sig
+        row.append("%s %.3f s%s" % (tag, dt, "" if sig == ref else " (DIFFERS)"))
+    if gpu:
+        _, dt = timed(lambda: FragmentStore.from_fragments(path, device=True))
+        row.append("plain device decode %.3f s" % dt)
+    print("cells  %d lines, %d cells found (%d in the pool), %d unassigned: %s" % (n, len(ref[0]), len(cells), ref[5], ", ".join(row)))
+
+
+def bench_split(d, store):
+    """per G four times: device split, host split at 16 and at 4 threads, the plain device decode of the same file"""
+    from nucleoatac_amd.device import Context
+    from nucleoatac_amd.pyatac.fragments import FragmentStore
+    path, n, cells, listed = single_cell_file(d, store)
+    gpu = Context.device_count() > 0
     if gpu:
         FragmentStore.from_fragments(path, device=True)          # (the first call pays the first launches)
     for G in (1, 16, 255):
@@ -138,7 +168,7 @@ def bench_split(d, store):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--fragments", "--split")]
+    args = [a for a in sys.argv[1:] if a not in ("--fragments", "--split", "--cells")]
     n = int(args[0]) if args else 4_000_000
     from nucleoatac_amd.pyatac.fragments import FragmentStore
     d = tempfile.mkdtemp(prefix="natac_bam_")
@@ -168,6 +198,8 @@ def main():
             bench_fragments(d, st)
         if "--split" in sys.argv:
             bench_split(d, st)
+        if "--cells" in sys.argv:
+            bench_cells(d, st)
     finally:
         import shutil
         shutil.rmtree(d, ignore_errors=True)
