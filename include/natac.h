@@ -501,11 +501,11 @@ void natac_bam_close(natac_bam *bam);
 int natac_bam_counts(natac_bam *bam, int32_t *n_refs, int64_t *n_records, int64_t *n_kept);
 int natac_bam_ref_info(natac_bam *bam, int32_t ref, char *name, size_t name_len, int64_t *length, int64_t *n_reads);
 int natac_bam_ref_reads(natac_bam *bam, int32_t ref, int64_t *pos, int64_t *tlen, int64_t n);
-/* The same extraction with the BGZF members inflated and the records walked ON THE DEVICE (csrc/natac_bam_dev.hpp: one lane per
- * member; the record chain through the members is confirmed link by link from the end of the header, so the result is exactly
- * natac_bam_open's).  A file whose chain cannot be confirmed -- or a HIP failure such as no memory for a window -- sends the file
- * through the host decoder inside this call; *on_device (may be NULL) tells which one answered.  Damaged files fail with the host
- * decoder's messages. */
+/* The same extraction with the BGZF members inflated and the records walked ON THE DEVICE (csrc/natac_bgzf_dev.hpp: the file in
+ * windows, one lane per member; csrc/natac_bam_dev.hpp: the record chain through the members is confirmed link by link from the end
+ * of the header, so the result is exactly natac_bam_open's).  A file whose chain cannot be confirmed -- or a HIP failure such as no
+ * memory for a window -- sends the file through the host decoder inside this call; *on_device (may be NULL) tells which one
+ * answered.  Damaged files fail with the host decoder's messages. */
 int natac_bam_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int *on_device);
 /* ---- fragment file (fragments.tsv.gz: Cell Ranger ATAC, the ENCODE pipeline, chromap, sinto, SnapATAC / ArchR) -> the same handle ----
  * THE FORMAT RULE (nucleoatac_amd/pyatac/fragments.py restates it; csrc/natac_fragfile.hpp: parse_line is it).
@@ -528,9 +528,9 @@ int natac_bam_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int
  * n_records = n_kept = the number of data lines. */
 int natac_frag_open(const char *path, int n_threads, natac_bam **out);
 /* The same with a BGZF file's members inflated (CRC-32 checked) and its text split into lines, parsed and compacted ON THE DEVICE
- * (csrc/natac_fragfile_dev.hpp).  The host decoder answers inside this call for another container, any malformed line or damaged
- * member (so the message is natac_frag_open's by construction), a line longer than a window, more than 65,536 chromosome runs in a
- * window, or a HIP failure; *on_device (may be NULL) tells which one answered. */
+ * (csrc/natac_bgzf_dev.hpp, csrc/natac_fragfile_dev.hpp: PlainJob).  The host decoder answers inside this call for another container,
+ * any malformed line or damaged member (so the message is natac_frag_open's by construction), a line longer than a window, more than
+ * 65,536 chromosome runs in a window, or a HIP failure; *on_device (may be NULL) tells which one answered. */
 int natac_frag_open_device(natac_ctx *ctx, const char *path, natac_bam **out, int *on_device);
 /* ---- a fragment file split by cell barcode: one pass, one handle per cell group (a cluster, a sample, a QC whitelist) ----
  * THE SPLIT RULE (csrc/natac_fragfile.hpp: split_line is it; nucleoatac_amd/pyatac/fragments.py restates it).
@@ -598,13 +598,13 @@ int natac_bam_ref_cells(natac_bam *bam, int32_t ref, int32_t *cell);
  *   natac_cells_close. */
 typedef struct natac_cells natac_cells;
 int natac_frag_cells(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, natac_cells **out);
-/* The same with a BGZF file inflated and split into lines ON THE DEVICE as by natac_frag_open_device, and the barcode table built there
- * from the file itself (csrc/natac_fragfile_dev.hpp: an open-addressing table in device memory that lives across windows; a slot is
- * claimed by the smallest line of a window, and only matches after the bytes compared equal; NATAC_SPLIT_HASH_BITS applies).  The table
- * has a FIXED size: 8,388,608 slots (NATAC_CELLS_DEV_SLOTS=<power of two> sets another: tests), of which at most half are taken.  The
- * host path answers inside this call for everything natac_frag_open_device hands over, for a line without a barcode field, for a full
- * table (more than slots / 2 barcodes: more than 4,194,304 by default), for more than 268,435,455 lines in a window and for a HIP
- * failure; *on_device (may be NULL) tells which one answered. */
+/* The same with a BGZF file inflated and split into lines ON THE DEVICE as by natac_frag_open_device, and the barcode table built
+ * there from the file itself (csrc/natac_fragfile_dev.hpp, CellsJob: an open-addressing table in device memory that lives across
+ * windows; a slot is claimed by the smallest line of a window, and only matches after the bytes compared equal; NATAC_SPLIT_HASH_BITS
+ * applies).  The table has a FIXED size: 8,388,608 slots (NATAC_CELLS_DEV_SLOTS=<power of two> sets another: tests), of which at most
+ * half are taken.  The host path answers inside this call for everything natac_frag_open_device hands over, for a line without a
+ * barcode field, for a full table (more than slots / 2 barcodes: more than 4,194,304 by default), for more than 268,435,455 lines in
+ * a window and for a HIP failure; *on_device (may be NULL) tells which one answered. */
 int natac_frag_cells_device(natac_ctx *ctx, const char *path, int32_t nfr_upper, int32_t mono_upper, natac_cells **out, int *on_device);
 int natac_cells_counts(natac_cells *cells, int64_t *n_cells, int64_t *n_bytes, int64_t *n_data, int64_t *n_unassigned);
 int natac_cells_read(natac_cells *cells, int64_t n_cells, int64_t n_bytes, void *bc_bytes, int64_t *bc_off, int64_t *n_frag, int64_t *n_nfr,

@@ -3436,18 +3436,40 @@ int natac_fasta_read(natac_fasta *fa, int32_t record, void *out, int64_t n) {
 
 /* ---------------- native BAM extractor ---------------- */
 
+// compressed bytes per window; the environment overrides (tests)
+static size_t env_window(const char *name, size_t window) {
+    if (const char *e = getenv(name)) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+    return window;
+}
+static size_t host_window() { return env_window("NATAC_BAM_WINDOW", (size_t)48 << 20); }              // the host decoders' streaming window
+static size_t bam_dev_window() { return env_window("NATAC_BAM_DEV_WINDOW", (size_t)8 << 30); }        // a device window of a BAM
+static size_t frag_dev_window() { return env_window("NATAC_FRAG_DEV_WINDOW", (size_t)1 << 30); }      // ... of a fragment file
+
+// is the file a sequence of BGZF members (the device decoders' container; anything else is the host decoders')
+static bool path_is_bgzf(const char *path) {
+    bool bgzf = false;
+    if (FILE *f = std::fopen(path, "rb")) {
+        unsigned char magic[1040];
+        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
+        std::fclose(f);
+    }
+    return bgzf;
+}
+
+// a decoder's end: the handle, or the decoder's message
+static int bam_handle(natac_bamio::Bam *impl, const char *path, const std::string &err, natac_bam **out) {
+    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
+    *out = new natac_bam();
+    (*out)->impl = impl;
+    return NATAC_OK;
+}
+
 int natac_bam_open(const char *path, int n_threads, natac_bam **out) {
     if (!path || !out) return fail(NATAC_E_ARG, "null argument");
     *out = nullptr;
     std::string err;
-    size_t window = (size_t)48 << 20;                 // compressed bytes per streaming window; NATAC_BAM_WINDOW overrides (tests)
-    if (const char *e = getenv("NATAC_BAM_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
-    natac_bamio::Bam *impl = natac_bamio::decode(path, n_threads, err, window);
-    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
-    natac_bam *h = new natac_bam();
-    h->impl = impl;
-    *out = h;
-    return NATAC_OK;
+    natac_bamio::Bam *impl = natac_bamio::decode(path, n_threads, err, host_window());
+    return bam_handle(impl, path, err, out);
 }
 
 int natac_bam_open_device(natac_ctx *c, const char *path, natac_bam **out, int *on_device) {
@@ -3455,41 +3477,21 @@ int natac_bam_open_device(natac_ctx *c, const char *path, natac_bam **out, int *
     *out = nullptr;
     HIPCHK(hipSetDevice(c->device));
     std::string err;
-    size_t window = (size_t)8 << 30;                  // compressed bytes per device window; NATAC_BAM_DEV_WINDOW overrides (tests)
-    if (const char *e = getenv("NATAC_BAM_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
     bool undecided = false;
-    natac_bamio::Bam *impl = natac_bamdev::decode_device(path, c->stream, err, &undecided, window);
+    natac_bamio::Bam *impl = natac_bamdev::decode_device(path, c->stream, err, &undecided, bam_dev_window());
     if (on_device) *on_device = impl ? 1 : 0;
-    if (!impl && undecided) {                         // the chain of record starts was not confirmed: the host decoder answers
-        size_t hw = (size_t)48 << 20;
-        if (const char *e = getenv("NATAC_BAM_WINDOW")) { const long long v = atoll(e); if (v > 0) hw = (size_t)v; }
-        impl = natac_bamio::decode(path, 0, err, hw);
-    }
-    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
-    natac_bam *h = new natac_bam();
-    h->impl = impl;
-    *out = h;
-    return NATAC_OK;
+    if (!impl && undecided) impl = natac_bamio::decode(path, 0, err, host_window());      // the chain of record starts was not confirmed: the host decoder answers
+    return bam_handle(impl, path, err, out);
 }
 
 /* ---------------- fragment files (fragments.tsv.gz) into the same handle ---------------- */
-
-static size_t frag_host_window() {                    // (compressed) bytes per streaming window; NATAC_BAM_WINDOW overrides (tests)
-    size_t window = (size_t)48 << 20;
-    if (const char *e = getenv("NATAC_BAM_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
-    return window;
-}
 
 int natac_frag_open(const char *path, int n_threads, natac_bam **out) {
     if (!path || !out) return fail(NATAC_E_ARG, "null argument");
     *out = nullptr;
     std::string err;
-    natac_bamio::Bam *impl = natac_fragio::decode(path, n_threads, err, frag_host_window());
-    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
-    natac_bam *h = new natac_bam();
-    h->impl = impl;
-    *out = h;
-    return NATAC_OK;
+    natac_bamio::Bam *impl = natac_fragio::decode(path, n_threads, err, host_window());
+    return bam_handle(impl, path, err, out);
 }
 
 int natac_frag_open_device(natac_ctx *c, const char *path, natac_bam **out, int *on_device) {
@@ -3497,28 +3499,16 @@ int natac_frag_open_device(natac_ctx *c, const char *path, natac_bam **out, int 
     *out = nullptr;
     if (on_device) *on_device = 0;
     HIPCHK(hipSetDevice(c->device));
-    bool bgzf = false;
-    if (FILE *f = std::fopen(path, "rb")) {
-        unsigned char magic[1040];
-        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
-        std::fclose(f);
-    }
     natac_bamio::Bam *impl = nullptr;
     std::string err;
-    if (bgzf) {                                       // other containers are the host decoder's
-        size_t window = (size_t)1 << 30;              // compressed bytes per device window; NATAC_FRAG_DEV_WINDOW overrides (tests)
-        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+    if (path_is_bgzf(path)) {                         // other containers are the host decoder's
         std::string why;
-        impl = natac_fragdev::decode_device(path, c->stream, why, window);
+        impl = natac_fragdev::decode_plain(path, c->stream, why, frag_dev_window());
         if (impl && on_device) *on_device = 1;
     }
     // not BGZF, a malformed line, a damaged file, a line longer than a window, too many runs or a HIP failure: the host decoder answers
-    if (!impl) impl = natac_fragio::decode(path, 0, err, frag_host_window());
-    if (!impl) return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
-    natac_bam *h = new natac_bam();
-    h->impl = impl;
-    *out = h;
-    return NATAC_OK;
+    if (!impl) impl = natac_fragio::decode(path, 0, err, host_window());
+    return bam_handle(impl, path, err, out);
 }
 
 /* ---------------- a fragment file split by cell barcode into one handle per group ---------------- */
@@ -3536,7 +3526,7 @@ static int frag_split_host(const char *path, int n_threads, const natac_fragio::
                            int64_t *n_unassigned) {
     std::vector<natac_bamio::Bam *> impl((size_t)table.n_groups, nullptr);
     std::string err;
-    if (!natac_fragio::decode_split(path, n_threads, table, impl.data(), bc_count, n_unassigned, err, frag_host_window()))
+    if (!natac_fragio::decode_split(path, n_threads, table, impl.data(), bc_count, n_unassigned, err, host_window()))
         return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
     for (int g = 0; g < table.n_groups; ++g) {
         out[g] = new natac_bam();
@@ -3564,7 +3554,7 @@ int natac_frag_open_cells(const char *path, int n_threads, int64_t n_barcodes, c
     if (const int rc = frag_split_table(n_barcodes, bc_bytes, bc_off, one_group.data(), 1, out, table)) return rc;
     natac_bamio::Bam *impl = nullptr;
     std::string err;
-    if (!natac_fragio::decode_split(path, n_threads, table, &impl, bc_count, n_unassigned, err, frag_host_window(), true))
+    if (!natac_fragio::decode_split(path, n_threads, table, &impl, bc_count, n_unassigned, err, host_window(), true))
         return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
     impl->tagged = true;
     *out = new natac_bam();
@@ -3579,21 +3569,12 @@ int natac_frag_split_device(natac_ctx *c, const char *path, int64_t n_barcodes, 
     natac_fragio::SplitTableHost table;
     if (const int rc = frag_split_table(n_barcodes, bc_bytes, bc_off, bc_group, n_groups, out, table)) return rc;
     HIPCHK(hipSetDevice(c->device));
-    bool bgzf = false;
-    if (FILE *f = std::fopen(path, "rb")) {
-        unsigned char magic[1040];
-        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
-        std::fclose(f);
-    }
-    if (bgzf && n_barcodes <= natac_fragdev::SPLIT_DEV_MAX_BARCODES) {      // other containers and larger tables are the host path's
-        size_t window = (size_t)1 << 30;
-        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+    if (path_is_bgzf(path) && n_barcodes <= natac_fragdev::SPLIT_DEV_MAX_BARCODES) {      // other containers and larger tables are the host path's
         natac_fragio::SplitBuilder sb(n_groups);
-        natac_fragdev::SplitJob job{&table, &sb, {}};
-        std::string why;
-        natac_bamio::Bam *token = natac_fragdev::decode_device(path, c->stream, why, window, &job);
-        if (token) {
-            delete token;
+        natac_fragdev::SplitJob job;
+        job.table = &table;
+        job.sb = &sb;
+        if (natac_fragdev::decode_device(path, c->stream, frag_dev_window(), job).empty()) {
             std::vector<natac_bamio::Bam *> impl((size_t)n_groups, nullptr);
             sb.finish(impl.data());
             for (int g = 0; g < n_groups; ++g) {
@@ -3615,7 +3596,7 @@ int natac_frag_split_device(natac_ctx *c, const char *path, int64_t n_barcodes, 
 static int frag_cells_host(const char *path, int n_threads, int32_t nfr_upper, int32_t mono_upper, natac_cells **out) {
     std::unique_ptr<natac_cells> h(new natac_cells());
     std::string err;
-    if (!natac_fragio::decode_cells(path, n_threads, nfr_upper, mono_upper, NATAC_SPLIT_MAX_BARCODES, &h->table, err, frag_host_window()))
+    if (!natac_fragio::decode_cells(path, n_threads, nfr_upper, mono_upper, NATAC_SPLIT_MAX_BARCODES, &h->table, err, host_window()))
         return fail(NATAC_E_ARG, "%s: %s", path, err.c_str());
     *out = h.release();
     return NATAC_OK;
@@ -3634,24 +3615,13 @@ int natac_frag_cells_device(natac_ctx *c, const char *path, int32_t nfr_upper, i
     if (on_device) *on_device = 0;
     if (!(0 < nfr_upper && nfr_upper < mono_upper)) return fail(NATAC_E_ARG, "0 < nfr_upper < mono_upper does not hold (got %d and %d)", nfr_upper, mono_upper);
     HIPCHK(hipSetDevice(c->device));
-    bool bgzf = false;
-    if (FILE *f = std::fopen(path, "rb")) {
-        unsigned char magic[1040];
-        bgzf = natac_fragio::is_bgzf(magic, std::fread(magic, 1, sizeof magic, f));
-        std::fclose(f);
-    }
-    if (bgzf) {                                       // other containers are the host path's
-        size_t window = (size_t)1 << 30;
-        if (const char *e = getenv("NATAC_FRAG_DEV_WINDOW")) { const long long v = atoll(e); if (v > 0) window = (size_t)v; }
+    if (path_is_bgzf(path)) {                         // other containers are the host path's
         std::unique_ptr<natac_cells> h(new natac_cells());
         natac_fragdev::CellsJob job;
         job.nfr_upper = nfr_upper;
         job.mono_upper = mono_upper;
         job.out = &h->table;
-        std::string why;
-        natac_bamio::Bam *token = natac_fragdev::decode_device(path, c->stream, why, window, nullptr, &job);
-        if (token) {
-            delete token;
+        if (natac_fragdev::decode_device(path, c->stream, frag_dev_window(), job).empty()) {
             *out = h.release();
             if (on_device) *on_device = 1;
             return NATAC_OK;
@@ -3691,7 +3661,7 @@ int natac_inflate_raw_host(const void *src, size_t csize, void *out, size_t isiz
     if ((!src && csize) || (!out && isize) || csize > 0xffffffffull || isize > 0xffffffffull) return -1;
     std::vector<unsigned char> padded(csize + 32, 0);        // the bit reader takes whole words: 32 readable bytes behind the payload
     if (csize) std::memcpy(padded.data(), src, csize);
-    return natac_bamdev::inflate_member_host(padded.data(), (unsigned int)csize, (unsigned char *)out, (unsigned int)isize);
+    return natac_bgzfdev::inflate_member_host(padded.data(), (unsigned int)csize, (unsigned char *)out, (unsigned int)isize);
 }
 
 void natac_bam_close(natac_bam *bam) {

@@ -1,18 +1,21 @@
 // natac_fragfile_dev.hpp -- BGZF fragment file -> fragment arrays on the GPU.
 //
-// The members are found, staged and inflated exactly as for a BAM (natac_bam_dev.hpp: walk_chain, two pinned staging buffers,
-// bamdev_inflate with its CRC check).  What follows the inflate differs: a window's inflated bytes are TEXT, and a line may start
-// anywhere and straddle any number of members, so nothing here works per member.  On the window's contiguous text:
+// The members are found, staged, inflated and CRC-checked exactly as for a BAM: both decoders read the file through
+// natac_bgzf_dev.hpp's DevWindows.  What follows the inflate differs: a window's inflated bytes are TEXT, and a line may start
+// anywhere and straddle any number of members, so nothing here works per member.  decode_device<Job> is the driver: per window it
+// builds the line index (a), hands the lines to the job and carries the bytes behind the window's last '\n' to the front of the next.
+// A job is start / window / finish, each returning "" or the reason the device path stops, and owns its device buffers and host
+// vectors.  Every device read is bounded by the window's length n, whatever the text holds.
 //   (a) frag_count_nl / frag_scan / frag_line_starts: every lane loads 16 bytes and builds a newline mask; the per-tile counts are
 //       scanned and become the offsets at which the lanes write the line starts.
+// PlainJob (natac_frag_open_device; decode_plain):
 //   (b) frag_parse: one lane per line runs natac_fragio::parse_line (the host decoder's own classifier) and compares the line's
 //       chromosome field byte-wise with the previous data line's: a difference starts a RUN.
 //   (c) frag_compact: a scan over (is data, starts a run) gives every data line its output slot and its run; start / end are
 //       written in file order, and per run its first slot, the offset and length of its name and its largest end.
-// The host reads the few run names back (frag_gather_names), maps them to chromosome ids with the host decoder's dictionary (this is
-// where a chromosome that comes back gets its old id) and appends.  The bytes behind a window's last '\n' are carried to the front
-// of the next window.  Every device read is bounded by the window's length n, whatever the text holds.
-// Splitting by cell barcode (natac_frag_split_device; decode_device with a SplitJob) keeps (a) and runs its own kernels behind it:
+//   The host reads the few run names back (RunTable: frag_gather_names), maps them to chromosome ids with the host decoder's dictionary
+//   (this is where a chromosome that comes back gets its old id) and appends.
+// SplitJob (natac_frag_split_device), splitting by cell barcode:
 //   (b') frag_split_parse: frag_parse with natac_fragio::split_line, so every data line also gets its group (or -1) from the barcode
 //        table, and the exact per-barcode counts grow by one integer atomic per set of lanes of a wave that share a barcode.
 //   (c') frag_split_compact: the run tables over ALL data lines as in (c), and every line's run instead of the compacted start / end.
@@ -21,22 +24,22 @@
 //        slot; the wave then walks its tile in file order, 64 lines a round, and gives the lanes of a group consecutive slots in lane
 //        order.  The counts of every (group, run) segment come from the same histogram.  Integers only: nothing depends on order.
 //   The host gets start / end of the assigned lines only, in group-major order, and the segment counts, and appends segment by segment.
-// Discovering the cells (natac_frag_cells_device; decode_device with a CellsJob) keeps (a) too and needs no runs: cells_parse, rounds of
-// cells_claim / cells_verify, cells_number / cells_adopt and cells_count build the barcode table from the file itself (see CellsJob below).
+// CellsJob (natac_frag_cells_device), discovering the cells, needs no runs: cells_parse, rounds of cells_claim / cells_verify,
+// cells_number / cells_adopt and cells_count build the barcode table from the file itself (see CellsJob below).
 // The host decoder answers instead (the caller runs it) for: a malformed line or a damaged file (so both paths give the same message
 // by construction), a window without any line end, more than MAX_RUNS runs in a window, a HIP failure;
 // when splitting also for a line without a barcode field (malformed), a table of more than SPLIT_DEV_MAX_BARCODES barcodes and more than
 // SPLIT_MAX_SEGMENTS groups x runs in a window; when discovering cells for a line without a barcode field, a full table (more than half
 // the slots taken: more than SPLIT_DEV_MAX_BARCODES cells with the default size) and more than 268,435,455 lines in a window.
 #pragma once
-#include "natac_bam_dev.hpp"
+#include <memory>
+#include "natac_bgzf_dev.hpp"
 #include "natac_fragfile.hpp"
 
 namespace natac_fragdev {
 
-using natac_bamdev::Chain;
-using natac_bamdev::DevBuf;
-using natac_bamdev::Member;
+using natac_bgzfdev::DevWindows;
+using natac_bgzfdev::DevBuf;
 typedef unsigned long long u64;
 
 constexpr int TILE_T = 256;                 // lanes per workgroup
@@ -543,8 +546,16 @@ __global__ void __launch_bounds__(TILE_T) cells_count(const unsigned int *__rest
     }
 }
 
-// What a discovery adds to decode_device: the table on the device and the per-window work behind the line index.
-struct CellsJob {
+// ---- the jobs ----
+// what the driver's clock needs of a job: parsed() marks where the "parse" phase of NATAC_FRAG_DEV_TIMING ends inside window()
+struct FragJob {
+    natac_bgzfdev::Laps *laps = nullptr;
+    double t_parse = 0;
+    void parsed() { if (laps) laps->lap(t_parse); }
+};
+
+// Discovery: the table on the device and the per-window work behind the line index.
+struct CellsJob : FragJob {
     int nfr_upper = 147, mono_upper = 294;
     natac_fragio::Cells *out = nullptr;
     unsigned int n_slots = 1u << 23, hash_mask = 0xffffffffu;
@@ -562,43 +573,43 @@ struct CellsJob {
         if (const char *e = getenv("NATAC_SPLIT_HASH_BITS")) { const int b = atoi(e); if (b >= 0 && b < 32) hash_mask = (1u << b) - 1u; }
     }
 
-#define CELLS_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return std::string(#expr) + ": " + hipGetErrorString(e_); } } while (0)
     // "" or what stops the device path
     std::string start(hipStream_t stream) {
         configure();
-        CELLS_HIP(slot.reserve((size_t)n_slots * sizeof(u64)));
-        CELLS_HIP(state.reserve(CELLS_S_WORDS * sizeof(u64)));
-        CELLS_HIP(off.reserve(4096 * sizeof(u64)));
-        CELLS_HIP(arena.reserve(65536));
-        CELLS_HIP(cnt.reserve(3 * 4096 * sizeof(u64)));
-        CELLS_HIP(hipMemsetAsync(slot.p, 0xff, (size_t)n_slots * sizeof(u64), stream));          // CELLS_EMPTY
-        CELLS_HIP(hipMemsetAsync(state.p, 0, CELLS_S_WORDS * sizeof(u64), stream));
-        CELLS_HIP(hipMemsetAsync(off.p, 0, sizeof(u64), stream));                                 // off[0]
+        NATAC_DEV_TRY(slot.reserve((size_t)n_slots * sizeof(u64)));
+        NATAC_DEV_TRY(state.reserve(CELLS_S_WORDS * sizeof(u64)));
+        NATAC_DEV_TRY(off.reserve(4096 * sizeof(u64)));
+        NATAC_DEV_TRY(arena.reserve(65536));
+        NATAC_DEV_TRY(cnt.reserve(3 * 4096 * sizeof(u64)));
+        NATAC_DEV_TRY(hipMemsetAsync(slot.p, 0xff, (size_t)n_slots * sizeof(u64), stream));          // CELLS_EMPTY
+        NATAC_DEV_TRY(hipMemsetAsync(state.p, 0, CELLS_S_WORDS * sizeof(u64), stream));
+        NATAC_DEV_TRY(hipMemsetAsync(off.p, 0, sizeof(u64), stream));                                 // off[0]
         return std::string();
     }
 
     // the lines of one window (ls[n_lines + 1] into data[0, n))
     std::string window(const unsigned char *data, u64 n, const u64 *ls, u64 n_lines, int open_tail, hipStream_t stream) {
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));            // the line index is complete
         if (n_lines >= CELLS_MAX_LINES) return "more than 268,435,455 lines in a window";
         const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
-        CELLS_HIP(bc_at.reserve((size_t)n_lines * sizeof(u64)));
-        CELLS_HIP(meta.reserve((size_t)n_lines * sizeof(unsigned int)));
-        CELLS_HIP(probe.reserve((size_t)n_lines * sizeof(unsigned int)));
-        CELLS_HIP(bsum.reserve((size_t)blocks * sizeof(u64)));
+        NATAC_DEV_TRY(bc_at.reserve((size_t)n_lines * sizeof(u64)));
+        NATAC_DEV_TRY(meta.reserve((size_t)n_lines * sizeof(unsigned int)));
+        NATAC_DEV_TRY(probe.reserve((size_t)n_lines * sizeof(unsigned int)));
+        NATAC_DEV_TRY(bsum.reserve((size_t)blocks * sizeof(u64)));
         u64 *st = (u64 *)state.p;
-        CELLS_HIP(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, 2 * sizeof(u64), stream));          // (the flags stay: any of them ends the device path)
+        NATAC_DEV_TRY(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, 2 * sizeof(u64), stream));          // (the flags stay: any of them ends the device path)
         hipLaunchKernelGGL(cells_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, ls, n_lines, open_tail, nfr_upper, mono_upper,
                            hash_mask & (n_slots - 1u), (u64 *)bc_at.p, (unsigned int *)meta.p, (unsigned int *)probe.p, st);
         u64 h[3] = {0, 0, 0};                            // unresolved, new, flags
         for (unsigned int round = 0;; ++round) {
-            if (round) CELLS_HIP(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, sizeof(u64), stream));
+            if (round) NATAC_DEV_TRY(hipMemsetAsync(st + CELLS_S_UNRESOLVED, 0, sizeof(u64), stream));
             hipLaunchKernelGGL(cells_claim, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, n_lines, (u64 *)slot.p, n_slots,
                                slot_bits, round);
             hipLaunchKernelGGL(cells_verify, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, n, (const u64 *)bc_at.p, (const unsigned int *)meta.p,
                                (unsigned int *)probe.p, n_lines, (const u64 *)slot.p, n_slots, (const unsigned char *)arena.p, (const u64 *)off.p, n_cells,
                                fill, round, st);
-            CELLS_HIP(hipMemcpyAsync(h, st + CELLS_S_UNRESOLVED, sizeof h, hipMemcpyDeviceToHost, stream));
-            CELLS_HIP(hipStreamSynchronize(stream));
+            NATAC_DEV_TRY(hipMemcpyAsync(h, st + CELLS_S_UNRESOLVED, sizeof h, hipMemcpyDeviceToHost, stream));
+            NATAC_DEV_TRY(hipStreamSynchronize(stream));
             if (h[2] & CELLS_F_MALFORMED) return "a malformed line";
             if (h[2] & CELLS_F_BROKEN) return "the cell table is out of range";
             if (h[2] & CELLS_F_FULL) return "the cell table is full";
@@ -608,16 +619,16 @@ struct CellsJob {
         hipLaunchKernelGGL(cells_number, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, (const unsigned int *)meta.p,
                            (const u64 *)slot.p, n_slots, n_lines, (u64 *)bsum.p);
         hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)bsum.p, blocks, st + CELLS_S_NEW);
-        CELLS_HIP(hipMemcpyAsync(h, st + CELLS_S_NEW, sizeof(u64), hipMemcpyDeviceToHost, stream));
-        CELLS_HIP(hipStreamSynchronize(stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(h, st + CELLS_S_NEW, sizeof(u64), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
         const u64 n_new = h[0] >> 36, new_bytes = h[0] & ((1ull << 36) - 1ull);
         if (n_new > n_lines || new_bytes > 255 * n_new) return "counts out of range";
         if (n_cells + n_new > n_slots / 2) return "the cell table is full";
         if (n_new) {
-            CELLS_HIP(arena.reserve((size_t)(fill + new_bytes), (size_t)fill, stream));
-            CELLS_HIP(off.reserve((size_t)(n_cells + n_new + 1) * sizeof(u64), (size_t)(n_cells + 1) * sizeof(u64), stream));
-            CELLS_HIP(cnt.reserve((size_t)(n_cells + n_new) * 3 * sizeof(u64), (size_t)n_cells * 3 * sizeof(u64), stream));
-            CELLS_HIP(hipMemsetAsync((u64 *)cnt.p + 3 * n_cells, 0, (size_t)n_new * 3 * sizeof(u64), stream));
+            NATAC_DEV_TRY(arena.reserve((size_t)(fill + new_bytes), (size_t)fill, stream));
+            NATAC_DEV_TRY(off.reserve((size_t)(n_cells + n_new + 1) * sizeof(u64), (size_t)(n_cells + 1) * sizeof(u64), stream));
+            NATAC_DEV_TRY(cnt.reserve((size_t)(n_cells + n_new) * 3 * sizeof(u64), (size_t)n_cells * 3 * sizeof(u64), stream));
+            NATAC_DEV_TRY(hipMemsetAsync((u64 *)cnt.p + 3 * n_cells, 0, (size_t)n_new * 3 * sizeof(u64), stream));
             hipLaunchKernelGGL(cells_adopt, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, data, (const u64 *)bc_at.p, (const unsigned int *)probe.p,
                                (const unsigned int *)meta.p, (u64 *)slot.p, n_slots, n_lines, (const u64 *)bsum.p, n_cells, n_new, fill, new_bytes,
                                (unsigned char *)arena.p, (u64 *)off.p);
@@ -628,7 +639,8 @@ struct CellsJob {
         while (cell_bits < 32 && (1ull << cell_bits) < n_cells) ++cell_bits;
         hipLaunchKernelGGL(cells_count, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned int *)probe.p, (const unsigned int *)meta.p,
                            (const u64 *)slot.p, n_slots, n_lines, n_cells, cell_bits, (u64 *)cnt.p, st);
-        CELLS_HIP(hipGetLastError());
+        NATAC_DEV_TRY(hipGetLastError());
+        parsed();
         return std::string();
     }
 
@@ -637,11 +649,11 @@ struct CellsJob {
         u64 h[CELLS_S_WORDS];
         std::vector<u64> h_off((size_t)n_cells + 1), h_cnt((size_t)n_cells * 3);
         out->bytes.resize((size_t)fill);
-        CELLS_HIP(hipMemcpyAsync(h, state.p, sizeof h, hipMemcpyDeviceToHost, stream));
-        CELLS_HIP(hipMemcpyAsync(h_off.data(), off.p, h_off.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
-        if (n_cells) CELLS_HIP(hipMemcpyAsync(h_cnt.data(), cnt.p, h_cnt.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
-        if (fill) CELLS_HIP(hipMemcpyAsync(out->bytes.data(), arena.p, (size_t)fill, hipMemcpyDeviceToHost, stream));
-        CELLS_HIP(hipStreamSynchronize(stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(h, state.p, sizeof h, hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(h_off.data(), off.p, h_off.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (n_cells) NATAC_DEV_TRY(hipMemcpyAsync(h_cnt.data(), cnt.p, h_cnt.size() * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        if (fill) NATAC_DEV_TRY(hipMemcpyAsync(out->bytes.data(), arena.p, (size_t)fill, hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
         if (h[CELLS_S_FLAGS] != 0) return "the cell table is out of range";
         out->off.assign(h_off.begin(), h_off.end());
         out->n_frag.resize((size_t)n_cells); out->n_nfr.resize((size_t)n_cells); out->n_mono.resize((size_t)n_cells);
@@ -658,377 +670,294 @@ struct CellsJob {
         out->n_unassigned = (int64_t)h[CELLS_S_UNASSIGNED];
         return std::string();
     }
-#undef CELLS_HIP
 };
 
-// what a split adds to decode_device: the table, the builder both paths share and the per-barcode counts (table->group.size() of them)
-struct SplitJob {
-    const natac_fragio::SplitTableHost *table;
-    natac_fragio::SplitBuilder *sb;
+// ---- what PlainJob and SplitJob share: RunTable and LineParse ----
+// The runs of a window's data lines (a run: consecutive data lines of one chromosome), as frag_compact / frag_split_compact write them:
+// zero() in front of that kernel, gather() behind it, download() in front of the job's synchronise, span() / name() behind it.
+struct RunTable {
+    DevBuf d_first, d_name, d_nlen, d_max, d_names;
+    std::vector<u64> first;
+    std::vector<unsigned int> nlen;
+    std::vector<int> rmax;
+    std::vector<unsigned char> names;
+    std::string zero(u64 n_runs, hipStream_t stream) {
+        NATAC_DEV_TRY(d_first.reserve((size_t)n_runs * sizeof(u64)));
+        NATAC_DEV_TRY(d_name.reserve((size_t)n_runs * sizeof(u64)));
+        NATAC_DEV_TRY(d_nlen.reserve((size_t)n_runs * sizeof(unsigned int)));
+        NATAC_DEV_TRY(d_max.reserve((size_t)n_runs * sizeof(int)));
+        NATAC_DEV_TRY(d_names.reserve((size_t)n_runs * 256));
+        NATAC_DEV_TRY(hipMemsetAsync(d_max.p, 0, (size_t)n_runs * sizeof(int), stream));
+        NATAC_DEV_TRY(hipMemsetAsync(d_first.p, 0, (size_t)n_runs * sizeof(u64), stream));
+        NATAC_DEV_TRY(hipMemsetAsync(d_nlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
+        NATAC_DEV_TRY(hipMemsetAsync(d_name.p, 0, (size_t)n_runs * sizeof(u64), stream));
+        return std::string();
+    }
+    void gather(const unsigned char *data, u64 n, u64 n_runs, hipStream_t stream) {
+        hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, data, n, (const u64 *)d_name.p,
+                           (const unsigned int *)d_nlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
+    }
+    std::string download(u64 n_runs, hipStream_t stream) {
+        first.resize(n_runs); nlen.resize(n_runs); rmax.resize(n_runs); names.resize((size_t)n_runs * 256);
+        NATAC_DEV_TRY(hipMemcpyAsync(first.data(), d_first.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(nlen.data(), d_nlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(rmax.data(), d_max.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
+        return std::string();
+    }
+    // run r = the data lines [*a, *b) of the window's n_data; false: the table is out of range
+    bool span(size_t r, u64 n_data, u64 *a, u64 *b) const {
+        *a = first[r];
+        *b = r + 1 < first.size() ? first[r + 1] : n_data;
+        return !(*a >= *b || *b > n_data || nlen[r] == 0 || nlen[r] > 255);
+    }
+    std::string name(size_t r) const { return std::string((const char *)names.data() + r * 256, nlen[r]); }
+};
+
+// The per-line arrays frag_parse / frag_split_parse fill, and the counts behind them.  `flag` is the parse kernels' status word: zeroed
+// once, so a malformed line ends the device path in the window where it occurs (the counts are read behind every parse).
+struct LineParse {
+    DevBuf code, start, end, nlen, bsum, total;            // total: the scan's sum, and behind it the flag
+    u64 blocks = 0, n_data = 0, n_runs = 0;
+    u64 packed = 0;                         // host words of the asynchronous downloads
+    int malformed = 0;
+    int *flag() const { return (int *)((u64 *)total.p + 1); }
+    std::string begin(hipStream_t stream) {
+        NATAC_DEV_TRY(total.reserve(2 * sizeof(u64)));
+        NATAC_DEV_TRY(hipMemsetAsync(flag(), 0, sizeof(int), stream));
+        return std::string();
+    }
+    std::string reserve(u64 n_lines) {
+        blocks = (n_lines + TILE_T - 1) / TILE_T;
+        NATAC_DEV_TRY(code.reserve((size_t)n_lines * sizeof(u64)));
+        NATAC_DEV_TRY(start.reserve((size_t)n_lines * sizeof(int)));
+        NATAC_DEV_TRY(end.reserve((size_t)n_lines * sizeof(int)));
+        NATAC_DEV_TRY(nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
+        NATAC_DEV_TRY(bsum.reserve((size_t)blocks * sizeof(u64)));
+        return std::string();
+    }
+    // behind the parse kernel: bsum scanned in place (the compaction's block offsets), n_data and n_runs on the host; G: groups (0: no split)
+    std::string counts(u64 n_lines, int G, hipStream_t stream) {
+        hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)bsum.p, blocks, (u64 *)total.p);
+        NATAC_DEV_TRY(hipMemcpyAsync(&packed, total.p, sizeof packed, hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(&malformed, flag(), sizeof malformed, hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
+        if (malformed != 0) return "a malformed line";
+        n_data = packed >> 32;
+        n_runs = packed & 0xffffffffull;
+        if (n_data > n_lines || n_runs > n_data) return "counts out of range";
+        if (n_runs > MAX_RUNS) return "more than 65,536 chromosome runs in a window";
+        if (n_runs * (u64)G > SPLIT_MAX_SEGMENTS) return "more than 1,048,576 groups x chromosome runs in a window";
+        return std::string();
+    }
+};
+
+// ---- the plain decode: (b) frag_parse, (c) frag_compact, the run names, and the append on the host ----
+struct PlainJob : FragJob {
+    natac_fragio::Builder bd;
+    LineParse lp;
+    RunTable runs;
+    DevBuf d_ostart, d_oend;
+    std::vector<int> h_start, h_end;
+    std::vector<int64_t> pos, tlen;
+    explicit PlainJob(natac_bamio::Bam *bam) : bd(bam) {}
+    std::string start(hipStream_t stream) { return lp.begin(stream); }
+    std::string window(const unsigned char *data, u64 n, const u64 *ls, u64 n_lines, int open_tail, hipStream_t stream) {
+        NATAC_DEV_TRY(lp.reserve(n_lines));
+        hipLaunchKernelGGL(frag_parse, dim3((unsigned)lp.blocks), dim3(TILE_T), 0, stream, data, ls, n_lines, open_tail, (u64 *)lp.code.p, (int *)lp.start.p,
+                           (int *)lp.end.p, (unsigned int *)lp.nlen.p, (u64 *)lp.bsum.p, lp.flag());
+        NATAC_DEV_TRY(lp.counts(n_lines, 0, stream));
+        parsed();
+        const u64 n_data = lp.n_data, n_runs = lp.n_runs;
+        if (!n_data) return std::string();
+        NATAC_DEV_TRY(d_ostart.reserve((size_t)n_data * sizeof(int)));
+        NATAC_DEV_TRY(d_oend.reserve((size_t)n_data * sizeof(int)));
+        NATAC_DEV_TRY(runs.zero(n_runs, stream));
+        hipLaunchKernelGGL(frag_compact, dim3((unsigned)lp.blocks), dim3(TILE_T), 0, stream, ls, n_lines, (const u64 *)lp.code.p, (const int *)lp.start.p,
+                           (const int *)lp.end.p, (const unsigned int *)lp.nlen.p, (const u64 *)lp.bsum.p, n_data, (unsigned int)n_runs, (int *)d_ostart.p,
+                           (int *)d_oend.p, (u64 *)runs.d_first.p, (u64 *)runs.d_name.p, (unsigned int *)runs.d_nlen.p, (int *)runs.d_max.p);
+        runs.gather(data, n, n_runs, stream);
+        h_start.resize(n_data); h_end.resize(n_data);
+        NATAC_DEV_TRY(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(runs.download(n_runs, stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
+        for (size_t r = 0; r < (size_t)n_runs; ++r) {
+            u64 a, b;
+            if (!runs.span(r, n_data, &a, &b)) return "run table out of range";
+            pos.resize((size_t)(b - a));
+            tlen.resize((size_t)(b - a));
+            for (u64 i = a; i < b; ++i) {
+                pos[(size_t)(i - a)] = (int64_t)h_start[(size_t)i] - 4;
+                tlen[(size_t)(i - a)] = (int64_t)h_end[(size_t)i] - (int64_t)h_start[(size_t)i] + 8;
+            }
+            natac_fragio::append_run(bd, runs.name(r), pos.data(), tlen.data(), (size_t)(b - a), runs.rmax[r]);
+        }
+        return std::string();
+    }
+    std::string finish(hipStream_t) { return std::string(); }
+};
+
+// ---- the split: the table goes up once, (b') to (d') per window, the segments into the builder both paths share, the per-barcode counts
+// (table->group.size() of them) at the end ----
+struct SplitJob : FragJob {
+    const natac_fragio::SplitTableHost *table = nullptr;
+    natac_fragio::SplitBuilder *sb = nullptr;
     std::vector<int64_t> bc_count;
-};
-
-// Returns the same object as natac_fragio::decode, or nullptr: the host decoder answers (`why` says what stopped the device path).
-// With `split` the returned object is empty (a token of success): the groups are in split->sb, the counts in split->bc_count.
-// With `cells` likewise: the table is in cells->out.
-inline natac_bamio::Bam *decode_device(const char *path, hipStream_t stream, std::string &why, size_t window_bytes = (size_t)1 << 30,
-                                       SplitJob *split = nullptr, CellsJob *cells = nullptr) {
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) { why = std::string("cannot open ") + path; return nullptr; }
-    struct stat sb;
-    if (fstat(fd, &sb) != 0) { close(fd); why = "cannot size the file"; return nullptr; }
-    const u64 fsize = (u64)sb.st_size;
-    window_bytes = std::max<size_t>(window_bytes, (size_t)4096);
-    const size_t STAGE = (size_t)std::min<u64>((u64)32 << 20, std::max<u64>(fsize, 4096));      // two small pinned buffers: natac_bam_dev.hpp says why
-    unsigned char *stage[2] = {nullptr, nullptr};
-    hipEvent_t staged[2] = {nullptr, nullptr};
-    natac_bamio::Bam *bam = new natac_bamio::Bam();
-    natac_fragio::Builder bd(bam);
-    DevBuf d_raw, d_mem, d_data[2], d_status, d_queue, d_crc, d_tile, d_ls, d_code, d_start, d_end, d_nlen, d_bsum, d_total, d_ostart, d_oend, d_rfirst,
-        d_rname, d_rnlen, d_rmax, d_names, d_tb_bytes, d_tb_off, d_tb_group, d_tb_slot, d_bcc, d_grp, d_lrun, d_thist, d_seg;
+    LineParse lp;
+    RunTable runs;
+    DevBuf d_tb_bytes, d_tb_off, d_tb_group, d_tb_slot, d_bcc, d_grp, d_lrun, d_thist, d_seg, d_assigned, d_ostart, d_oend;
     natac_fragio::SplitTable dev_tb{};
     int bc_bits = 1, G = 0;
+    u64 n_assigned = 0;
     std::vector<unsigned int> h_seg;
-    std::vector<int> run_chrom;
-    hipStream_t aux[3] = {nullptr, nullptr, nullptr};
-    std::vector<Member> mem;
-    std::vector<int> h_start, h_end, h_rmax;
-    std::vector<u64> h_rfirst;
-    std::vector<unsigned int> h_rnlen;
-    std::vector<unsigned char> h_names;
-    std::vector<int64_t> pos, tlen;
-    int cur_buf = 0;
-    Chain chain;
-    std::thread walker(natac_bamdev::walk_chain, fd, fsize, &chain);
-    auto cleanup = [&]() {
-        if (walker.joinable()) walker.join();
-        for (int i = 0; i < 3; ++i) if (aux[i]) { (void)hipStreamSynchronize(aux[i]); (void)hipStreamDestroy(aux[i]); }
-        (void)hipStreamSynchronize(stream);
-        for (int i = 0; i < 2; ++i) { if (stage[i]) (void)hipHostFree(stage[i]); if (staged[i]) (void)hipEventDestroy(staged[i]); }
-        close(fd);
-    };
-    auto give_up = [&](const std::string &msg) -> natac_bamio::Bam * { why = msg; delete bam; cleanup(); return nullptr; };
-#define FRAGDEV_HIP(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { (void)hipGetLastError(); return give_up(std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    for (int i = 0; i < 2; ++i) {
-        FRAGDEV_HIP(hipHostMalloc((void **)&stage[i], STAGE, hipHostMallocDefault));
-        FRAGDEV_HIP(hipEventCreateWithFlags(&staged[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
-    FRAGDEV_HIP(d_status.reserve(4 * sizeof(int)));
-    FRAGDEV_HIP(d_total.reserve(4 * sizeof(u64)));
-    if (cells) { const std::string stop = cells->start(stream); if (!stop.empty()) return give_up(stop); }
-    if (split) {                                         // the table goes up once
-        const natac_fragio::SplitTableHost &t = *split->table;
+    std::vector<int> run_chrom, h_start, h_end;
+    std::string start(hipStream_t stream) {
+        const natac_fragio::SplitTableHost &t = *table;
         G = t.n_groups;
         while (bc_bits < 32 && ((size_t)1 << bc_bits) < t.group.size()) ++bc_bits;
-        FRAGDEV_HIP(d_tb_bytes.reserve(t.bytes.size()));
-        FRAGDEV_HIP(d_tb_off.reserve(t.off.size() * sizeof(uint32_t)));
-        FRAGDEV_HIP(d_tb_group.reserve(t.group.size() * sizeof(int32_t)));
-        FRAGDEV_HIP(d_tb_slot.reserve(t.slot.size() * sizeof(uint32_t)));
-        FRAGDEV_HIP(d_bcc.reserve(t.group.size() * sizeof(u64)));
-        FRAGDEV_HIP(hipMemcpyAsync(d_tb_bytes.p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipMemcpyAsync(d_tb_off.p, t.off.data(), t.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipMemcpyAsync(d_tb_group.p, t.group.data(), t.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipMemcpyAsync(d_tb_slot.p, t.slot.data(), t.slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipMemsetAsync(d_bcc.p, 0, t.group.size() * sizeof(u64), stream));
-        FRAGDEV_HIP(hipStreamSynchronize(stream));
+        NATAC_DEV_TRY(d_assigned.reserve(sizeof(u64)));
+        NATAC_DEV_TRY(d_tb_bytes.reserve(t.bytes.size()));
+        NATAC_DEV_TRY(d_tb_off.reserve(t.off.size() * sizeof(uint32_t)));
+        NATAC_DEV_TRY(d_tb_group.reserve(t.group.size() * sizeof(int32_t)));
+        NATAC_DEV_TRY(d_tb_slot.reserve(t.slot.size() * sizeof(uint32_t)));
+        NATAC_DEV_TRY(d_bcc.reserve(t.group.size() * sizeof(u64)));
+        NATAC_DEV_TRY(hipMemcpyAsync(d_tb_bytes.p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(d_tb_off.p, t.off.data(), t.off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(d_tb_group.p, t.group.data(), t.group.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        NATAC_DEV_TRY(hipMemcpyAsync(d_tb_slot.p, t.slot.data(), t.slot.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        NATAC_DEV_TRY(hipMemsetAsync(d_bcc.p, 0, t.group.size() * sizeof(u64), stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
         dev_tb = natac_fragio::SplitTable{(const unsigned char *)d_tb_bytes.p, (const uint32_t *)d_tb_off.p, (const int32_t *)d_tb_group.p,
                                           (const uint32_t *)d_tb_slot.p, (uint32_t)t.group.size(), (uint32_t)t.slot.size(), t.hash_mask};
+        return lp.begin(stream);
     }
-    {
-        std::vector<unsigned int> t8(8 * 256);
-        natac_bamdev::crc32_slice8_tables(t8.data());
-        FRAGDEV_HIP(d_crc.reserve(t8.size() * sizeof(unsigned int)));
-        FRAGDEV_HIP(hipMemcpyAsync(d_crc.p, t8.data(), t8.size() * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipStreamSynchronize(stream));      // t8 is a local
-    }
-    int n_cu = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    }
-    const bool timing = getenv("NATAC_FRAG_DEV_TIMING") != nullptr;
-    double t_read = 0, t_scan = 0, t_inflate = 0, t_lines = 0, t_parse = 0, t_out = 0;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now();
-    auto lap = [&](double &acc) { const double t = now(); acc += t - t0; t0 = t; };
-    u64 pend = 0;          // carried bytes at the front of d_data[cur_buf]
-    u64 win_start = 0;     // file offset of the window = start of its first member
-    size_t m0 = 0;         // its first member in the chain
-    for (;;) {
-        // ---- the members of this window: as many as fit window_bytes (at least one), once the chain walk has got that far
-        size_t m1 = m0;
-        u64 win_end = win_start;
-        {
-            std::unique_lock<std::mutex> lk(chain.mu);
-            chain.cv.wait(lk, [&]() { return chain.done || (!chain.ends.empty() && chain.ends.back() >= win_start + window_bytes); });
-            if (!chain.error.empty()) { const std::string e = chain.error; lk.unlock(); return give_up(e); }
-            while (m1 < chain.ends.size() && (m1 == m0 || chain.ends[m1] <= win_start + window_bytes)) ++m1;
-            mem.assign(chain.members.begin() + (long)m0, chain.members.begin() + (long)m1);
-            if (m1 > m0) win_end = chain.ends[m1 - 1];
+    std::string window(const unsigned char *data, u64 n, const u64 *ls, u64 n_lines, int open_tail, hipStream_t stream) {
+        NATAC_DEV_TRY(lp.reserve(n_lines));
+        NATAC_DEV_TRY(d_grp.reserve((size_t)n_lines * sizeof(int)));
+        hipLaunchKernelGGL(frag_split_parse, dim3((unsigned)lp.blocks), dim3(TILE_T), 0, stream, data, ls, n_lines, open_tail, dev_tb, bc_bits, (u64 *)lp.code.p,
+                           (int *)lp.start.p, (int *)lp.end.p, (unsigned int *)lp.nlen.p, (int *)d_grp.p, (u64 *)d_bcc.p, (u64 *)lp.bsum.p, lp.flag());
+        NATAC_DEV_TRY(lp.counts(n_lines, G, stream));
+        parsed();
+        const u64 n_data = lp.n_data, n_runs = lp.n_runs;
+        if (!n_data) return std::string();
+        NATAC_DEV_TRY(d_lrun.reserve((size_t)n_lines * sizeof(int)));
+        const u64 n_tiles = (n_lines + PART_LINES - 1) / PART_LINES, n_seg = n_runs * (u64)G;
+        NATAC_DEV_TRY(d_thist.reserve((size_t)(n_tiles * (u64)G) * sizeof(u64)));
+        NATAC_DEV_TRY(d_seg.reserve((size_t)n_seg * sizeof(unsigned int)));
+        NATAC_DEV_TRY(runs.zero(n_runs, stream));
+        NATAC_DEV_TRY(hipMemsetAsync(d_seg.p, 0, (size_t)n_seg * sizeof(unsigned int), stream));
+        hipLaunchKernelGGL(frag_split_compact, dim3((unsigned)lp.blocks), dim3(TILE_T), 0, stream, ls, n_lines, (const u64 *)lp.code.p, (const int *)lp.end.p,
+                           (const unsigned int *)lp.nlen.p, (const u64 *)lp.bsum.p, n_data, (unsigned int)n_runs, (u64 *)runs.d_first.p, (u64 *)runs.d_name.p,
+                           (unsigned int *)runs.d_nlen.p, (int *)runs.d_max.p, (int *)d_lrun.p);
+        runs.gather(data, n, n_runs, stream);
+        hipLaunchKernelGGL(frag_split_hist, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p, n_lines, G,
+                           (unsigned int)n_runs, n_tiles, (u64 *)d_thist.p, (unsigned int *)d_seg.p);
+        hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_thist.p, n_tiles * (u64)G, (u64 *)d_assigned.p);
+        NATAC_DEV_TRY(hipMemcpyAsync(&n_assigned, d_assigned.p, sizeof n_assigned, hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(runs.download(n_runs, stream));
+        h_seg.resize((size_t)n_seg);
+        NATAC_DEV_TRY(hipMemcpyAsync(h_seg.data(), d_seg.p, (size_t)n_seg * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
+        NATAC_DEV_TRY(hipStreamSynchronize(stream));
+        if (n_assigned > n_data) return "counts out of range";
+        if (n_assigned) {                    // unassigned lines stay on the device
+            NATAC_DEV_TRY(d_ostart.reserve((size_t)n_assigned * sizeof(int)));
+            NATAC_DEV_TRY(d_oend.reserve((size_t)n_assigned * sizeof(int)));
+            hipLaunchKernelGGL(frag_split_scatter, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p,
+                               (const int *)lp.start.p, (const int *)lp.end.p, n_lines, G, (unsigned int)n_runs, n_tiles, (const u64 *)d_thist.p, n_assigned,
+                               (int *)d_ostart.p, (int *)d_oend.p);
+            h_start.resize(n_assigned); h_end.resize(n_assigned);
+            NATAC_DEV_TRY(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+            NATAC_DEV_TRY(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
+            NATAC_DEV_TRY(hipStreamSynchronize(stream));
         }
-        if (mem.empty()) break;                                         // the whole chain is done
-        u64 n = pend;
-        for (auto &mb : mem) { mb.coff -= win_start; mb.uoff = n; n += mb.isize; }
-        const int M = (int)mem.size();
-        const size_t o = (size_t)(win_end - win_start);
-        lap(t_scan);
-        // ---- upload (the read of one staging buffer next to the copy of the other) + inflate of the members that have arrived
-        FRAGDEV_HIP(d_raw.reserve(o + 64));
-        FRAGDEV_HIP(d_mem.reserve(mem.size() * sizeof(Member)));
-        FRAGDEV_HIP(d_data[cur_buf].reserve((size_t)n + 64, (size_t)pend, stream));      // the carry at the front stays
-        unsigned char *data = (unsigned char *)d_data[cur_buf].p;
-        const size_t SUBWIN = (size_t)256 << 20;
-        const int max_launches = (int)(o / SUBWIN) + 2;
-        FRAGDEV_HIP(d_queue.reserve((size_t)max_launches * sizeof(int)));
-        FRAGDEV_HIP(hipMemcpyAsync(d_mem.p, mem.data(), mem.size() * sizeof(Member), hipMemcpyHostToDevice, stream));
-        FRAGDEV_HIP(hipMemsetAsync(d_status.p, 0, 4 * sizeof(int), stream));
-        FRAGDEV_HIP(hipMemsetAsync(d_queue.p, 0, (size_t)max_launches * sizeof(int), stream));
-        {
-            int which = 0, launched = 0, n_launch = 0;
-            size_t since = 0;
-            for (size_t at = 0; at < o; which ^= 1) {
-                const size_t len = std::min(STAGE, o - at);
-                FRAGDEV_HIP(hipEventSynchronize(staged[which]));         // the copy that used this buffer last has finished
-                {   // four concurrent preads fill the staging buffer, as for a BAM
-                    const int RT = len >= ((size_t)4 << 20) ? 4 : 1;
-                    bool bad[4] = {false, false, false, false};
-                    auto fill = [&](int t) {
-                        size_t a = len * (size_t)t / (size_t)RT;
-                        const size_t b = len * ((size_t)t + 1) / (size_t)RT;
-                        while (a < b) {
-                            const ssize_t r = pread(fd, stage[which] + a, b - a, (off_t)(win_start + at + a));
-                            if (r <= 0) { bad[t] = true; return; }
-                            a += (size_t)r;
-                        }
-                    };
-                    std::thread th[3];
-                    for (int t = 1; t < RT; ++t) th[t - 1] = std::thread(fill, t);
-                    fill(0);
-                    for (int t = 1; t < RT; ++t) th[t - 1].join();
-                    if (bad[0] || bad[1] || bad[2] || bad[3]) return give_up("read error");
-                }
-                FRAGDEV_HIP(hipMemcpyAsync((unsigned char *)d_raw.p + at, stage[which], len, hipMemcpyHostToDevice, stream));
-                FRAGDEV_HIP(hipEventRecord(staged[which], stream));
-                at += len;
-                since += len;
-                if (since >= SUBWIN || at == o) {
-                    int upto = launched;                                // members that lie completely inside the uploaded bytes
-                    while (upto < M && mem[(size_t)upto].coff + mem[(size_t)upto].csize + 8 <= at) ++upto;
-                    if (at == o) upto = M;
-                    if (upto > launched) {
-                        hipStream_t side = aux[n_launch % 3];
-                        FRAGDEV_HIP(hipStreamWaitEvent(side, staged[which], 0));
-                        const int cnt = upto - launched;
-                        hipLaunchKernelGGL(natac_bamdev::bamdev_inflate, dim3((unsigned)std::min<long long>((cnt + 63) / 64, 3ll * n_cu)), dim3(64), 0, side,
-                                           (const unsigned char *)d_raw.p, (const Member *)d_mem.p, launched, upto, data, (int *)d_status.p,
-                                           (int *)d_queue.p + n_launch, (const unsigned int *)d_crc.p);
-                        launched = upto;
-                        ++n_launch;
-                        since = 0;
-                    }
-                }
+        run_chrom.resize(n_runs);
+        for (size_t r = 0; r < (size_t)n_runs; ++r) {
+            u64 a, b;
+            if (!runs.span(r, n_data, &a, &b)) return "run table out of range";
+            run_chrom[r] = sb->chrom(runs.name(r), runs.rmax[r], (int64_t)(b - a));
+        }
+        u64 at = 0;                          // the segments, group-major as the partition wrote them
+        for (int g = 0; g < G; ++g)
+            for (size_t r = 0; r < (size_t)n_runs; ++r) {
+                const u64 cnt = h_seg[(size_t)g * (size_t)n_runs + r];
+                if (cnt > n_assigned - at) return "segment table out of range";
+                for (u64 k = at; k < at + cnt; ++k) sb->append(g, run_chrom[r], h_start[(size_t)k], h_end[(size_t)k]);
+                at += cnt;
             }
-        }
-        lap(t_read);
-        for (int i = 0; i < 3; ++i) FRAGDEV_HIP(hipStreamSynchronize(aux[i]));
-        int st[2] = {0, 0};
-        FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
-        FRAGDEV_HIP(hipStreamSynchronize(stream));
-        if (st[0] != 0) return give_up("a BGZF member does not inflate or fails its CRC-32");
-        const bool eof = win_end == fsize;
-        win_start = win_end;
-        m0 = m1;
-        lap(t_inflate);
+        if (at != n_assigned) return "segment table out of range";
+        return std::string();
+    }
+    std::string finish(hipStream_t) {
+        std::vector<u64> h_bcc(table->group.size());
+        bc_count.resize(h_bcc.size());
+        NATAC_DEV_TRY(hipMemcpy(h_bcc.data(), d_bcc.p, h_bcc.size() * sizeof(u64), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < h_bcc.size(); ++k) bc_count[k] = (int64_t)h_bcc[k];
+        return std::string();
+    }
+};
+
+// ---- the driver: per window (a), then the job, then the carry of the bytes behind the last '\n' ----
+// "" or why the host path answers instead (natac_api.hip runs it).  A job's window() synchronises the stream before it returns.
+template <class Job>
+inline std::string decode_device(const char *path, hipStream_t stream, size_t window_bytes, Job &job) {
+    DevBuf d_tile, d_ls, d_total;
+    DevWindows win;                        // (declared last: it waits for the device before any buffer above is freed)
+    NATAC_DEV_TRY(win.open(path, stream, window_bytes, (size_t)256 << 20));
+    NATAC_DEV_TRY(d_total.reserve(sizeof(u64)));
+    NATAC_DEV_TRY(job.start(stream));
+    job.laps = &win.laps;
+    double t_lines = 0, t_out = 0;
+    const DevWindows::Window &w = win.w;
+    for (;;) {
+        NATAC_DEV_TRY(win.next());
+        if (w.M == 0) break;                // the whole chain is done
+        const unsigned char *data = w.data;
+        const u64 n = w.n;
         u64 cur = 0;                        // the carry into the next window starts here
         if (n > 0) {
-            // ---- (a) line index
             const u64 tiles = (n + TILE_B - 1) / TILE_B;
-            FRAGDEV_HIP(d_tile.reserve((size_t)tiles * sizeof(u64)));
-            hipLaunchKernelGGL(frag_count_nl, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, (const unsigned char *)data, n, (u64 *)d_tile.p);
+            NATAC_DEV_TRY(d_tile.reserve((size_t)tiles * sizeof(u64)));
+            hipLaunchKernelGGL(frag_count_nl, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, data, n, (u64 *)d_tile.p);
             hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_tile.p, tiles, (u64 *)d_total.p);
             u64 n_nl = 0;
             unsigned char last_byte = 0;
-            FRAGDEV_HIP(hipMemcpyAsync(&n_nl, d_total.p, sizeof n_nl, hipMemcpyDeviceToHost, stream));
-            FRAGDEV_HIP(hipMemcpyAsync(&last_byte, data + n - 1, 1, hipMemcpyDeviceToHost, stream));
-            FRAGDEV_HIP(hipStreamSynchronize(stream));
-            if (n_nl > n) return give_up("line count out of range");
-            const int open_tail = eof && last_byte != '\n' ? 1 : 0;        // a last line without '\n' is a line
+            NATAC_DEV_TRY(hipMemcpyAsync(&n_nl, d_total.p, sizeof n_nl, hipMemcpyDeviceToHost, stream));
+            NATAC_DEV_TRY(hipMemcpyAsync(&last_byte, data + n - 1, 1, hipMemcpyDeviceToHost, stream));
+            NATAC_DEV_TRY(hipStreamSynchronize(stream));
+            if (n_nl > n) return "line count out of range";
+            const int open_tail = w.eof && last_byte != '\n' ? 1 : 0;      // a last line without '\n' is a line
             const u64 n_lines = n_nl + (u64)open_tail;
-            if (n_lines == 0) return give_up("a window without a line end (a line longer than a window)");
-            {
-                FRAGDEV_HIP(d_ls.reserve((size_t)(n_lines + 2) * sizeof(u64)));
-                u64 *ls = (u64 *)d_ls.p;
-                const u64 zero = 0, behind = n + 1;
-                FRAGDEV_HIP(hipMemcpyAsync(ls, &zero, sizeof zero, hipMemcpyHostToDevice, stream));
-                hipLaunchKernelGGL(frag_line_starts, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, (const unsigned char *)data, n, (const u64 *)d_tile.p, n_nl, ls);
-                if (open_tail) FRAGDEV_HIP(hipMemcpyAsync(ls + n_lines, &behind, sizeof behind, hipMemcpyHostToDevice, stream));
-                FRAGDEV_HIP(hipMemcpyAsync(&cur, ls + n_nl, sizeof cur, hipMemcpyDeviceToHost, stream));
-                lap(t_lines);
-                if (cells) {                             // ---- discovery: the table grows by this window's lines (CellsJob)
-                    FRAGDEV_HIP(hipStreamSynchronize(stream));
-                    if (cur > n) return give_up("counts out of range");
-                    const std::string stop = cells->window((const unsigned char *)data, n, (const u64 *)ls, n_lines, open_tail, stream);
-                    if (!stop.empty()) return give_up(stop);
-                    if (open_tail) cur = n;
-                    lap(t_parse);
-                } else {
-                    // ---- (b) parse
-                    const u64 blocks = (n_lines + TILE_T - 1) / TILE_T;
-                    FRAGDEV_HIP(d_code.reserve((size_t)n_lines * sizeof(u64)));
-                    FRAGDEV_HIP(d_start.reserve((size_t)n_lines * sizeof(int)));
-                    FRAGDEV_HIP(d_end.reserve((size_t)n_lines * sizeof(int)));
-                    FRAGDEV_HIP(d_nlen.reserve((size_t)n_lines * sizeof(unsigned int)));
-                    FRAGDEV_HIP(d_bsum.reserve((size_t)blocks * sizeof(u64)));
-                    if (split) {
-                        FRAGDEV_HIP(d_grp.reserve((size_t)n_lines * sizeof(int)));
-                        hipLaunchKernelGGL(frag_split_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
-                                           open_tail, dev_tb, bc_bits, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (int *)d_grp.p,
-                                           (u64 *)d_bcc.p, (u64 *)d_bsum.p, (int *)d_status.p);
-                    } else
-                        hipLaunchKernelGGL(frag_parse, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const unsigned char *)data, (const u64 *)ls, n_lines,
-                                           open_tail, (u64 *)d_code.p, (int *)d_start.p, (int *)d_end.p, (unsigned int *)d_nlen.p, (u64 *)d_bsum.p,
-                                           (int *)d_status.p);
-                    hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_bsum.p, blocks, (u64 *)d_total.p + 1);
-                    u64 packed = 0;
-                    FRAGDEV_HIP(hipMemcpyAsync(&packed, (u64 *)d_total.p + 1, sizeof packed, hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipMemcpyAsync(st, d_status.p, sizeof st, hipMemcpyDeviceToHost, stream));
-                    FRAGDEV_HIP(hipStreamSynchronize(stream));
-                    if (st[0] != 0) return give_up("a malformed line");
-                    const u64 n_data = packed >> 32, n_runs = packed & 0xffffffffull;
-                    if (n_data > n_lines || n_runs > n_data || cur > n) return give_up("counts out of range");
-                    if (n_runs > MAX_RUNS) return give_up("more than 65,536 chromosome runs in a window");
-                    if (split && n_runs * (u64)G > SPLIT_MAX_SEGMENTS) return give_up("more than 1,048,576 groups x chromosome runs in a window");
-                    if (open_tail) cur = n;
-                    lap(t_parse);
-                    // ---- (c) compaction, the run names, and the append on the host
-                    if (n_data && split) {
-                        FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
-                        FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
-                        FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
-                        FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
-                        FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
-                        FRAGDEV_HIP(d_lrun.reserve((size_t)n_lines * sizeof(int)));
-                        const u64 n_tiles = (n_lines + PART_LINES - 1) / PART_LINES, n_seg = n_runs * (u64)G;
-                        FRAGDEV_HIP(d_thist.reserve((size_t)(n_tiles * (u64)G) * sizeof(u64)));
-                        FRAGDEV_HIP(d_seg.reserve((size_t)n_seg * sizeof(unsigned int)));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_seg.p, 0, (size_t)n_seg * sizeof(unsigned int), stream));
-                        hipLaunchKernelGGL(frag_split_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
-                                           (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data, (unsigned int)n_runs,
-                                           (u64 *)d_rfirst.p, (u64 *)d_rname.p, (unsigned int *)d_rnlen.p, (int *)d_rmax.p, (int *)d_lrun.p);
-                        hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
-                                           (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
-                        hipLaunchKernelGGL(frag_split_hist, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p, n_lines, G,
-                                           (unsigned int)n_runs, n_tiles, (u64 *)d_thist.p, (unsigned int *)d_seg.p);
-                        hipLaunchKernelGGL(frag_scan, dim3(1), dim3(1024), 0, stream, (u64 *)d_thist.p, n_tiles * (u64)G, (u64 *)d_total.p + 2);
-                        u64 n_assigned = 0;
-                        FRAGDEV_HIP(hipMemcpyAsync(&n_assigned, (u64 *)d_total.p + 2, sizeof n_assigned, hipMemcpyDeviceToHost, stream));
-                        h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256); h_seg.resize((size_t)n_seg);
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_seg.data(), d_seg.p, (size_t)n_seg * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipStreamSynchronize(stream));
-                        if (n_assigned > n_data) return give_up("counts out of range");
-                        if (n_assigned) {                    // unassigned lines stay on the device
-                            FRAGDEV_HIP(d_ostart.reserve((size_t)n_assigned * sizeof(int)));
-                            FRAGDEV_HIP(d_oend.reserve((size_t)n_assigned * sizeof(int)));
-                            hipLaunchKernelGGL(frag_split_scatter, dim3((unsigned)n_tiles), dim3(PART_T), 0, stream, (const int *)d_grp.p, (const int *)d_lrun.p,
-                                               (const int *)d_start.p, (const int *)d_end.p, n_lines, G, (unsigned int)n_runs, n_tiles, (const u64 *)d_thist.p,
-                                               n_assigned, (int *)d_ostart.p, (int *)d_oend.p);
-                            h_start.resize(n_assigned); h_end.resize(n_assigned);
-                            FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
-                            FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_assigned * sizeof(int), hipMemcpyDeviceToHost, stream));
-                            FRAGDEV_HIP(hipStreamSynchronize(stream));
-                        }
-                        run_chrom.resize(n_runs);
-                        for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                            const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
-                            if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
-                            run_chrom[r] = split->sb->chrom(std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), h_rmax[r], (int64_t)(b - a));
-                        }
-                        u64 at = 0;                          // the segments, group-major as the partition wrote them
-                        for (int g = 0; g < G; ++g)
-                            for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                                const u64 cnt = h_seg[(size_t)g * (size_t)n_runs + r];
-                                if (cnt > n_assigned - at) return give_up("segment table out of range");
-                                for (u64 k = at; k < at + cnt; ++k) split->sb->append(g, run_chrom[r], h_start[(size_t)k], h_end[(size_t)k]);
-                                at += cnt;
-                            }
-                        if (at != n_assigned) return give_up("segment table out of range");
-                    } else if (n_data) {
-                        FRAGDEV_HIP(d_ostart.reserve((size_t)n_data * sizeof(int)));
-                        FRAGDEV_HIP(d_oend.reserve((size_t)n_data * sizeof(int)));
-                        FRAGDEV_HIP(d_rfirst.reserve((size_t)n_runs * sizeof(u64)));
-                        FRAGDEV_HIP(d_rname.reserve((size_t)n_runs * sizeof(u64)));
-                        FRAGDEV_HIP(d_rnlen.reserve((size_t)n_runs * sizeof(unsigned int)));
-                        FRAGDEV_HIP(d_rmax.reserve((size_t)n_runs * sizeof(int)));
-                        FRAGDEV_HIP(d_names.reserve((size_t)n_runs * 256));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rmax.p, 0, (size_t)n_runs * sizeof(int), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rfirst.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rnlen.p, 0, (size_t)n_runs * sizeof(unsigned int), stream));
-                        FRAGDEV_HIP(hipMemsetAsync(d_rname.p, 0, (size_t)n_runs * sizeof(u64), stream));
-                        hipLaunchKernelGGL(frag_compact, dim3((unsigned)blocks), dim3(TILE_T), 0, stream, (const u64 *)ls, n_lines, (const u64 *)d_code.p,
-                                           (const int *)d_start.p, (const int *)d_end.p, (const unsigned int *)d_nlen.p, (const u64 *)d_bsum.p, n_data,
-                                           (unsigned int)n_runs, (int *)d_ostart.p, (int *)d_oend.p, (u64 *)d_rfirst.p, (u64 *)d_rname.p,
-                                           (unsigned int *)d_rnlen.p, (int *)d_rmax.p);
-                        hipLaunchKernelGGL(frag_gather_names, dim3((unsigned)((n_runs + 63) / 64)), dim3(64), 0, stream, (const unsigned char *)data, n,
-                                           (const u64 *)d_rname.p, (const unsigned int *)d_rnlen.p, (unsigned int)n_runs, (unsigned char *)d_names.p);
-                        h_start.resize(n_data); h_end.resize(n_data);
-                        h_rfirst.resize(n_runs); h_rnlen.resize(n_runs); h_rmax.resize(n_runs); h_names.resize((size_t)n_runs * 256);
-                        FRAGDEV_HIP(hipMemcpyAsync(h_start.data(), d_ostart.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_end.data(), d_oend.p, (size_t)n_data * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rfirst.data(), d_rfirst.p, (size_t)n_runs * sizeof(u64), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rnlen.data(), d_rnlen.p, (size_t)n_runs * sizeof(unsigned int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_rmax.data(), d_rmax.p, (size_t)n_runs * sizeof(int), hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipMemcpyAsync(h_names.data(), d_names.p, (size_t)n_runs * 256, hipMemcpyDeviceToHost, stream));
-                        FRAGDEV_HIP(hipStreamSynchronize(stream));
-                        for (size_t r = 0; r < (size_t)n_runs; ++r) {
-                            const u64 a = h_rfirst[r], b = r + 1 < (size_t)n_runs ? h_rfirst[r + 1] : n_data;
-                            if (a >= b || b > n_data || h_rnlen[r] == 0 || h_rnlen[r] > 255) return give_up("run table out of range");
-                            pos.resize((size_t)(b - a));
-                            tlen.resize((size_t)(b - a));
-                            for (u64 i = a; i < b; ++i) {
-                                pos[(size_t)(i - a)] = (int64_t)h_start[(size_t)i] - 4;
-                                tlen[(size_t)(i - a)] = (int64_t)h_end[(size_t)i] - (int64_t)h_start[(size_t)i] + 8;
-                            }
-                            natac_fragio::append_run(bd, std::string((const char *)h_names.data() + r * 256, h_rnlen[r]), pos.data(), tlen.data(), (size_t)(b - a),
-                                                     h_rmax[r]);
-                        }
-                    }
-                }
-            }
+            if (n_lines == 0) return "a window without a line end (a line longer than a window)";
+            NATAC_DEV_TRY(d_ls.reserve((size_t)(n_lines + 2) * sizeof(u64)));
+            u64 *ls = (u64 *)d_ls.p;
+            const u64 zero = 0, behind = n + 1;
+            NATAC_DEV_TRY(hipMemcpyAsync(ls, &zero, sizeof zero, hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(frag_line_starts, dim3((unsigned)tiles), dim3(TILE_T), 0, stream, data, n, (const u64 *)d_tile.p, n_nl, ls);
+            if (open_tail) NATAC_DEV_TRY(hipMemcpyAsync(ls + n_lines, &behind, sizeof behind, hipMemcpyHostToDevice, stream));
+            NATAC_DEV_TRY(hipMemcpyAsync(&cur, ls + n_nl, sizeof cur, hipMemcpyDeviceToHost, stream));      // (arrives with the job's first synchronise)
+            win.laps.lap(t_lines);
+            NATAC_DEV_TRY(job.window(data, n, (const u64 *)ls, n_lines, open_tail, stream));
+            if (cur > n) return "counts out of range";
+            if (open_tail) cur = n;
         }
-        // ---- carry the bytes behind the last '\n' to the front of the other buffer
-        pend = n - cur;
-        FRAGDEV_HIP(d_data[cur_buf ^ 1].reserve((size_t)pend + 64));
-        if (pend) FRAGDEV_HIP(hipMemcpyAsync(d_data[cur_buf ^ 1].p, data + cur, (size_t)pend, hipMemcpyDeviceToDevice, stream));
-        FRAGDEV_HIP(hipStreamSynchronize(stream));
-        cur_buf ^= 1;
-        lap(t_out);
-        if (eof) break;
+        NATAC_DEV_TRY(win.carry(cur));
+        win.laps.lap(t_out);
+        if (w.eof) break;
     }
-    if (timing)
+    if (getenv("NATAC_FRAG_DEV_TIMING"))
         std::fprintf(stderr, "[natac_frag_dev] read + upload %.3f s, waiting for the member chain %.3f, inflate %.3f, line index %.3f, parse %.3f, compaction + append + carry %.3f\n",
-                     t_read, t_scan, t_inflate, t_lines, t_parse, t_out);
-#undef FRAGDEV_HIP
-    if (pend != 0) return give_up("bytes left behind the last window");
-    if (cells) { const std::string stop = cells->finish(stream); if (!stop.empty()) return give_up(stop); }
-    if (split) {
-        std::vector<u64> h_bcc(split->table->group.size());
-        split->bc_count.resize(h_bcc.size());
-        const hipError_t e_ = hipMemcpy(h_bcc.data(), d_bcc.p, h_bcc.size() * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e_ != hipSuccess) { (void)hipGetLastError(); return give_up(std::string("hipMemcpy of the barcode counts: ") + hipGetErrorString(e_)); }
-        for (size_t k = 0; k < h_bcc.size(); ++k) split->bc_count[k] = (int64_t)h_bcc[k];
-    }
-    cleanup();
-    return bam;
+                     win.t_read, win.t_chain, win.t_inflate, t_lines, job.t_parse, t_out);
+    if (win.pend != 0) return "bytes left behind the last window";
+    return job.finish(stream);
+}
+
+// Returns the same object as natac_fragio::decode, or nullptr: the host decoder answers (`why` says what stopped the device path).
+inline natac_bamio::Bam *decode_plain(const char *path, hipStream_t stream, std::string &why, size_t window_bytes) {
+    std::unique_ptr<natac_bamio::Bam> bam(new natac_bamio::Bam());
+    PlainJob job(bam.get());
+    why = decode_device(path, stream, window_bytes, job);
+    return why.empty() ? bam.release() : nullptr;
 }
 
 }  // namespace natac_fragdev

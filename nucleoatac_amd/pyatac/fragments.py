@@ -140,7 +140,8 @@ class FragmentStore(object):
 
     @staticmethod
     def from_bam(path, n_threads=0, device=None):
-        """native decoder in libnatac_hip.so.  On a GPU box: natac_bam_open_device (csrc/natac_bam_dev.hpp) -- the file goes to the
+        """native decoder in libnatac_hip.so.  On a GPU box: natac_bam_open_device (csrc/natac_bam_dev.hpp on the
+        window stream of csrc/natac_bgzf_dev.hpp) -- the file goes to the
         device through two pinned staging buffers, every lane of the chip inflates BGZF members from a queue while the rest of
         the file is still being read, the records are walked on the device and the chain of record starts is confirmed link by
         link.  Without a GPU, or with device=False / NATAC_DEVICE_BAM=0: natac_bam_open, parallel inflate + record walk on the
@@ -213,7 +214,8 @@ class FragmentStore(object):
         - a malformed data line raises "<path>: line <N>: <reason>" (N 1-based, counting skipped lines), nothing is returned.
 
         The container goes by magic bytes: BGZF, any other gzip, plain text.  On a GPU box a BGZF file goes through
-        natac_frag_open_device (csrc/natac_fragfile_dev.hpp): the members are staged and inflated as a BAM's, then the text is split
+        natac_frag_open_device (csrc/natac_fragfile_dev.hpp, PlainJob): the members are staged and inflated by the BAM path's window
+        stream (csrc/natac_bgzf_dev.hpp), then the text is split
         into lines, parsed and compacted on the device; FragmentStore.last_frag_on_device tells whether the device answered (the host
         decoder answers inside the call for another container, a malformed line, a damaged file, a line longer than a window, more
         than 65,536 chromosome runs in a window).  Without a GPU, or with device=False / NATAC_DEVICE_BAM=0: natac_frag_open, parallel
@@ -259,7 +261,8 @@ class FragmentStore(object):
           data lines), so groups are comparable; a chromosome on which a group has nothing is present and empty;
         - a group's records are its lines in file order within each chromosome (then sorted stably by the FragmentStore, like any).
 
-        On a GPU box a BGZF file goes through natac_frag_split_device (csrc/natac_fragfile_dev.hpp): the barcode of every data line is
+        On a GPU box a BGZF file goes through natac_frag_split_device (csrc/natac_fragfile_dev.hpp, SplitJob): the barcode of every data
+        line is
         hashed, looked up and counted on the device and each window's assigned lines are partitioned by group there;
         FragmentStore.last_frag_on_device tells whether the device answered (the host path answers inside the call for everything
         from_fragments hands over, a line without a barcode field, a table of more than 4,194,304 barcodes and more than 1,048,576
@@ -466,7 +469,8 @@ class FragmentStore(object):
         - the result is a function of the file's bytes and the two bounds only: not of n_threads, the windows, the BGZF member size, the
           container, or which path answered.
 
-        With device=True a BGZF file goes through natac_frag_cells_device (csrc/natac_fragfile_dev.hpp): the text is inflated and split
+        With device=True a BGZF file goes through natac_frag_cells_device (csrc/natac_fragfile_dev.hpp, CellsJob): the text is inflated and
+        split
         into lines on the device, and the table is built there from the file itself -- an open-addressing table of FIXED size (8,388,608
         slots, at most half of them taken) in device memory that lives across windows; a slot is claimed by the smallest line of a window
         and only matches after the bytes compared equal.  FragmentStore.last_frag_on_device tells whether the device answered (the host

@@ -71,7 +71,7 @@ def _lines(seed, n=6000):
 
 def _windows(z, window):
     """the inflated offsets at which the device path's windows end: members are taken while they end inside win_start + window (one at
-    least), natac_fragfile_dev.hpp"""
+    least), DevWindows::next of natac_bgzf_dev.hpp"""
     ends, sizes, o = [], [], 0
     while o < len(z):
         bsize = struct.unpack_from("<H", z, o + 16)[0] + 1
