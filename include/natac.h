@@ -52,9 +52,9 @@ extern "C" {
  * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device; 11: added
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
- * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`); the binding
- * refuses another version */
-#define NATAC_ABI_VERSION 13
+ * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`);
+ * the binding refuses another version */
+#define NATAC_ABI_VERSION 14
 
 enum {
     NATAC_OK = 0,
@@ -354,6 +354,42 @@ int natac_region_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, con
 int natac_region_cell_counts(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells,
                              int64_t n_regions, const int64_t *start, const int64_t *end, int lower, int upper, int atac, int64_t *row_ptr,
                              int64_t cap, int32_t *col, int32_t *val, double *kernel_ms);
+/* ---- per-cell TSS counts, the aggregate TSS profile and per-cell fragments in peaks of one chromosome (this library's own; `pyatac
+ * cellqc`) ----
+ * pos / tlen / cell / n_cells as natac_region_cell_counts takes them.  A record is the fragment l = pos + 4, ilen = tlen - 8,
+ * r = l + ilen - 1 (the ATAC offsets of natac_region_counts).  EVERY record counts: there is no size filter.  Its two insertions are l and
+ * r; ilen == 0 gives r = l - 1, ilen == 1 gives r == l, a negative ilen gives r < l - 1, and in all these cases both insertions count on
+ * their own.
+ *   Sites: site_center[n_sites] ascending (equal centres are separate sites), site_minus[i] != 0 a minus-strand site (NULL: all plus).  For
+ *   an insertion x and a site (c, minus) let d = x - c, or c - x for a minus site.  When |d| <= flank the pair adds 1 to profile[d + flank],
+ *   1 to tss_center[cell] if |d| <= center, and 1 to tss_flank[cell] if |d| > flank - edge.
+ *   Peaks: [peak_start[j], peak_end[j]) disjoint and ascending (peak_end[j] >= peak_start[j], peak_start[j] >= peak_end[j - 1]: touching
+ *   intervals are fine).  A record is in peaks if l or r lies in some interval; it adds 1 to in_peaks[cell], once.
+ * tss_center / tss_flank / in_peaks [n_cells] and profile [2 * flank + 1] are exact int64, overwritten.  Only integer atomics are used: the
+ * result is a pure function of the inputs, and the sum over any split of the sites, of the records or of the chromosomes into calls equals
+ * the single call.  0 <= center, 1 <= edge, center + edge <= flank, 1 <= flank <= NATAC_CELLQC_MAX_FLANK.  The operands are checked on the
+ * host (NATAC_E_ARG names the offending index, the outputs stay untouched): the flank / center / edge rule, pos non-decreasing, cell in
+ * range, centres ascending, peaks disjoint.  n_sites == 0 skips the site part, n_peaks == 0 the peak part; with no records, or with neither
+ * sites nor peaks, the results are zeros, nothing is launched and kernel_ms is 0.
+ * The kernel (csrc/natac_cellqc.hpp) takes NATAC_CELLQC_BLOCK records per workgroup and step, one per thread.  The per-cell counts come
+ * from bounds searched in site_center (the three classes are symmetric in d); the profile needs the pairs and is kept per workgroup as
+ * 2 * flank + 1 32-bit counters in LDS: an insertion with at most NATAC_CELLQC_LANE_MAX sites in reach is walked by its lane, one with
+ * more by its wave.  NATAC_CELLQC_MAX_FLANK rests on the LDS of a gfx950 CU: 5,001 counters are 20,004 bytes, so eight workgroups of four
+ * waves -- the 32 waves a CU can hold -- fit its 160 KiB.  A workgroup adds at most 2 * NATAC_CELLQC_BLOCK * n_sites pairs per step, and it
+ * flushes its counters into profile (64-bit atomics) every floor((2^32 - 1) / (2 * NATAC_CELLQC_BLOCK * n_sites)) steps, before one can
+ * wrap; more than NATAC_CELLQC_SITE_CHUNK sites go through several launches, the peaks with the first.  A launch has at most
+ * NATAC_CELLQC_MAX_BLOCKS workgroups: past NATAC_CELLQC_MAX_BLOCKS * NATAC_CELLQC_BLOCK records a workgroup takes further steps with its
+ * counters carried over.  kernel_ms (may be NULL): device time of the kernels of the call; like the other outputs it is written only
+ * behind the checks. */
+#define NATAC_CELLQC_MAX_FLANK 2500
+#define NATAC_CELLQC_BLOCK 256
+#define NATAC_CELLQC_LANE_MAX 8
+#define NATAC_CELLQC_MAX_BLOCKS 2048
+#define NATAC_CELLQC_SITE_CHUNK 4194304
+int natac_cell_site_qc(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells,
+                       int64_t n_sites, const int64_t *site_center, const uint8_t *site_minus, int flank, int center, int edge,
+                       int64_t n_peaks, const int64_t *peak_start, const int64_t *peak_end, int64_t *tss_center, int64_t *tss_flank,
+                       int64_t *in_peaks, int64_t *profile, double *kernel_ms);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -396,6 +396,37 @@ class Context(object):
         out = (indptr, col[:nnz].copy(), val[:nnz].copy())
         return out + (ms.value,) if with_kernel_ms else out
 
+    def cell_site_qc(self, pos, tlen, cell, n_cells, site_center=None, site_minus=None, flank=1000, center=500, edge=100, peak_start=None,
+                     peak_end=None, with_kernel_ms=False):
+        """per-cell TSS counts, the aggregate TSS profile and per-cell fragments in peaks of one chromosome (natac_cell_site_qc):
+        (tss_center int64[n_cells], tss_flank int64[n_cells], in_peaks int64[n_cells], profile int64[2 * flank + 1]), exact.  pos (sorted) /
+        tlen / cell as region_cell_counts takes them; every record counts with its two insertions l = pos + 4 and r = pos + tlen - 5.
+        site_center must be ascending (site_minus, or None for all plus, carried along); a pair of an insertion and a site with
+        |d| <= flank adds to profile[d + flank], to tss_center of the cell if |d| <= center and to tss_flank if |d| > flank - edge.
+        peak_start / peak_end are disjoint ascending intervals; a record with l or r in one adds 1 to in_peaks of its cell.  None for the
+        sites or for the peaks skips that part.  with_kernel_ms: also return the device time of the call's kernels."""
+        p = np.ascontiguousarray(pos, dtype=np.int64)
+        t = np.ascontiguousarray(tlen, dtype=np.int64)
+        ce = np.ascontiguousarray(cell, dtype=np.int32)
+        sc = np.ascontiguousarray([] if site_center is None else site_center, dtype=np.int64)
+        sm = None if site_minus is None else np.ascontiguousarray(site_minus, dtype=np.uint8)
+        ps = np.ascontiguousarray([] if peak_start is None else peak_start, dtype=np.int64)
+        pe = np.ascontiguousarray([] if peak_end is None else peak_end, dtype=np.int64)
+        if p.ndim != 1 or p.shape != t.shape or p.shape != ce.shape or sc.ndim != 1 or ps.ndim != 1 or ps.shape != pe.shape or \
+                (sm is not None and sm.shape != sc.shape):
+            raise ValueError("pos / tlen / cell, site_center / site_minus and peak_start / peak_end must be 1-d arrays of one length each")
+        n_cells, flank = int(n_cells), int(flank)
+        if not 1 <= n_cells <= L.SPLIT_MAX_BARCODES:      # before it sizes the outputs and is narrowed to the int32 of the C call
+            raise ValueError("n_cells must be in [1, %d] (got %d)" % (L.SPLIT_MAX_BARCODES, n_cells))
+        out = [np.zeros(n_cells, dtype=np.int64) for _ in range(3)]
+        profile = np.zeros(2 * min(max(flank, 0), L.CELLQC_MAX_FLANK) + 1, dtype=np.int64)
+        ms = C.c_double(0)
+        L.check(self._lib.natac_cell_site_qc(self._h, p.shape[0], _ptr(p), _ptr(t), _ptr(ce), n_cells, sc.shape[0], _ptr(sc),
+                                             None if sm is None else _ptr(sm), flank, int(center), int(edge), ps.shape[0], _ptr(ps), _ptr(pe),
+                                             _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(profile), C.byref(ms)))
+        res = (out[0], out[1], out[2], profile)
+        return res + (ms.value,) if with_kernel_ms else res
+
     def site_seq_counts(self, seq, centers, minus, up, down, word=1, with_kernel_ms=False):
         """word counts of `pyatac nucleotide` (_nucleotideHelper, pyatac/get_nucleotide.py:19-38) around the sites of one chromosome:
         (M int64[4 or 16, up + down + 1], n = the sites whose window lies inside the chromosome), exact.  seq: the chromosome's bytes,

@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | split | cellcounts` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -8,7 +8,10 @@ store per cell group (a cluster, a sample, a whitelist) in one pass, each writte
 takes through --bam.  `cellcounts` is this package's own too: the cell-by-window count matrix of a single-cell fragment file (rows the BED
 windows, columns the barcodes of a table), sparse, as MatrixMarket text or .npz.  `cells`, this package's own as well, comes before both: it
 discovers the barcodes of a single-cell fragment file with per-cell fragment counts and writes the table of those that pass the user's
-thresholds, which `split --groups` and `cellcounts --cells` take unchanged.  The other pyatac tools (vplot, bias_vplot) are not part of
+thresholds, which `split --groups` and `cellcounts --cells` take unchanged.  `cellqc`, this package's own too, stands between them: for
+the barcodes of such a table it gives per-cell TSS enrichment (insertions around a BED of transcription start sites, with the aggregate
+profile) and FRiP (the fraction of a cell's fragments in a BED of peaks), and writes the table of the cells that pass the user's thresholds
+on those.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -143,6 +146,28 @@ def add_cells_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output. Default is the fragment file's name without its suffixes")
 
 
+def add_cellqc_parser(sub):
+    p = sub.add_parser("cellqc", help="per-cell TSS enrichment and fraction of fragments in peaks of a single-cell fragment file")
+    p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
+    p.add_argument("--cells", metavar="table", required=True,
+                   help="TAB-separated table whose first column lists the barcodes, in order of first appearance (the table `split --groups` "
+                        "takes and `cells` writes; a group column is not used).  Lines of a barcode the table does not list are left out")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--tss", metavar="bed_file", help="Transcription start sites: every row is centred and counts as one site")
+    p.add_argument("--strand", metavar="int", type=int, default=None, help="Column of --tss with strand information (1-based)")
+    p.add_argument("--peaks", metavar="bed_file", help="Peaks: overlapping rows are merged, a fragment counts once")
+    p.add_argument("--flank", metavar="int", default=1000, type=int, help="Bases on either side of a site that the profile covers. Default is 1000")
+    p.add_argument("--center", metavar="int", default=500, type=int,
+                   help="Insertions within this many bases of a site are the cell's signal. Default is 500")
+    p.add_argument("--edge", metavar="int", default=100, type=int,
+                   help="Insertions in the outermost this many bases of either flank are the cell's background. Default is 100")
+    p.add_argument("--min_tss_enrichment", metavar="float", default=None, type=float,
+                   help="A cell passes only with at least this TSS enrichment. Default is no such test")
+    p.add_argument("--min_frip", metavar="float", default=None, type=float,
+                   help="A cell passes only with at least this fraction of its fragments in peaks. Default is no such test")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the fragment file's name without its suffixes")
+
+
 def add_cellcounts_parser(sub):
     p = sub.add_parser("cellcounts", help="cell-by-window fragment count matrix of a single-cell fragment file")
     p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
@@ -164,8 +189,8 @@ def pyatac_parser():
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
                                                                 "insertion, coverage and Tn5 bias tracks, fragment counts per window, "
                                                                 "nucleotide content and track signal around sites; a single-cell fragment file "
-                                                                "split by cell group, its cell-by-window count matrix, and the discovery "
-                                                                "of its cells")
+                                                                "split by cell group, its cell-by-window count matrix, the discovery "
+                                                                "of its cells and their TSS enrichment and fraction of fragments in peaks")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -178,6 +203,7 @@ def pyatac_parser():
     add_nucleotide_parser(sub)
     add_signal_parser(sub)
     add_cells_parser(sub)
+    add_cellqc_parser(sub)
     add_split_parser(sub)
     add_cellcounts_parser(sub)
     return parser
@@ -254,6 +280,18 @@ def pyatac_main(args):
             get_cells(args)
         except (CellsError, NatacError) as e:
             sys.stderr.write("pyatac cells: %s\n" % e)
+            return 1
+    elif args.call == "cellqc":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .chunk import BedColumnError
+        from .get_cellqc import CellQCError, get_cellqc
+        print("---------Getting per-cell TSS enrichment and FRiP---------------------------------------")
+        print("plots are not produced: only the .cellqc files are written")
+        try:
+            get_cellqc(args)
+        except (CellQCError, BedColumnError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac cellqc: %s\n" % e)
             return 1
     elif args.call == "split":
         from .._lib import NatacError
