@@ -12,6 +12,7 @@
 // Every arm writes (cell, count) pairs, cell ascending, at the row's offset of a staging area (a row needs at most min(h, n_cells)
 // pairs) and the row's number of pairs; a scan of those gives row_ptr, and cc_gather_rows / cc_gather_long move the pairs to their place.
 // Nothing depends on the order of records, waves or blocks: the sort, not the gather order, fixes a row's layout.
+// Behind the kernels: the entry point, which picks every row's arm on the host between two waits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -234,3 +235,116 @@ __global__ void __launch_bounds__(CC_BLOCK) cc_gather_long(long long row, const 
 }
 
 }  // namespace natac_cellcounts
+
+// ---- entry point -----------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int natac_region_cell_counts(natac_ctx *c, int64_t nf, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells,
+                             int64_t nr, const int64_t *start, const int64_t *end, int lower, int upper, int atac, int64_t *row_ptr, int64_t cap,
+                             int32_t *col, int32_t *val, double *kernel_ms) {
+    using namespace natac_cellcounts;
+    static_assert(CC_WAVE_MAX == NATAC_CELLCOUNT_WAVE_MAX && CC_SHORT_MAX == NATAC_CELLCOUNT_SHORT_MAX, "the arms' bounds are in natac.h");
+    if (!c || !row_ptr) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0 || nr < 0 || cap < 0) return fail(NATAC_E_ARG, "negative size");
+    if ((nf > 0 && (!pos || !tlen || !cell)) || (nr > 0 && (!start || !end))) return fail(NATAC_E_ARG, "null argument");
+    if (!col != !val || (!col && cap != 0)) return fail(NATAC_E_ARG, "col and val go together; a sizing call passes neither and cap 0");
+    if (n_cells < 1 || n_cells > NATAC_SPLIT_MAX_BARCODES) return fail(NATAC_E_ARG, "n_cells must be in [1, %d] (got %d)", NATAC_SPLIT_MAX_BARCODES, n_cells);
+    if (upper <= lower) return fail(NATAC_E_ARG, "upper (%d) <= lower (%d)", upper, lower);
+    if (nf >= (1LL << 40) || nr >= (1LL << 40)) return fail(NATAC_E_ARG, "too many records or regions in one call");
+    if (kernel_ms) *kernel_ms = 0;
+    if (const int rc = check_intervals("region", nr, start, end, false)) return rc;
+    if (const int rc = check_fragments(nf, pos, tlen, cell, n_cells)) return rc;
+    for (int64_t i = 0; i <= nr; ++i) row_ptr[i] = 0;
+    if (nr == 0 || nf == 0) return NATAC_OK;
+    DeviceCall dc(c, "region_cell_counts");
+    const long long *d_pos = dc.upload((const long long *)pos, (size_t)nf), *d_tlen = dc.upload((const long long *)tlen, (size_t)nf);
+    const int *d_cell = dc.upload((const int *)cell, (size_t)nf);
+    const long long *d_s = dc.upload((const long long *)start, (size_t)nr), *d_e = dc.upload((const long long *)end, (size_t)nr);
+    long long *d_lo = dc.alloc<long long>((size_t)nr), *d_n = dc.alloc<long long>((size_t)nr), *d_long = dc.alloc<long long>((size_t)nr);
+    unsigned long long *d_hits = dc.zeroed<unsigned long long>((size_t)nr + 1);     // hits[nr], then natac_region_ranges' long-region count
+    const int shift = atac ? 4 : 0, trim = atac ? 8 : 0;
+    // the events span the whole call on the stream: its kernels and the two host round trips between them
+    dc.time_begin(kernel_ms);
+    // (1) candidates and hits per row, as natac_region_counts
+    region_hits(dc, c, d_pos, d_tlen, nf, nr, d_s, d_e, lower, upper, shift, trim, d_lo, d_n, d_long, d_hits);
+    std::vector<unsigned long long> h_hits((size_t)nr);
+    dc.fetch(h_hits.data(), d_hits, (size_t)nr);
+    if (const int rc = dc.sync()) return rc;
+    // (2) the arm of every row and its place in the staging area: a row of h hits has at most min(h, n_cells) pairs
+    std::vector<unsigned long long> h_off((size_t)nr + 1);
+    std::vector<long long> mid_rows, long_rows;
+    unsigned long long n_stage = 0;
+    for (int64_t i = 0; i < nr; ++i) {
+        const unsigned long long h = h_hits[(size_t)i];
+        if (h > 2147483647ULL) return fail(NATAC_E_ARG, "region %lld: %llu counting records, more than 2147483647", (long long)i, h);
+        h_off[(size_t)i] = n_stage;
+        n_stage += std::min<unsigned long long>(h, (unsigned long long)n_cells);
+        if (h > (unsigned long long)CC_SHORT_MAX) long_rows.push_back(i);
+        else if (h > (unsigned long long)CC_WAVE_MAX) mid_rows.push_back(i);
+    }
+    h_off[(size_t)nr] = n_stage;
+    const unsigned long long *d_off = dc.upload(h_off.data(), h_off.size());
+    int *d_scol = dc.alloc<int>((size_t)n_stage), *d_sval = dc.alloc<int>((size_t)n_stage);
+    unsigned long long *d_nnz = dc.zeroed<unsigned long long>((size_t)nr);
+    unsigned long long *d_rp = dc.alloc<unsigned long long>((size_t)nr + 1);
+    if (dc.ok()) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + CC_BLOCK / 64 - 1) / (CC_BLOCK / 64), 16384);
+        hipLaunchKernelGGL(cc_rows_wave, dim3(bx), dim3(CC_BLOCK), 0, c->stream, d_pos, d_tlen, d_cell, (long long)nr, d_s, d_e, d_lo, d_n, d_hits,
+                           d_off, lower, upper, shift, trim, d_scol, d_sval, d_nnz);
+        dc.launched();
+    }
+    if (!mid_rows.empty()) {
+        const long long *d_list = dc.upload(mid_rows.data(), mid_rows.size());
+        if (dc.ok()) {
+            const unsigned bx = (unsigned)std::min<size_t>(mid_rows.size(), 16384);
+            hipLaunchKernelGGL(cc_rows_block, dim3(bx), dim3(CC_BLOCK), 0, c->stream, d_pos, d_tlen, d_cell, d_list, (long long)mid_rows.size(), d_s,
+                               d_e, d_lo, d_n, d_hits, d_off, lower, upper, shift, trim, d_scol, d_sval, d_nnz);
+            dc.launched();
+        }
+    }
+    const unsigned cell_blocks = (unsigned)(((long long)n_cells + CC_CELLS_PER_BLOCK - 1) / CC_CELLS_PER_BLOCK);
+    if (!long_rows.empty()) {
+        unsigned *d_dense = dc.zeroed<unsigned>((size_t)n_cells);
+        unsigned long long *d_sums = dc.alloc<unsigned long long>((size_t)cell_blocks + 1);
+        for (const long long row : long_rows) {             // one long row at a time: they share the counters
+            if (!dc.ok()) break;
+            hipLaunchKernelGGL(cc_long_count, dim3(2048), dim3(CC_BLOCK), 0, c->stream, d_pos, d_tlen, d_cell, row, d_s, d_e, d_lo, d_n, lower,
+                               upper, shift, trim, d_dense);
+            hipLaunchKernelGGL(cc_long_block_nnz, dim3(cell_blocks), dim3(CC_BLOCK), 0, c->stream, d_dense, (int)n_cells, d_sums);
+            hipLaunchKernelGGL(natac_textz::tz_scan_sums, dim3(1), dim3(1024), 0, c->stream, d_sums, (long long)cell_blocks);
+            hipLaunchKernelGGL(cc_long_compact, dim3(cell_blocks), dim3(CC_BLOCK), 0, c->stream, d_dense, (int)n_cells, d_sums, row, d_off, d_scol,
+                               d_sval, d_nnz);
+            dc.launched();
+        }
+    }
+    // (3) row_ptr = the scan of the rows' pair counts
+    dev_scan(c, d_nnz, (long long)nr, d_rp, dc);
+    dc.fetch(row_ptr, d_rp, (size_t)nr + 1);
+    if (const int rc = dc.sync()) {
+        for (int64_t i = 0; i <= nr; ++i) row_ptr[i] = 0;
+        return rc;
+    }
+    const int64_t nnz = row_ptr[nr];
+    if (!col || nnz > cap) {
+        dc.time_end();
+        const int rc = dc.finish();
+        if (rc) return rc;
+        if (!col) return NATAC_OK;                          // the sizing call
+        return fail(NATAC_E_ARG, "cap %lld is less than the %lld entries of the matrix", (long long)cap, (long long)nnz);
+    }
+    // (4) staging -> CSR
+    int *d_col = dc.alloc<int>((size_t)nnz), *d_val = dc.alloc<int>((size_t)nnz);
+    if (dc.ok() && nnz) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + CC_BLOCK / 64 - 1) / (CC_BLOCK / 64), 16384);
+        hipLaunchKernelGGL(cc_gather_rows, dim3(bx), dim3(CC_BLOCK), 0, c->stream, (long long)nr, d_hits, d_off, d_rp, d_scol, d_sval, d_col, d_val);
+        for (const long long row : long_rows)
+            hipLaunchKernelGGL(cc_gather_long, dim3(1024), dim3(CC_BLOCK), 0, c->stream, row, d_off, d_rp, d_scol, d_sval, d_col, d_val);
+        dc.launched();
+    }
+    dc.time_end();
+    dc.fetch(col, d_col, (size_t)nnz);
+    dc.fetch(val, d_val, (size_t)nnz);
+    return dc.finish();
+}
+
+}  // extern "C"

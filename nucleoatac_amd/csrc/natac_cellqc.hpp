@@ -17,8 +17,11 @@
 // flush_tiles * 2 * CQ_BLOCK * n_sites < 2^32 no 32-bit counter has wrapped; the host computes flush_tiles from the n_sites of the launch and
 // launches over at most CQ_SITE_CHUNK sites at a time (the sum over any split of the sites is the single call).  A flush adds the non-zero
 // counters to the int64 profile with 64-bit global atomics and clears them.  Only integer atomics: the result is a pure function of the inputs.
+// Behind the kernel: the entry point with the operand checks and the launches over the site chunks.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "natac_sites.hpp"
 
 namespace natac_cellqc {
 
@@ -152,3 +155,66 @@ __global__ void __launch_bounds__(CQ_BLOCK) cq_count(const long long *__restrict
 }
 
 }  // namespace natac_cellqc
+
+// ---- entry point -----------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int natac_cell_site_qc(natac_ctx *c, int64_t nf, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells, int64_t ns,
+                       const int64_t *site_center, const uint8_t *site_minus, int flank, int center, int edge, int64_t np,
+                       const int64_t *peak_start, const int64_t *peak_end, int64_t *tss_center, int64_t *tss_flank, int64_t *in_peaks,
+                       int64_t *profile, double *kernel_ms) {
+    using namespace natac_cellqc;
+    static_assert(CQ_MAX_FLANK == NATAC_CELLQC_MAX_FLANK && CQ_BLOCK == NATAC_CELLQC_BLOCK && CQ_LANE_MAX == NATAC_CELLQC_LANE_MAX &&
+                      CQ_MAX_BLOCKS == NATAC_CELLQC_MAX_BLOCKS && CQ_SITE_CHUNK == NATAC_CELLQC_SITE_CHUNK,
+                  "the kernel's sizes are in natac.h");
+    static_assert(2ULL * CQ_BLOCK * CQ_SITE_CHUNK <= 0xffffffffULL, "a tile's pairs fit a 32-bit counter");
+    static_assert((2 * CQ_MAX_FLANK + 1) * sizeof(unsigned) * 8 <= 160 * 1024, "eight workgroups' profiles fit the LDS of a CU");
+    if (!c || !tss_center || !tss_flank || !in_peaks || !profile) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0 || ns < 0 || np < 0) return fail(NATAC_E_ARG, "negative size");
+    if ((nf > 0 && (!pos || !tlen || !cell)) || (ns > 0 && !site_center) || (np > 0 && (!peak_start || !peak_end)))
+        return fail(NATAC_E_ARG, "null argument");
+    if (flank < 1 || flank > NATAC_CELLQC_MAX_FLANK) return fail(NATAC_E_ARG, "flank must be in [1, %d] (got %d)", NATAC_CELLQC_MAX_FLANK, flank);
+    if (center < 0 || edge < 1 || (long long)center + edge > flank)
+        return fail(NATAC_E_ARG, "0 <= center, 1 <= edge and center + edge <= flank must hold (got center %d, edge %d, flank %d)", center, edge,
+                    flank);
+    if (n_cells < 1 || n_cells > NATAC_SPLIT_MAX_BARCODES) return fail(NATAC_E_ARG, "n_cells must be in [1, %d] (got %d)", NATAC_SPLIT_MAX_BARCODES, n_cells);
+    if (nf >= (1LL << 40) || ns >= (1LL << 40) || np >= (1LL << 40)) return fail(NATAC_E_ARG, "too many records, sites or peaks in one call");
+    // the kernel searches the two tables and indexes counters by cell and by d + flank: all of that is checked here
+    if (const int rc = check_fragments(nf, pos, tlen, cell, n_cells)) return rc;
+    if (const int rc = check_site_centres(ns, site_center)) return rc;
+    if (const int rc = check_intervals("peak", np, peak_start, peak_end, true)) return rc;
+    const int K = 2 * flank + 1;
+    if (kernel_ms) *kernel_ms = 0;       // behind the checks: a refused call leaves every output as it was
+    for (int32_t i = 0; i < n_cells; ++i) tss_center[i] = tss_flank[i] = in_peaks[i] = 0;
+    for (int i = 0; i < K; ++i) profile[i] = 0;
+    if (nf == 0 || (ns == 0 && np == 0)) return NATAC_OK;
+    DeviceCall dc(c, "cell_site_qc");
+    const long long *d_pos = dc.upload((const long long *)pos, (size_t)nf), *d_tlen = dc.upload((const long long *)tlen, (size_t)nf);
+    const int *d_cell = dc.upload((const int *)cell, (size_t)nf);
+    const long long *d_sc = ns ? dc.upload((const long long *)site_center, (size_t)ns) : nullptr;
+    const unsigned char *d_sm = ns && site_minus ? dc.upload((const unsigned char *)site_minus, (size_t)ns) : nullptr;
+    const long long *d_ps = np ? dc.upload((const long long *)peak_start, (size_t)np) : nullptr;
+    const long long *d_pe = np ? dc.upload((const long long *)peak_end, (size_t)np) : nullptr;
+    const size_t n_out = 3 * (size_t)n_cells + (size_t)K;          // tss_center, tss_flank, in_peaks, profile
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(n_out);
+    const long long n_tiles = (nf + CQ_BLOCK - 1) / CQ_BLOCK;
+    const unsigned bx = (unsigned)std::min<long long>(n_tiles, CQ_MAX_BLOCKS);
+    dc.time_begin(kernel_ms);
+    for (long long s0 = 0; s0 == 0 || s0 < ns; s0 += CQ_SITE_CHUNK) {      // the peaks go with the first launch
+        if (!dc.ok()) break;
+        const long long n = std::min<long long>(ns - s0, CQ_SITE_CHUNK);
+        const long long flush_tiles = n ? std::max<long long>(1, (long long)(0xffffffffULL / (2ULL * CQ_BLOCK * (unsigned long long)n))) : 1;
+        hipLaunchKernelGGL(cq_count, dim3(bx), dim3(CQ_BLOCK), (size_t)K * sizeof(unsigned), c->stream, d_pos, d_tlen, d_cell, (long long)nf,
+                           (int)n_cells, d_sc ? d_sc + s0 : nullptr, d_sm ? d_sm + s0 : nullptr, n, flank, center, edge, d_ps, d_pe,
+                           s0 == 0 ? (long long)np : 0LL, flush_tiles, d_out);
+        dc.launched();
+    }
+    dc.time_end();
+    dc.fetch(tss_center, d_out, (size_t)n_cells);
+    dc.fetch(tss_flank, d_out + n_cells, (size_t)n_cells);
+    dc.fetch(in_peaks, d_out + 2 * (size_t)n_cells, (size_t)n_cells);
+    dc.fetch(profile, d_out + 3 * (size_t)n_cells, (size_t)K);
+    return dc.finish();
+}
+
+}  // extern "C"

@@ -898,7 +898,7 @@ struct SplitJob : FragJob {
 };
 
 // ---- the driver: per window (a), then the job, then the carry of the bytes behind the last '\n' ----
-// "" or why the host path answers instead (natac_api.hip runs it).  A job's window() synchronises the stream before it returns.
+// "" or why the host path answers instead (natac_files.hpp runs it).  A job's window() synchronises the stream before it returns.
 template <class Job>
 inline std::string decode_device(const char *path, hipStream_t stream, size_t window_bytes, Job &job) {
     DevBuf d_tile, d_ls, d_total;

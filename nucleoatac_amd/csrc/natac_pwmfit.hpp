@@ -6,8 +6,11 @@
 //                         pyatac/seq.py:47-72)
 // Every count is an integer: the kernels add in registers and LDS as 32-bit, and every block adds its totals to the int64 result with
 // one atomic per counter, so the result is exact and does not depend on the order of the fragments, the blocks or the waves.
+// Behind the kernels: their entry points (natac_insertion_seq_counts, natac_base_counts).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "natac_runtime.hpp"
 
 namespace natac_pwmfit {
 
@@ -154,3 +157,94 @@ __global__ void __launch_bounds__(PF_BLOCK) natac_base_count(const unsigned char
 }
 
 }  // namespace natac_pwmfit
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int natac_insertion_seq_counts(natac_ctx *c, int32_t nc, const int32_t *chunk_len, const int64_t *frag_off, const int32_t *frag_lpos,
+                               const int32_t *frag_ilen, const int64_t *seq_off, const uint8_t *seq, int flank, int lower, int upper, int sym,
+                               int64_t *counts, int64_t *n_ins, double *kernel_ms) {
+    using namespace natac_pwmfit;
+    if (!c || !counts || !n_ins) return fail(NATAC_E_ARG, "null argument");
+    if (flank < 0 || flank > PF_MAX_FLANK) return fail(NATAC_E_ARG, "flank must be in [0, %d] (got %d)", PF_MAX_FLANK, flank);
+    if (upper <= lower) return fail(NATAC_E_ARG, "upper (%d) <= lower (%d)", upper, lower);
+    if (nc < 0) return fail(NATAC_E_ARG, "negative chunk count");
+    if (nc > 0 && (!chunk_len || !frag_off || !seq_off)) return fail(NATAC_E_ARG, "null argument");
+    const int K = 2 * flank + 1;
+    if (kernel_ms) *kernel_ms = 0;
+    for (int i = 0; i < 4 * K; ++i) counts[i] = 0;
+    *n_ins = 0;
+    if (nc == 0) return NATAC_OK;
+    // the kernel trusts both offset arrays: every window access lies in [seq_off[k], seq_off[k+1]), every fragment in one chunk
+    if (frag_off[0] != 0 || seq_off[0] != 0) return fail(NATAC_E_ARG, "frag_off[0] and seq_off[0] must be 0");
+    for (int k = 0; k < nc; ++k) {
+        if (chunk_len[k] < 0) return fail(NATAC_E_ARG, "chunk %d: negative length", k);
+        if (frag_off[k + 1] < frag_off[k]) return fail(NATAC_E_ARG, "frag_off must be non-decreasing (chunk %d)", k);
+        if (seq_off[k + 1] - seq_off[k] != (int64_t)chunk_len[k] + K - 1)
+            return fail(NATAC_E_ARG, "seq_off: chunk %d has %lld bases, its window [start - %d, end + %d) needs %lld", k,
+                        (long long)(seq_off[k + 1] - seq_off[k]), flank, flank, (long long)chunk_len[k] + K - 1);
+    }
+    const long long nf = frag_off[nc], ns = seq_off[nc];
+    if (nf > 0 && (!frag_lpos || !frag_ilen)) return fail(NATAC_E_ARG, "null argument");
+    if (ns > 0 && !seq) return fail(NATAC_E_ARG, "null argument");
+    if (nf >= (1LL << 40)) return fail(NATAC_E_ARG, "too many fragments in one call");
+    if (nf == 0) return NATAC_OK;
+    DeviceCall dc(c, "insertion_seq_counts");
+    const int *d_len = dc.upload(chunk_len, (size_t)nc);
+    const long long *d_fo = dc.upload((const long long *)frag_off, (size_t)nc + 1), *d_so = dc.upload((const long long *)seq_off, (size_t)nc + 1);
+    const int *d_l = dc.upload(frag_lpos, (size_t)nf), *d_n = dc.upload(frag_ilen, (size_t)nf);
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)ns);
+    std::vector<unsigned long long> h((size_t)4 * K + 1);
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(h.size());
+    dc.time_begin(kernel_ms);
+    if (dc.ok()) {
+        const int CW = K < 64 ? K : 64;
+        const long long nseg = (nf + PF_SEG - 1) / PF_SEG;
+        const int bx = (int)std::min<long long>((nseg + PF_BLOCK / 64 - 1) / (PF_BLOCK / 64), 2048);
+        hipLaunchKernelGGL(natac_ins_seq_counts, dim3(bx, (K + CW - 1) / CW), dim3(PF_BLOCK), 0, c->stream, d_fo, d_l, d_n, nf, (int)nc,
+                           d_len, d_so, d_s, flank, lower, upper, sym ? 1 : 0, d_out, d_out + 4 * K);
+        dc.launched();
+    }
+    dc.time_end();
+    dc.fetch(h.data(), d_out, h.size());
+    const int rc = dc.finish();
+    if (rc) return rc;
+    for (int i = 0; i < 4 * K; ++i) counts[i] = (int64_t)h[i];
+    *n_ins = (int64_t)h[4 * K];
+    return NATAC_OK;
+}
+
+int natac_base_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int32_t nr, const int64_t *start, const int64_t *end, int64_t *counts) {
+    using namespace natac_pwmfit;
+    if (!c || !counts || n < 0 || nr < 0) return fail(NATAC_E_ARG, "null argument or negative size");
+    if (nr > 0 && (!start || !end)) return fail(NATAC_E_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) counts[i] = 0;
+    std::vector<long long> cum((size_t)nr + 1, 0);
+    for (int i = 0; i < nr; ++i) {
+        if (start[i] < 0 || end[i] < start[i] || end[i] > n)
+            return fail(NATAC_E_ARG, "range %d [%lld, %lld) outside [0, %lld)", i, (long long)start[i], (long long)end[i], (long long)n);
+        cum[i + 1] = cum[i] + (end[i] - start[i]);
+    }
+    const long long total = cum[nr];
+    if (total == 0) return NATAC_OK;
+    if (!seq) return fail(NATAC_E_ARG, "null argument");
+    // lane counters are 32-bit: a block adds at most ceil(total / blocks) bases
+    const long long bx = std::min<long long>((total + PF_SPAN - 1) / PF_SPAN, 8192);
+    if ((total + bx - 1) / bx >= (1LL << 31)) return fail(NATAC_E_ARG, "ranges too long for one call");
+    DeviceCall dc(c, "base_counts");
+    const unsigned char *d_s = dc.upload((const unsigned char *)seq, (size_t)n);
+    const long long *d_st = dc.upload((const long long *)start, (size_t)nr), *d_cum = dc.upload(cum.data(), cum.size());
+    unsigned long long h[4] = {0, 0, 0, 0};
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(4);
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_base_count, dim3((unsigned)bx), dim3(PF_BLOCK), 0, c->stream, d_s, (int)nr, d_st, d_cum, d_out);
+        dc.launched();
+    }
+    dc.fetch(h, d_out, 4);
+    const int rc = dc.finish();
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) counts[i] = (int64_t)h[i];
+    return NATAC_OK;
+}
+
+}  // extern "C"

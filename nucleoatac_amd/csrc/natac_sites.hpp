@@ -9,6 +9,8 @@
 //                          (_signalHelper, signal_around_sites.py:24-74)
 // Every count is an integer: lanes and waves add 32-bit partial counts, the results are 64-bit, and nothing depends on the order of
 // the records, the sites, the blocks or the waves.  The signal sums are float64 and are added in one fixed order, without atomics.
+// Behind the kernels: the host's checks of the operands they trust, and the entry points (natac_region_counts, natac_site_seq_counts,
+// natac_site_signal).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -296,3 +298,205 @@ __global__ void __launch_bounds__(SG_BLOCK) natac_site_signal_agg(const double *
 }
 
 }  // namespace natac_sites
+
+// ---- the host's checks ------------------------------------------------------------------------------------------------------------
+// The kernels here and in natac_cellcounts.hpp and natac_cellqc.hpp search their tables and index counters without looking again: the
+// host checks every operand those indices rest on, once per kind.  Each check returns NATAC_OK or the refusal (NATAC_E_ARG).
+
+constexpr long long COORD_LIM = 1LL << 60;      // coordinates far inside int64: start - upper, pos + tlen, x +- flank cannot overflow
+
+// the fragment table of one chromosome: sorted by pos (the FragmentStore's order; the kernels search it), cell (may be null: a table
+// without cells) an index into n_cells counters
+static int check_fragments(int64_t nf, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells) {
+    for (int64_t i = 0; i < nf; ++i) {
+        if (pos[i] < -COORD_LIM || pos[i] > COORD_LIM || tlen[i] < -COORD_LIM || tlen[i] > COORD_LIM)
+            return fail(NATAC_E_ARG, "record %lld: pos or tlen out of range", (long long)i);
+        if (i && pos[i] < pos[i - 1]) return fail(NATAC_E_ARG, "pos must be non-decreasing (record %lld)", (long long)i);
+        if (cell && (cell[i] < 0 || cell[i] >= n_cells))
+            return fail(NATAC_E_ARG, "record %lld: cell %d outside [0, %d)", (long long)i, cell[i], n_cells);
+    }
+    return NATAC_OK;
+}
+
+// a table of intervals [start, end), `what` = "region" or "peak"; disjoint_ascending: every interval starts at or behind the end of the
+// one before (the peaks, which the kernel searches).  An interval that is both inverted and out of range is reported as out of range
+// in such a table and as inverted in the other, as the two always were.
+static int check_intervals(const char *what, int64_t n, const int64_t *start, const int64_t *end, bool disjoint_ascending) {
+    for (int64_t i = 0; i < n; ++i) {
+        const bool far = start[i] < -COORD_LIM || end[i] > COORD_LIM;
+        if (end[i] < start[i] && !(far && disjoint_ascending))
+            return fail(NATAC_E_ARG, "%s %lld: end %lld < start %lld", what, (long long)i, (long long)end[i], (long long)start[i]);
+        if (far) return fail(NATAC_E_ARG, "%s %lld: coordinates out of range", what, (long long)i);
+        if (disjoint_ascending && i && start[i] < end[i - 1])
+            return fail(NATAC_E_ARG, "%ss must be disjoint and ascending (%s %lld starts at %lld, before the end %lld of the one before)", what,
+                        what, (long long)i, (long long)start[i], (long long)end[i - 1]);
+    }
+    return NATAC_OK;
+}
+
+// the centres of a site table the kernel searches
+static int check_site_centres(int64_t ns, const int64_t *centre) {
+    for (int64_t i = 0; i < ns; ++i) {
+        if (centre[i] < -COORD_LIM || centre[i] > COORD_LIM) return fail(NATAC_E_ARG, "site %lld: centre out of range", (long long)i);
+        if (i && centre[i] < centre[i - 1]) return fail(NATAC_E_ARG, "site centres must be ascending (site %lld)", (long long)i);
+    }
+    return NATAC_OK;
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------------
+
+// hits[i] = the records that count for region i (hits[nr]: natac_region_ranges' number of long regions, zeroed by the caller); cand_lo and
+// cand_n are left for whoever walks the candidates again.  Queued on the call's stream, failures stay in its latch.
+static void region_hits(DeviceCall &dc, natac_ctx *c, const long long *d_pos, const long long *d_tlen, long long nf, long long nr,
+                        const long long *d_s, const long long *d_e, int lower, int upper, int shift, int trim, long long *d_lo,
+                        long long *d_n, long long *d_long, unsigned long long *d_hits) {
+    using namespace natac_sites;
+    if (dc.ok()) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK - 1) / RC_BLOCK, 4096);
+        hipLaunchKernelGGL(natac_region_ranges, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, nf, nr, d_s, d_e, lower, upper, shift, d_lo,
+                           d_n, d_long, d_hits + nr);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        const unsigned bx = (unsigned)std::min<long long>((nr + RC_BLOCK / 64 - 1) / (RC_BLOCK / 64), 8192);
+        hipLaunchKernelGGL(natac_region_count_short, dim3(bx), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, nr, d_s, d_e, d_lo, d_n, lower,
+                           upper, shift, trim, d_hits);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        // the number of long regions stays on the device: a fixed grid, idle when there is none
+        const unsigned bx = (unsigned)std::min<long long>(nr, 128);
+        hipLaunchKernelGGL(natac_region_count_long, dim3(bx, RC_LONG_Y), dim3(RC_BLOCK), 0, c->stream, d_pos, d_tlen, d_s, d_e, d_lo, d_n,
+                           d_long, d_hits + nr, lower, upper, shift, trim, d_hits);
+        dc.launched();
+    }
+}
+
+extern "C" {
+
+int natac_region_counts(natac_ctx *c, int64_t nf, const int64_t *pos, const int64_t *tlen, int64_t nr, const int64_t *start,
+                        const int64_t *end, int lower, int upper, int atac, int64_t *counts, double *kernel_ms) {
+    if (!c) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0 || nr < 0) return fail(NATAC_E_ARG, "negative size");
+    if ((nf > 0 && (!pos || !tlen)) || (nr > 0 && (!start || !end || !counts))) return fail(NATAC_E_ARG, "null argument");
+    if (upper <= lower) return fail(NATAC_E_ARG, "upper (%d) <= lower (%d)", upper, lower);
+    if (nf >= (1LL << 40) || nr >= (1LL << 40)) return fail(NATAC_E_ARG, "too many records or regions in one call");
+    if (kernel_ms) *kernel_ms = 0;
+    if (const int rc = check_intervals("region", nr, start, end, false)) return rc;
+    if (const int rc = check_fragments(nf, pos, tlen, nullptr, 0)) return rc;
+    for (int64_t i = 0; i < nr; ++i) counts[i] = 0;
+    if (nr == 0 || nf == 0) return NATAC_OK;
+    DeviceCall dc(c, "region_counts");
+    const long long *d_pos = dc.upload((const long long *)pos, (size_t)nf), *d_tlen = dc.upload((const long long *)tlen, (size_t)nf);
+    const long long *d_s = dc.upload((const long long *)start, (size_t)nr), *d_e = dc.upload((const long long *)end, (size_t)nr);
+    long long *d_lo = dc.alloc<long long>((size_t)nr), *d_n = dc.alloc<long long>((size_t)nr), *d_long = dc.alloc<long long>((size_t)nr);
+    unsigned long long *d_out = dc.zeroed<unsigned long long>((size_t)nr + 1);      // counts[nr], then the number of long regions
+    dc.time_begin(kernel_ms);
+    region_hits(dc, c, d_pos, d_tlen, nf, nr, d_s, d_e, lower, upper, atac ? 4 : 0, atac ? 8 : 0, d_lo, d_n, d_long, d_out);
+    dc.time_end();
+    dc.fetch(counts, d_out, (size_t)nr);
+    return dc.finish();
+}
+
+int natac_site_seq_counts(natac_ctx *c, const uint8_t *seq, int64_t n, int64_t ns, const int64_t *center, const uint8_t *minus, int up,
+                          int down, int word, int64_t *counts, int64_t *n_used, double *kernel_ms) {
+    using namespace natac_sites;
+    if (!c || !counts || !n_used) return fail(NATAC_E_ARG, "null argument");
+    if (n < 0 || ns < 0) return fail(NATAC_E_ARG, "negative size");
+    if (word != 1 && word != 2) return fail(NATAC_E_ARG, "word length must be 1 or 2 (got %d)", word);
+    if (up < 0 || down < 0 || up > SS_MAX_FLANK || down > SS_MAX_FLANK)
+        return fail(NATAC_E_ARG, "up and down must be in [0, %d] (got %d, %d)", SS_MAX_FLANK, up, down);
+    if ((n > 0 && !seq) || (ns > 0 && !center)) return fail(NATAC_E_ARG, "null argument");
+    if (ns >= (1LL << 40)) return fail(NATAC_E_ARG, "too many sites in one call");
+    const int K = up + down + 1, R = word == 2 ? 16 : 4;
+    if (kernel_ms) *kernel_ms = 0;
+    // the kernel trusts the centres: every window it reads is checked against [0, n) from a centre inside it
+    for (int64_t i = 0; i < ns; ++i)
+        if (center[i] < 0 || center[i] >= n)
+            return fail(NATAC_E_ARG, "site %lld: centre %lld outside the sequence [0, %lld)", (long long)i, (long long)center[i], (long long)n);
+    for (long long i = 0; i < (long long)R * K; ++i) counts[i] = 0;
+    *n_used = 0;
+    if (ns == 0) return NATAC_OK;
+    DeviceCall dc(c, "site_seq_counts");
+    const size_t nout = (size_t)R * K + 1;      // counts[R x K], then n_used
+    const unsigned char *d_seq = dc.upload((const unsigned char *)seq, (size_t)n);
+    const long long *d_c = dc.upload((const long long *)center, (size_t)ns);
+    const unsigned char *d_m = minus ? dc.upload((const unsigned char *)minus, (size_t)ns) : nullptr;
+    unsigned long long *d_out = dc.zeroed<unsigned long long>(nout);
+    std::vector<unsigned long long> h(nout);
+    dc.time_begin(kernel_ms);
+    if (dc.ok()) {
+        const unsigned bx = (unsigned)std::min<long long>((ns + SS_SEG - 1) / SS_SEG, 1024);
+        hipLaunchKernelGGL(natac_site_seq_count, dim3(bx, (unsigned)((K + SS_TILE - 1) / SS_TILE)), dim3(SS_BLOCK), 0, c->stream, d_seq,
+                           (long long)n, (long long)ns, d_c, d_m, up, down, word, d_out, d_out + (nout - 1));
+        dc.launched();
+    }
+    dc.time_end();
+    dc.fetch(h.data(), d_out, nout);
+    const int rc = dc.finish();
+    if (rc) return rc;
+    for (size_t i = 0; i + 1 < nout; ++i) counts[i] = (int64_t)h[i];
+    *n_used = (int64_t)h[nout - 1];
+    return NATAC_OK;
+}
+
+int natac_site_signal(natac_ctx *c, const double *vals, int64_t n_vals, int64_t ns, const int64_t *src, const int32_t *len,
+                      const int32_t *lead, const uint8_t *minus, int K, int flags, double *mat, double *agg, double *kernel_ms) {
+    using namespace natac_sites;
+    static_assert(SG_SEG == NATAC_SIGNAL_SEG, "the segment length is part of the documented summation order");
+    if (!c || !agg) return fail(NATAC_E_ARG, "null argument");
+    if (n_vals < 0 || ns < 0) return fail(NATAC_E_ARG, "negative size");
+    if (K < 1 || K > 2 * SS_MAX_FLANK + 1) return fail(NATAC_E_ARG, "K must be in [1, %d] (got %d)", 2 * SS_MAX_FLANK + 1, K);
+    if (flags & ~(SG_EXP | SG_POSITIVE | SG_SCALE)) return fail(NATAC_E_ARG, "flags must be a sum of 1 (exp), 2 (positive), 4 (scale) (got %d)", flags);
+    if ((n_vals > 0 && !vals) || (ns > 0 && (!src || !len || !lead))) return fail(NATAC_E_ARG, "null argument");
+    if (ns >= (1LL << 40)) return fail(NATAC_E_ARG, "too many sites in one call");
+    if (kernel_ms) *kernel_ms = 0;
+    // the kernels trust their operands: every read is vals[src + r] with 0 <= r < len
+    for (int64_t i = 0; i < ns; ++i) {
+        if (len[i] < 0 || lead[i] < 0) return fail(NATAC_E_ARG, "site %lld: negative len (%d) or lead (%d)", (long long)i, len[i], lead[i]);
+        if ((int64_t)lead[i] + len[i] > K)
+            return fail(NATAC_E_ARG, "site %lld: lead %d + len %d exceed the %d columns", (long long)i, lead[i], len[i], K);
+        if (src[i] < 0 || src[i] > n_vals || len[i] > n_vals - src[i])
+            return fail(NATAC_E_ARG, "site %lld: values [%lld, %lld + %d) outside [0, %lld)", (long long)i, (long long)src[i], (long long)src[i],
+                        len[i], (long long)n_vals);
+    }
+    for (int j = 0; j < K; ++j) agg[j] = 0;
+    if (ns == 0) return NATAC_OK;
+    const long long nseg = (ns + SG_SEG - 1) / SG_SEG;
+    DeviceCall dc(c, "site_signal");
+    const double *d_v = dc.upload(vals, (size_t)n_vals);
+    const long long *d_src = dc.upload((const long long *)src, (size_t)ns);
+    const int *d_len = dc.upload(len, (size_t)ns), *d_lead = dc.upload(lead, (size_t)ns);
+    const unsigned char *d_m = minus ? dc.upload((const unsigned char *)minus, (size_t)ns) : nullptr;
+    double *d_div = (flags & SG_SCALE) ? dc.alloc<double>((size_t)ns) : nullptr;
+    double *d_mat = mat ? dc.alloc<double>((size_t)ns * K) : nullptr;
+    double *d_part = dc.alloc<double>((size_t)nseg * K), *d_agg = dc.alloc<double>((size_t)K);
+    dc.time_begin(kernel_ms);
+    if (dc.ok() && (flags & SG_SCALE)) {
+        int W = 1;                          // the kernel's group width: 64 / W sites per wave
+        while (W < K && W < 64) W <<= 1;
+        const long long per_block = (SG_BLOCK / 64) * (64 / W);
+        const unsigned bx = (unsigned)std::min<long long>((ns + per_block - 1) / per_block, 8192);
+        hipLaunchKernelGGL(natac_site_signal_div, dim3(bx), dim3(SG_BLOCK), 0, c->stream, d_v, (long long)ns, d_src, d_len, d_lead, d_m, K,
+                           flags, d_div);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        const int ng = SG_BLOCK / std::min(K, SG_TILE);      // segments per block in the widest tile
+        const unsigned bx = (unsigned)std::min<long long>((nseg + ng - 1) / ng, 65535);
+        hipLaunchKernelGGL(natac_site_signal_rows, dim3(bx, (unsigned)((K + SG_TILE - 1) / SG_TILE)), dim3(SG_BLOCK), 0, c->stream, d_v,
+                           (long long)ns, d_src, d_len, d_lead, d_m, K, flags, d_div, d_mat, d_part);
+        dc.launched();
+    }
+    if (dc.ok()) {
+        hipLaunchKernelGGL(natac_site_signal_agg, dim3((unsigned)((K + SG_BLOCK - 1) / SG_BLOCK)), dim3(SG_BLOCK), 0, c->stream, d_part, nseg,
+                           K, d_agg);
+        dc.launched();
+    }
+    dc.time_end();
+    if (mat) dc.fetch(mat, d_mat, (size_t)ns * K);
+    dc.fetch(agg, d_agg, (size_t)K);
+    return dc.finish();
+}
+
+}  // extern "C"

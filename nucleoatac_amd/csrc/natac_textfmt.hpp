@@ -26,7 +26,7 @@ namespace natac_text {
 
 struct P10 { uint64_t hi, lo; int e; int exact; };
 
-static const P10 H_P10[] = {      // host copy; natac_api.hip uploads it once per context for the kernels
+static const P10 H_P10[] = {      // host copy; natac_trackio.hpp (ensure_text_tables) uploads it once per context for the kernels
 #include "natac_pow10.inc"
 };
 

@@ -1,10 +1,14 @@
-"""CPU: who returns device memory in natac_api.hip.  Pool blocks go back only through the owner type (PoolBuf) and the pool itself;
-hipFree is the pool's, plus the clock trace's sampler buffer (d_ck), which relies on hipFree's implicit device synchronisation."""
+"""CPU: who takes and returns device memory in the library's translation unit (natac_api.hip and every csrc/*.hpp it includes).  Pool
+blocks go back only through the owner type (PoolBuf, natac_runtime.hpp) and the pool itself; hipMalloc and hipFree are the pool's, plus
+two owners outside it: DevBuf (natac_bgzf_dev.hpp), the device decoders' window owner -- a cached 8 GiB window would starve the
+pipeline of the pool's memory -- and the clock trace's sampler buffer (d_ck), which relies on hipFree's implicit device synchronisation."""
+import glob
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "nucleoatac_amd", "csrc", "natac_api.hip")
+CSRC = os.path.join(ROOT, "nucleoatac_amd", "csrc")
+SOURCES = [os.path.join(CSRC, "natac_api.hip")] + sorted(glob.glob(os.path.join(CSRC, "*.hpp")))
 
 
 def code_only(src):
@@ -13,6 +17,11 @@ def code_only(src):
         t = m.group(0)
         return t if t.startswith('"') else re.sub(r"[^\n]", " ", t)
     return re.sub(r'"(?:\\.|[^"\\\n])*"|//[^\n]*|/\*.*?\*/', blank, src, flags=re.S)
+
+
+def translation_unit():
+    """{file name: its code}"""
+    return {os.path.basename(p): code_only(open(p).read()) for p in SOURCES}
 
 
 def braced(code, head):
@@ -47,18 +56,42 @@ def calls(code, name):
             for m in re.finditer(r"(?<!void )\b%s\(([^()]*)\)" % name, code)]
 
 
+def uses(code, name):
+    """(line, the line's text) of every `name(`, whatever its arguments"""
+    lines = code.split("\n")
+    return [(n, lines[n - 1].strip()) for n in (code.count("\n", 0, m.start()) + 1 for m in re.finditer(r"\b%s\(" % name, code))]
+
+
+def owners(tu):
+    """{file name: spans of the code that may call the driver's allocator}: the pool and DevBuf"""
+    return {"natac_runtime.hpp": [pool_span(tu["natac_runtime.hpp"])],
+            "natac_bgzf_dev.hpp": [braced(tu["natac_bgzf_dev.hpp"], "struct DevBuf {")]}
+
+
 def test_pool_blocks_are_freed_only_by_their_owner():
-    code = code_only(open(SRC).read())
+    tu = translation_unit()
+    code = tu["natac_runtime.hpp"]
     pool = pool_span(code)
     owner = braced(code, "class PoolBuf {")
     assert [arg for _, arg in calls(code[slice(*owner)], "dev_free")] == ["p_"]      # reset(): the one way a block goes back
-    rest = outside(code, [pool, owner])
-    assert calls(rest, "dev_free") == [], "dev_free outside PoolBuf and the pool (line, argument)"
+    tu["natac_runtime.hpp"] = outside(code, [pool, owner])
+    stray = [(name, line, arg) for name, rest in tu.items() for line, arg in calls(rest, "dev_free")]
+    assert stray == [], "dev_free outside PoolBuf and the pool (file, line, argument)"
 
 
 def test_hip_free_only_in_pool_and_clock_trace():
-    code = code_only(open(SRC).read())
-    pool = pool_span(code)
-    assert len(calls(code[slice(*pool)], "hipFree")) >= 2          # the pool's own: trim and the uncached free
-    stray = [(line, arg) for line, arg in calls(outside(code, [pool]), "hipFree") if arg != "c->d_ck"]
-    assert stray == [], "hipFree outside the pool and the clock trace (line, argument)"
+    tu = translation_unit()
+    own = owners(tu)
+    pool = tu["natac_runtime.hpp"][slice(*own["natac_runtime.hpp"][0])]
+    assert len(calls(pool, "hipFree")) >= 2          # the pool's own: trim and the uncached free
+    assert len(uses(pool, "hipMalloc")) >= 2         # ... and the allocation with its retry after a trim
+    devbuf = tu["natac_bgzf_dev.hpp"][slice(*own["natac_bgzf_dev.hpp"][0])]
+    assert uses(devbuf, "hipMalloc") and uses(devbuf, "hipFree")      # DevBuf is an owner: it takes and returns its memory itself
+    stray = []
+    for name, code in tu.items():
+        rest = outside(code, own.get(name, []))
+        stray += [(name, line, arg) for line, arg in calls(rest, "hipFree") if arg != "c->d_ck"]
+        # every hipFree is seen by calls(): none has nested parentheses in its argument
+        assert len(calls(rest, "hipFree")) == len(uses(rest, "hipFree")), name
+        stray += [(name, line, text) for line, text in uses(rest, "hipMalloc") if "&c->d_ck" not in text]
+    assert stray == [], "hipFree / hipMalloc outside the pool, DevBuf and the clock trace (file, line, argument or text)"

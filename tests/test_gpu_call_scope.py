@@ -1,4 +1,4 @@
-"""The per-call device scope of natac_api.hip (DeviceCall: temporaries, copies, error latch, kernel timing, one finishing step)
+"""The per-call device scope of the library (DeviceCall, csrc/natac_runtime.hpp: temporaries, copies, error latch, kernel timing, one finishing step)
 through the entry points built on it, at the smallest shapes where the scope rather than a kernel can go wrong: empty and one-element
 inputs (the one-element allocation of an empty upload, skipped launches, the early returns), a call that fails after its device work
 followed at once by a call of another size on the same context (pool blocks recycled across the failure), kernel_ms with and without
