@@ -231,7 +231,12 @@ int natac_run_candidates(natac_batch *b, int64_t n_cand, const int32_t *cand_chu
  * (BASELINE configs[4]: "fp64 multinomial_cov path, tolerance sweep"; needs natac_run_nuc first).  Candidate k's probability
  * vector is SignalDistribution's p = B window / sum (NucleosomeCalling.py:70-76), v = the V-plot, r = int(nuc_cov[pos]) (:125).
  * mode 0 = closed form r (sum p v^2 - (sum p v)^2) in fp64 -- what natac_run_candidates reports; mode 1 = the .pyx's literal
- * O(N^2) pair sum in fp64; mode 2 = the closed form evaluated in fp32.  var[n_cand] on the host. */
+ * O(N^2) pair sum in fp64; mode 2 = the closed form evaluated in fp32.  var[n_cand] on the host.
+ * r is defined for every double a NUC_COV track can hold (natac_batch_set_track): the value truncated towards zero (0.99 and -0.5
+ * give 0 and var = +0, 7.9 gives 7, -1.5 gives -1), saturated at INT_MIN / INT_MAX beyond the range of `int` (3e9 counts as
+ * 2147483647), and a NaN coverage gives a NaN variance.  natac_run_candidates and natac_run_peaks form their var with the same r.
+ * Only NUC_COV is read of the batch: with a bias track whose margins are shorter than natac_run_nuc asks for, exp(bias) counts as 0
+ * outside the track (a window that lies outside it altogether gives NaN). */
 int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand_chunk, const int32_t *cand_pos, int mode,
                              double *var);
 /* Candidate search + statistics entirely on the device (needs natac_run_nuc first):

@@ -1414,7 +1414,7 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     }
     dc.fetch(reads.data(), d_r, (size_t)n_cand);
     if ((rc = dc.finish())) return rc;
-    for (int64_t k = 0; k < n_cand; ++k) var[k] = var[k] * (double)(int)reads[(size_t)k];
+    for (int64_t k = 0; k < n_cand; ++k) var[k] = var[k] * cov_reads(reads[(size_t)k]);
     return NATAC_OK;
 }
 

@@ -287,8 +287,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     const double nl = acc, ul = cntf * log(myB0V / tB);
     if (l == 0 && k0 + row < ncand) {
         const double m1 = tBV / tB;
-        const int reads = (int)nuc_cov[op];
-        const double var = (double)reads * (myBV2 / tB - m1 * m1);
+        const double var = cov_reads(nuc_cov[op]) * (myBV2 / tB - m1 * m1);
         out_lr[k0 + row] = myzero ? __builtin_nan("") : (nl - ul);
         out_var[k0 + row] = var;
         out_z[k0 + row] = norm[op] / sqrt(var);

@@ -43,6 +43,15 @@ struct VMatDev {
 
 __device__ __forceinline__ int floor_half(int x) { return x >> 1; }  // arithmetic shift == python x//2
 
+// r of calculateCov as a double: the .pyx's `int r` of nuc_cov[pos] (multinomial_cov.pyx:20, NucleosomeCalling.py:125), defined for every
+// double (natac.h): truncated towards zero, saturated at INT_MIN / INT_MAX, NaN stays NaN.  In range it is (double)(int)x, bit for bit.
+__host__ __device__ __forceinline__ double cov_reads(double x) {
+    if (x != x) return x;
+    const double t = x < 0 ? ceil(x) : floor(x);
+    if (t == 0.0) return 0.0;        // (double)(int)-0.5 is +0
+    return t < -2147483648.0 ? -2147483648.0 : (t > 2147483647.0 ? 2147483647.0 : t);
+}
+
 __device__ __forceinline__ int lower_bound_i32(const int *a, int lo, int hi, int key) {
     // first index in [lo,hi) with a[idx] >= key
     while (lo < hi) {
@@ -1535,8 +1544,7 @@ __global__ void __launch_bounds__(256) natac_candidates(ChunkTable ct, VMatDev v
         ul = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
         const long long o = ct.out_off[chunk] + p;
         const double m1 = sBV / sB;
-        const int reads = (int)nuc_cov[o];
-        const double var = (double)reads * (sBV2 / sB - m1 * m1);
+        const double var = cov_reads(nuc_cov[o]) * (sBV2 / sB - m1 * m1);
         out_lr[k] = zero ? __builtin_nan("") : (nl - ul);
         out_var[k] = var;
         out_z[k] = norm[o] / sqrt(var);
@@ -1769,8 +1777,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(USEBG 
         if (lane == 0 && k0 + q < ncand) {
             const long long o = ct.out_off[chunk[q]] + p;
             const double m1 = tBV / tB;
-            const int reads = (int)nuc_cov[o];
-            const double var = (double)reads * (tBV2 / tB - m1 * m1);
+            const double var = cov_reads(nuc_cov[o]) * (tBV2 / tB - m1 * m1);
             out_lr[k0 + q] = anyzero ? __builtin_nan("") : (nl - ul);
             out_var[k0 + q] = var;
             out_z[k0 + q] = norm[o] / sqrt(var);

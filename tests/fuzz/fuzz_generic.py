@@ -1,8 +1,10 @@
 """Randomised parity sweep over MODEL geometries (development / release check): per round a random V-plot (lower bound, even /
 odd row count, width), smoothing width, occupancy window / step / size range / alpha grid -- so the fallback kernels run
 (generic smoothing, natac_occ_mle, natac_candidates4, the FFT kernel's odd-row loop, natac_background_generic) -- on a
-few ragged chunks, against the CPU oracle.   usage: python tests/fuzz/fuzz_generic.py [n_rounds] [seed]"""
+few ragged chunks, against the CPU oracle; then the occupancy peak tail (natac_run_occ_peaks) and the variance sweep
+(natac_run_candidates_cov, three variants) on the same geometry.   usage: python tests/fuzz/fuzz_generic.py [n_rounds] [seed]"""
 import contextlib
+import copy
 import os
 import sys
 import time
@@ -72,10 +74,12 @@ def one_round(rng, par, ctx=None):
                                                L.T_OCC_LOWER, L.T_OCC_UPPER, L.T_OCC_COV)}
         kw = dict(min_signal=0, sep=25, boundary=w, order=10)
         cc, cp, lr, var, z = b.run_peaks(**kw)
+        nts = []
         for k, Lc in enumerate(lens):
             l, n = fr[k]
             try:
                 nt = O.nuc_chunk_tracks(l, n, 0, Lc, pk.chunk_bias(k), -BL, vm, vlo, vup, sizes[:vup], smooth_sd=sd)
+                nts.append(nt)
                 assert_track(tr[L.T_NUC_COV][k], nt["nuc_cov"], "nuc_cov", exact=True)
                 assert_track(tr[L.T_NFR_COV][k], nt["nfr_cov"], "nfr_cov", exact=True)
                 assert_track(tr[L.T_RAW][k], nt["raw"], "raw")
@@ -104,8 +108,65 @@ def one_round(rng, par, ctx=None):
                         assert abs(varv - ref_var) <= 1e-9 * max(1e-12, abs(ref_var)), ("var", varv, ref_var)
             except AssertionError as e:
                 raise AssertionError("%s | chunk %d | %r" % (e, k, desc))
+        # The peak-position families on the round's geometry.  Their choices come from a generator of their own, seeded by the value
+        # that follows the round's last draw -- read from a copy, so that the stream the next round draws from is what it was before
+        # these checks existed.
+        sub = np.random.default_rng(int(copy.deepcopy(rng).integers(1 << 62)))
+        try:
+            occ_peak_tail(b, sub, lens, fr, tr, st, flank, occ_up)
+            cov_sweep(b, sub, nts, vm, vlo, vup, w, cc, cp)
+        except AssertionError as e:
+            raise AssertionError("%s | %r" % (e, desc))
         b.free()
     return sum(lens)
+
+
+def occ_peak_tail(b, sub, lens, fr, tr, st, flank, occ_up):
+    """natac_run_occ_peaks with the round's flank and size range against OccChunk.callPeaks + getNucDist (Occupancy.py:225-240)
+    restated on the device's own tracks (tests/test_gpu_occ_peak_tail.py), as fuzz_parity.py does for the default geometry"""
+    from test_gpu_occ_peak_tail import _restate
+    min_occ = float(sub.choice([0.0, 0.1, 0.3]))
+    osep = int(sub.choice([60, 120]))
+    oc_c, oc_p, oc_occ, oc_lo, oc_up, oc_rd, oc_keep, nd = b.run_occ_peaks(min_occ=min_occ, sep=osep)
+    st2 = b.status()
+    occ = b.split(b.track(L.T_OCC))
+    assert nd.shape == (len(lens), occ_up)
+    for k in range(len(lens)):
+        if (st[k] & 1) or (st2[k] & 2):
+            continue
+        lov, upv, covv = tr[L.T_OCC_LOWER][k], tr[L.T_OCC_UPPER][k], tr[L.T_OCC_COV][k]
+        pk_, keep, ref_nd = _restate(occ[k], lov, covv, fr[k][0], fr[k][1], min_occ, osep, flank, occ_up)
+        m = oc_c == k
+        assert np.array_equal(oc_p[m], pk_), ("occ peaks", k, min_occ, osep, oc_p[m][:12], pk_[:12])
+        assert np.array_equal(oc_occ[m], occ[k][pk_]) and np.array_equal(oc_lo[m], lov[pk_], equal_nan=True) and \
+            np.array_equal(oc_up[m], upv[pk_], equal_nan=True) and np.array_equal(oc_rd[m], covv[pk_]), ("occ peak values", k)
+        assert np.array_equal(oc_keep[m].astype(bool), keep), ("occ keep", k)
+        assert np.array_equal(nd[k], ref_nd, equal_nan=True), ("nuc_dist", k, min_occ, osep)
+
+
+def cov_sweep(b, sub, nts, vm, vlo, vup, w, cc, cp):
+    """natac_run_candidates_cov in its three variants at up to 10 of the round's candidates against the oracle, with the bounds of
+    tests/test_gpu_cov_sweep_geometry.py.  Its relative tolerances hold while (S1 + S2^2) / (S1 - S2^2) <= 10; a random V-plot may pass
+    that, and the tolerance then grows in proportion (the errors are relative to S1 + S2^2, not to their difference)."""
+    if len(cc) == 0:
+        return
+    pick = np.sort(sub.choice(len(cc), size=min(10, len(cc)), replace=False))
+    kc, kp = cc[pick], cp[pick]
+    got = {m: b.run_candidates_cov(kc, kp, m) for m in ("literal", "closed", "fp32")}
+    v = np.ravel(vm)
+    for j, (k, p) in enumerate(zip(kc, kp)):
+        k, p = int(k), int(p)
+        r = nts[k]["nuc_cov"][p]
+        if int(r) <= 0:
+            assert got["literal"][j] == 0.0 and got["closed"][j] == 0.0 and got["fp32"][j] == 0.0, ("cov sweep without reads", k, p)
+            continue
+        pr = O.signal_distribution_probs(nts[k]["bmat"], nts[k]["b_start"], vlo, vup, w, p)
+        S1, S2 = float(np.sum(pr * v * v)), float(np.sum(pr * v))
+        slack = max(1.0, (S1 + S2 * S2) / (S1 - S2 * S2) / 10.0)
+        lit, clo = O.calculate_cov_literal(pr, v, r), O.calculate_cov_closed(pr, v, r)
+        assert abs(got["literal"][j] - lit) <= 1e-10 * slack * abs(lit), ("cov literal", k, p, got["literal"][j], lit)
+        assert abs(got["closed"][j] - clo) <= 1e-9 * slack * abs(clo), ("cov closed", k, p, got["closed"][j], clo)
+        assert abs(got["fp32"][j] - clo) <= (v.size + 8) * 2.0 ** -24 * int(r) * (S1 + 2 * S2 * S2), ("cov fp32", k, p, got["fp32"][j], clo)
 
 
 def main():
