@@ -52,9 +52,9 @@ extern "C" {
  * 9: added natac_frag_open / natac_frag_open_device for fragment files; 10: added natac_frag_split / natac_frag_split_device; 11: added
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
- * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`);
- * the binding refuses another version */
-#define NATAC_ABI_VERSION 14
+ * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
+ * 15: added natac_enriched_regions for `pyatac peaks`); the binding refuses another version */
+#define NATAC_ABI_VERSION 15
 
 enum {
     NATAC_OK = 0,
@@ -395,6 +395,37 @@ int natac_cell_site_qc(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, cons
                        int64_t n_sites, const int64_t *site_center, const uint8_t *site_minus, int flank, int center, int edge,
                        int64_t n_peaks, const int64_t *peak_start, const int64_t *peak_end, int64_t *tss_center, int64_t *tss_flank,
                        int64_t *in_peaks, int64_t *profile, double *kernel_ms);
+/* ---- the enriched regions of one chromosome (this library's own; `pyatac peaks`) ----
+ * pos / tlen as natac_region_counts takes them (pos non-decreasing), chrom_len = n the chromosome's length.  EVERY record gives two
+ * insertions, l = pos + 4 and r = pos + tlen - 5; there is no size filter; an insertion outside [0, n) is dropped on its own.  ins[x] is the
+ * number of insertions at base x and C_w(x) the sum of ins[y] over |y - x| <= w, 0 <= y < n (the window is clipped at the ends).
+ *   p(x) = C_half_width(x), s(x) = C_small(x), g(x) = C_large(x), 1 <= half_width <= small <= large <= NATAC_PEAKS_MAX_WINDOW.
+ *   Base x is significant when p(x) >= min_pileup, s(x) <= thr_small[k] and g(x) <= thr_large[k], k = min(p(x), n_table - 1): the two
+ *   int32 tables [n_table >= 2] and min_pileup >= 1 are all the statistics the device sees (the caller derives them from Poisson critical
+ *   values; a negative entry admits nothing).
+ *   Significant bases with at most max_gap >= 0 others between them are one region [first significant base, last + 1); a region shorter
+ *   than min_length >= 1 is dropped.  summit = (a + b) / 2 with a / b the first / last base of the region where p is largest.
+ * Per kept region, ascending: start, end, summit, pileup = p(summit), n_small = s(summit), n_large = g(summit).  *n_regions = the number
+ * of kept regions; if that is more than capacity, the six arrays stay as they were and the caller comes again with room (nothing is ever
+ * cut short).  n_found (may be NULL) = the regions before the length rule, n_significant (may be NULL) = the significant bases.
+ * Refused (NATAC_E_ARG, every output untouched): unsorted pos and the other findings of the fragment check, a parameter outside the rules
+ * above, NULL tables, n_table < 2, chrom_len < 1 or >= 2^31, n_frags >= 2^30.  With no records nothing is launched and the counts are 0.
+ * The chromosome is worked through in segments of NATAC_PEAKS_SEGMENT bases (environment; default NATAC_PEAKS_SEGMENT_DEFAULT) with
+ * halos of `large` bases, 21 bytes of device memory per base of a segment; the result does not depend on the segment size (a region
+ * across borders is joined by a carried last significant base and by 64-bit atomic maxima of packed (p, base) keys).  The first sweep has
+ * room for NATAC_PEAKS_FIRST_CAPACITY region starts and is run again with the counted number if there are more.  A region's piece of at
+ * most NATAC_PEAKS_SHORT_MAX bases in a segment is searched by one wave, a longer one by a workgroup.  Only integer arithmetic and integer
+ * atomics run on the device: the result is a pure function of the inputs (csrc/natac_peakcall.hpp).  kernel_ms (may be NULL): device time
+ * from the first to the last kernel of the call, the host's steps between the sweeps included; written only behind the checks. */
+#define NATAC_PEAKS_MAX_WINDOW 50000
+#define NATAC_PEAKS_SEGMENT_DEFAULT 4194304
+#define NATAC_PEAKS_SHORT_MAX 2048
+#define NATAC_PEAKS_FIRST_CAPACITY 4096
+int natac_enriched_regions(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, int64_t chrom_len, int half_width,
+                           int small, int large, int max_gap, int min_length, int min_pileup, int32_t n_table, const int32_t *thr_small,
+                           const int32_t *thr_large, int64_t *n_regions, int64_t capacity, int64_t *start, int64_t *end, int64_t *summit,
+                           int32_t *pileup, int32_t *n_small, int32_t *n_large, int64_t *n_found, int64_t *n_significant,
+                           double *kernel_ms);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

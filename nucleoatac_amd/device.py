@@ -427,6 +427,39 @@ class Context(object):
         res = (out[0], out[1], out[2], profile)
         return res + (ms.value,) if with_kernel_ms else res
 
+    def enriched_regions(self, pos, tlen, chrom_len, thr_small, thr_large, min_pileup, half_width=75, small=500, large=5000, max_gap=75,
+                         min_length=150, capacity=None, with_kernel_ms=False, with_counts=False):
+        """the enriched regions of one chromosome (natac_enriched_regions; include/natac.h states the rule): (start, end, summit int64,
+        pileup, n_small, n_large int32) of the kept regions in ascending order, exact.  pos (sorted) / tlen as region_counts takes them;
+        every record counts with its two insertions l = pos + 4 and r = pos + tlen - 5, each dropped on its own outside [0, chrom_len).
+        A base is significant when its pileup p (insertions within half_width) is at least min_pileup and its counts within small and
+        large are at most thr_small[k] and thr_large[k], k = min(p, len(thr_small) - 1); significant bases at most max_gap apart are one
+        region, one shorter than min_length is dropped.  capacity: the room of the first call (default 4096); a call that finds more
+        is made again with room for all.  with_counts: also (regions before the length rule, significant bases); with_kernel_ms: also
+        the device time of the calls' kernels."""
+        p = np.ascontiguousarray(pos, dtype=np.int64)
+        t = np.ascontiguousarray(tlen, dtype=np.int64)
+        ts = np.ascontiguousarray(thr_small, dtype=np.int32)
+        tl = np.ascontiguousarray(thr_large, dtype=np.int32)
+        if p.ndim != 1 or p.shape != t.shape or ts.ndim != 1 or ts.shape != tl.shape:
+            raise ValueError("pos / tlen and thr_small / thr_large must be 1-d arrays of one length each")
+        cap = 4096 if capacity is None else max(int(capacity), 0)
+        n, found, nsig, ms, total_ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_double(0), 0.0
+        while True:
+            out = [np.zeros(max(cap, 1), dtype=np.int64) for _ in range(3)] + [np.zeros(max(cap, 1), dtype=np.int32) for _ in range(3)]
+            L.check(self._lib.natac_enriched_regions(self._h, p.shape[0], _ptr(p), _ptr(t), int(chrom_len), int(half_width), int(small),
+                                                     int(large), int(max_gap), int(min_length), int(min_pileup), ts.shape[0], _ptr(ts),
+                                                     _ptr(tl), C.byref(n), cap, *[_ptr(o) for o in out], C.byref(found), C.byref(nsig),
+                                                     C.byref(ms)))
+            total_ms += ms.value
+            if n.value <= cap:
+                break
+            cap = int(n.value)
+        res = tuple(o[:n.value].copy() for o in out)
+        if with_counts:
+            res += (int(found.value), int(nsig.value))
+        return res + (total_ms,) if with_kernel_ms else res
+
     def site_seq_counts(self, seq, centers, minus, up, down, word=1, with_kernel_ms=False):
         """word counts of `pyatac nucleotide` (_nucleotideHelper, pyatac/get_nucleotide.py:19-38) around the sites of one chromosome:
         (M int64[4 or 16, up + down + 1], n = the sites whose window lies inside the chromosome), exact.  seq: the chromosome's bytes,

@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | peaks` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -11,7 +11,10 @@ discovers the barcodes of a single-cell fragment file with per-cell fragment cou
 thresholds, which `split --groups` and `cellcounts --cells` take unchanged.  `cellqc`, this package's own too, stands between them: for
 the barcodes of such a table it gives per-cell TSS enrichment (insertions around a BED of transcription start sites, with the aggregate
 profile) and FRiP (the fraction of a cell's fragments in a BED of peaks), and writes the table of the cells that pass the user's thresholds
-on those.  The other pyatac tools (vplot, bias_vplot) are not part of
+on those.  `peaks`, this package's own as well, makes the peak set the other commands take (`counts --bed`, `cellqc --peaks`, `cellcounts
+--bed`, `nucleoatac run --bed`) from nothing but the fragments: regions whose insertion pileup is improbable at the genome-wide and at
+two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windows of one width; run per cell group behind `split`, it is
+the last link before `nucleoatac run`.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -184,13 +187,33 @@ def add_cellcounts_parser(sub):
                    help="BASE.cellcounts.mtx.gz with .barcodes.tsv and .regions.bed (default) or BASE.cellcounts.npz (CSR arrays)")
 
 
+def add_peaks_parser(sub):
+    p = sub.add_parser("peaks", help="call enriched regions (peaks) from the insertions of a fragment store")
+    p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
+    p.add_argument("--fasta", metavar="fasta_file", help="Chromosome lengths from this FASTA (or FastaStore .npz)")
+    p.add_argument("--sizes", metavar="genome_sizes_file", help="Chromosome lengths from this file (names in 1st col, sizes in 2nd). "
+                                                                "Without --fasta and --sizes the lengths are those of the reads' source")
+    p.add_argument("--out", metavar="basename", help="Basename for output")
+    p.add_argument("--half_width", metavar="int", default=75, type=int, help="Half-width of the pileup window. Default is 75")
+    p.add_argument("--small", metavar="int", default=500, type=int, help="Half-width of the small local window. Default is 500")
+    p.add_argument("--large", metavar="int", default=5000, type=int, help="Half-width of the large local window. Default is 5000")
+    p.add_argument("--mlog10p", metavar="float", default=5.0, type=float,
+                   help="A base is significant when its pileup has a Poisson tail probability of at most 10^-this. Default is 5")
+    p.add_argument("--max_gap", metavar="int", default=75, type=int,
+                   help="Significant bases with at most this many others between them are one region. Default is 75")
+    p.add_argument("--min_length", metavar="int", default=150, type=int, help="Regions shorter than this are dropped. Default is 150")
+    p.add_argument("--fixed_width", metavar="int", default=None, type=int,
+                   help="Also write disjoint windows of this width around the summits, the most significant first")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
                                                                 "insertion, coverage and Tn5 bias tracks, fragment counts per window, "
                                                                 "nucleotide content and track signal around sites; a single-cell fragment file "
                                                                 "split by cell group, its cell-by-window count matrix, the discovery "
-                                                                "of its cells and their TSS enrichment and fraction of fragments in peaks")
+                                                                "of its cells and their TSS enrichment and fraction of fragments in peaks; "
+                                                                "enriched regions (peaks) of a fragment store")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -206,6 +229,7 @@ def pyatac_parser():
     add_cellqc_parser(sub)
     add_split_parser(sub)
     add_cellcounts_parser(sub)
+    add_peaks_parser(sub)
     return parser
 
 
@@ -313,6 +337,15 @@ def pyatac_main(args):
             get_cellcounts(args)
         except (CountsError, BedColumnError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac cellcounts: %s\n" % e)
+            return 1
+    elif args.call == "peaks":
+        from .._lib import NatacError
+        from .get_peaks import PeaksError, get_peaks
+        print("---------Calling enriched regions---------------------------------------")
+        try:
+            get_peaks(args)
+        except (PeaksError, NatacError) as e:
+            sys.stderr.write("pyatac peaks: %s\n" % e)
             return 1
     return 0
 
