@@ -286,6 +286,8 @@ int natac_batch_status(natac_batch *b, int32_t *dst, size_t dst_bytes);
 int natac_batch_track_ptr(natac_batch *b, int track, void **dptr);
 
 /* ---- drop-in replacements of the Cython functions (host buffers in / out, synchronous) --- */
+/* n_frags < 0 is refused (NATAC_E_ARG, "negative size") before any device work by the four fragment calls below; an insert size may
+ * be zero or negative wherever [lower, upper) admits it (its right end is l + n - 1, its centre l + floor((n - 1) / 2)). */
 /* makeFragmentMat, pyatac/fragments.pyx:17-40: mat[(upper-lower) x (end-start)] float64, zeroed + filled. */
 int natac_make_fragment_mat(natac_ctx *ctx, int64_t n_frags, const int64_t *l, const int32_t *n, int64_t start,
                             int64_t end, int lower, int upper, double *mat);
@@ -297,7 +299,8 @@ int natac_get_insertions(natac_ctx *ctx, int64_t n_frags, const int64_t *l, cons
 int natac_get_stranded_insertions(natac_ctx *ctx, int64_t n_frags, const int64_t *l, const int32_t *n, int64_t start,
                                   int64_t end, int lower, int upper, double *plus, double *minus);
 /* getFragmentSizesFromChunkList, pyatac/fragments.pyx:123-145 (one chromosome's fragments, its chunks):
- * sizes[upper-lower] float64 counts (not normalised). */
+ * sizes[upper-lower] float64 counts (not normalised).  lower may be negative: a size in [lower, 0) is counted into bin size - lower
+ * like any other.  At most 1 << 20 bins. */
 int natac_fragment_sizes(natac_ctx *ctx, int64_t n_frags, const int64_t *l, const int32_t *n, int32_t n_chunks,
                          const int64_t *chunk_start, const int64_t *chunk_end, int lower, int upper, double *sizes);
 /* calculateCov, nucleoatac/multinomial_cov.pyx:20-31.  mode 0 = closed form O(N), mode 1 = literal O(N^2)
@@ -307,11 +310,14 @@ int natac_calculate_cov(natac_ctx *ctx, const double *p, const double *v, int64_
 /* ---- operator-level entry points behind the Track / BiasMat2D / bias / occupancy classes ------ */
 /* utils.smooth, pyatac/utils.py:23-52, on one host array.  w[M] is the window (ones for 'flat', scipy's
  * gaussian(M, sd) otherwise; M odd).  mode 0 = 'valid' (out[n-M+1]), 1 = 'same' (out[n], needs n >= M).
- * norm != 0: NaN-aware normalisation (0 weight -> NaN). */
+ * norm != 0: NaN-aware normalisation (0 weight -> NaN).  Orientation: np.convolve(w, x), so out[t] = sum_k w[k] * x[t + M-1 - k]
+ * ('valid'; 'same' has (M-1)/2 in place of M-1 and skips taps outside x): w[0] meets the rightmost value under the window.  An even M
+ * and n < M are refused (NATAC_E_ARG). */
 int natac_smooth(natac_ctx *ctx, const double *x, int64_t n, const double *w, int M, int mode, int norm, double *out);
 /* BiasMat2D.makeBiasMat, pyatac/chunkmat2d.py:140-153 (log-scale track): mat[(upper-lower) x (end-start)].
- * bias_log[nb] starts at genomic coordinate track_start; returns NATAC_E_ARG if the track does not cover
- * [start - upper//2, end + upper//2). */
+ * bias_log[nb] starts at genomic coordinate track_start; returns NATAC_E_ARG if the track does not cover every cell that a row
+ * i in [lower, upper) reads, start + x - (i-1)//2 and start + x + i//2 (the message names the sufficient [start - upper//2,
+ * end + upper//2)).  nb < 0 is refused ("negative size") before any device work. */
 int natac_make_bias_mat(natac_ctx *ctx, const double *bias_log, int64_t nb, int64_t track_start, int64_t start,
                         int64_t end, int lower, int upper, double *mat);
 /* InsertionBiasTrack.computeBias, pyatac/bias.py:85-92: seq[n] (upper-case ASCII) covers [start-up, end+down);

@@ -15,6 +15,7 @@ int natac_make_fragment_mat(natac_ctx *c, int64_t nf, const int64_t *l, const in
                             int upper, double *mat) {
     if (!c || !mat || (nf > 0 && (!l || !n))) return fail(NATAC_E_ARG, "null argument");
     if (end <= start || upper <= lower) return fail(NATAC_E_ARG, "empty matrix");
+    if (nf < 0) return fail(NATAC_E_ARG, "negative size");
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
     DeviceCall dc(c, "make_fragment_mat");
@@ -34,6 +35,7 @@ int natac_make_fragment_mat(natac_ctx *c, int64_t nf, const int64_t *l, const in
 int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32_t *n, int64_t start, int64_t end, int lower,
                          int upper, double *out) {
     if (!c || !out || (nf > 0 && (!l || !n))) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0) return fail(NATAC_E_ARG, "negative size");
     if (end <= start) return fail(NATAC_E_ARG, "empty region");
     const long long npos = end - start;
     if (npos > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");
@@ -59,6 +61,7 @@ int natac_get_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32
 int natac_get_stranded_insertions(natac_ctx *c, int64_t nf, const int64_t *l, const int32_t *n, int64_t start, int64_t end, int lower,
                                   int upper, double *plus, double *minus) {
     if (!c || !plus || !minus || (nf > 0 && (!l || !n))) return fail(NATAC_E_ARG, "null argument");
+    if (nf < 0) return fail(NATAC_E_ARG, "negative size");
     if (end <= start) return fail(NATAC_E_ARG, "empty region");
     const long long npos = end - start;
     if (npos > 0x3fffffffLL) return fail(NATAC_E_ARG, "region too long");
@@ -173,6 +176,7 @@ int natac_smooth(natac_ctx *c, const double *x, int64_t n, const double *w, int 
 int natac_make_bias_mat(natac_ctx *c, const double *bias_log, int64_t nb, int64_t track_start, int64_t start, int64_t end,
                         int lower, int upper, double *mat) {
     if (!c || !bias_log || !mat) return fail(NATAC_E_ARG, "null argument");
+    if (nb < 0) return fail(NATAC_E_ARG, "negative size");
     if (end <= start || upper <= lower || lower < 0) return fail(NATAC_E_ARG, "empty matrix");
     const long long ncol = end - start, nrow = upper - lower;
     if (ncol > 0x7fffffffLL) return fail(NATAC_E_ARG, "region too long");

@@ -2308,6 +2308,7 @@ __global__ void natac_i32_to_f64(const int *__restrict__ a, double *__restrict__
 // global atomic per non-empty bin at the end (lh == nullptr: bins too many for LDS, global atomics directly).
 constexpr int SIZE_SEG = 2048;     // fragments per segment (8 per thread)
 constexpr int SIZE_STAGE = 1024;   // staged chunk starts / ends per segment
+constexpr int SIZE_NONE = -0x7fffffff - 1;   // il[] mark of a slot that is not counted (lower may be negative, so -1 is a size; INT_MIN has no ilen - 1)
 
 __device__ __forceinline__ int upper_bound_i64(const long long *a, int lo, int hi, long long key) {
     // number of entries <= key in the sorted array a[0, hi), searching from lo
@@ -2340,7 +2341,7 @@ __global__ void __launch_bounds__(256) natac_size_hist(const long long *__restri
 #pragma unroll
         for (int q = 0; q < SIZE_SEG / 256; ++q) {
             const long long i = seg * SIZE_SEG + q * 256 + threadIdx.x;
-            il[q] = -1;
+            il[q] = SIZE_NONE;
             c[q] = 0;
             if (i < nf) {
                 const int ilen = n[i];
@@ -2370,7 +2371,7 @@ __global__ void __launch_bounds__(256) natac_size_hist(const long long *__restri
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < SIZE_SEG / 256; ++q) {
-            if (il[q] < 0) continue;
+            if (il[q] == SIZE_NONE) continue;
             int a, b;
             if (staged) {
                 a = s0 + upper_bound_i64(ss, 0, s1 - s0, c[q]);

@@ -514,6 +514,9 @@ class Context(object):
     def calculate_occupancy(self, inserts, bias):
         """calculateOccupancy (nucleoatac/Occupancy.py:104-120) with the model of set_occ_model."""
         ins, b = _f64(inserts), _f64(bias)
+        upper = getattr(self, "occ_upper", None)
+        if upper is not None and (ins.shape != (upper,) or b.shape != (upper,)):    # the C entry reads occ_upper values of each
+            raise ValueError("inserts and bias must each hold the model's %d values (got %s and %s)" % (upper, ins.shape, b.shape))
         out = np.empty(3, dtype=np.float64)
         rc = self._lib.natac_calculate_occupancy(self._h, _ptr(ins), _ptr(b), _ptr(out))
         if rc == -1 and b"likelihood-ratio" in self._lib.natac_last_error():

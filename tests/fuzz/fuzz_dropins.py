@@ -1,6 +1,7 @@
 """Randomised sweep over the single-region drop-ins (the Cython functions' replacements and the operator-level helpers) against
-the CPU oracle: makeFragmentMat, getInsertions, getFragmentSizesFromChunkList, calculateCov (closed + literal), smooth in
+the CPU oracle: makeFragmentMat, getInsertions, getStrandedInsertions, getFragmentSizesFromChunkList, calculateCov (closed + literal), smooth in
 every mode, makeBiasMat, the PWM score, correlate 'valid', calculateOccupancy.   usage: python tests/fuzz/fuzz_dropins.py [rounds] [seed]"""
+import copy
 import os
 import sys
 import time
@@ -34,6 +35,19 @@ def one_round(c, rng):
     upper = lower + int(rng.integers(1, 300))
     assert np.array_equal(c.make_fragment_mat(l, n, start, end, lower, upper), O.make_fragment_mat(l, n, start, end, lower, upper))
     assert np.array_equal(c.get_insertions(l, n, start, end, lower, upper), O.get_insertions(l, n, start, end, lower, upper))
+    plus, minus = c.get_stranded_insertions(l, n, start, end, lower, upper)
+    ref_plus, ref_minus = O.get_stranded_insertions(l, n, start, end, lower, upper)
+    assert np.array_equal(plus, ref_plus) and np.array_equal(minus, ref_minus)
+    # the same two calls under limits of their own, which may be negative.  Drawn from a generator seeded from a copy of the round's, so
+    # that the stream the rest of the round draws from is what it was before this check existed.
+    sub = np.random.default_rng(int(copy.deepcopy(rng).integers(1 << 62)))
+    lo3 = int(sub.integers(-20, 120))
+    up3 = lo3 + int(sub.integers(1, 700))
+    n3 = n - int(sub.integers(0, 30))
+    plus, minus = c.get_stranded_insertions(l, n3, start, end, lo3, up3)
+    ref_plus, ref_minus = O.get_stranded_insertions(l, n3, start, end, lo3, up3)
+    assert np.array_equal(plus, ref_plus) and np.array_equal(minus, ref_minus)
+    assert np.array_equal(c.get_insertions(l, n3, start, end, lo3, up3), plus + minus)
     # size histogram over a random (overlapping / empty / unsorted) chunk list
     nch = int(rng.integers(1, 40))
     cs = rng.integers(start - 800, end + 800, size=nch).astype(np.int64)
