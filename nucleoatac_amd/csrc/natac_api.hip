@@ -108,9 +108,18 @@ static void launch_candidates(natac_ctx *c, const ChunkTable &ct, const VMatDev 
             c->lrt_gen = c->model_gen;
         }
     }
+    if (paired && (c->ctab_gen != c->model_gen || !c->d_ctab)) {    // the sweep's template stream, likewise (natac_cand_table)
+        const size_t nd = cand_table_doubles(c->R);
+        if (c->d_ctab.size() < nd && dev_alloc(c->d_ctab, nd) != NATAC_OK) paired = false;
+        if (paired) {
+            hipLaunchKernelGGL(natac_cand_table, dim3((unsigned)((nd / 2 + 255) / 256)), dim3(256), 0, c->stream, c->d_vmat, c->R, c->W, c->d_ctab);
+            c->ctab_gen = c->model_gen;
+        }
+    }
     if (paired) {
         VMatDev vml = vm;
         vml.lrt = c->d_lrt;
+        vml.ctab = c->d_ctab;
         const long long per_block = 4 * CAND_PER_WAVE;
         const dim3 grid((unsigned)((n + per_block - 1) / per_block));
         if (c->vlower & 1)
@@ -582,6 +591,7 @@ static VMatDev make_vmat(natac_ctx *c) {
     v.mat = c->d_vmat; v.matp = c->d_vmat_pad; v.srow = c->d_srow; v.lower = c->vlower; v.upper = c->vupper; v.w = c->vw; v.R = c->R; v.W = c->W;
     v.has_zero = (c->vmat_zero || c->srow_zero) ? 1 : 0;
     v.lrt = nullptr;
+    v.ctab = nullptr;
     return v;
 }
 static OccModelDev make_occ(natac_ctx *c) {

@@ -50,6 +50,29 @@ __global__ void __launch_bounds__(256) natac_lr_table(const double *__restrict__
     if (i < R * W) out[i] = log(vmat[i] / srow[i / W]);
 }
 
+// The sweep's template stream (formed once per V-plot, like natac_lr_table): the values a lane multiplies, in the order the sweep
+// loads them.  Pair k (rows 2k, 2k+1) is two 1 KiB halves, row a then row b; lane l's 16 bytes of a half hold the row's values at
+// column l and at column l + 64 -- +0.0 where l + 64 >= W, which is what the sweep's `0.0 * v` gave a lane without a second column
+// (and its weight s * (v * v) is then s * (0 * 0) as before).  Every load of the sweep is so one contiguous KiB over the wave at an
+// immediate offset from one running address.  CAND_TAB_PAD zero pairs follow the last one: the sweep requests its values two pairs
+// ahead without a bound check.
+constexpr int CAND_TAB_PAD = 2;
+constexpr int CAND_TAB_PAIR = WAVE * 4;                         // doubles per pair
+__host__ __device__ constexpr size_t cand_table_doubles(int R) { return (size_t)((R >> 1) + CAND_TAB_PAD) * CAND_TAB_PAIR; }
+__global__ void __launch_bounds__(256) natac_cand_table(const double *__restrict__ vmat, int R, int W, double *__restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;              // (pair, row of the pair, lane)
+    const int k = i >> 7, row = (i >> 6) & 1, l = i & 63;
+    if (k >= (R >> 1) + CAND_TAB_PAD) return;
+    double v0 = 0.0, v1 = 0.0;
+    if (k < (R >> 1)) {
+        const double *r = vmat + (size_t)(2 * k + row) * W;
+        v0 = r[l];
+        if (l + WAVE < W) v1 = r[l + WAVE];
+    }
+    out[(size_t)i * 2] = v0;
+    out[(size_t)i * 2 + 1] = v1;
+}
+
 constexpr int CANDP_STRIDE = 376;   // doubles per candidate window in LDS (compile-time: every LDS address of the sweep is a
                                     // running base register + an immediate); V-plots with W + upper - 2 > 376 use natac_candidates4
 
@@ -109,35 +132,42 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     }
     const double *__restrict__ vmat = vm.mat;
     const int npair = R >> 1;
-    // running LDS pointers of the two columns: shared factor (moves by -1 / +1 per pair) and new other factor (+1 / -1)
-    const double *psh1 = Ew + c1 + (LODD ? A - m0 : A + m0), *psh2 = Ew + c2 + (LODD ? A - m0 : A + m0);
-    const double *pnw1 = Ew + c1 + (LODD ? A + m0 + 1 : A - m0), *pnw2 = Ew + c2 + (LODD ? A + m0 + 1 : A - m0);
+    // running LDS indices of the two columns: shared factor (moves by -1 / +1 per pair) and new other factor (+1 / -1).  Inside a
+    // four-pair trip pair j reads at the compile-time offset j * D from the trip's lowest position, so a trip moves each index once
+    // and every LDS address of the sweep is one register + an immediate.  (Opaque to the compiler, which otherwise splits each
+    // into a wave base and a running part and adds the two again for every pair.)
     constexpr int DSH = LODD ? -1 : 1, DNW = LODD ? 1 : -1;
-    // template values and size weights of pair k (rows 2k, 2k+1), requested one trip ahead of their use: the L2 round trip of
-    // these loads is as long as the arithmetic of a trip and three waves per SIMD do not hide it
+    constexpr int BSH = DSH < 0 ? 3 : 0, BNW = DNW < 0 ? 3 : 0;      // the trip's first position, from its lowest one
+    const int ew0 = wave * Q * EWP;
+    int ish1 = ew0 + c1 + (LODD ? A - m0 : A + m0) - BSH, ish2 = ew0 + c2 + (LODD ? A - m0 : A + m0) - BSH;
+    int inw1 = ew0 + c1 + (LODD ? A + m0 + 1 : A - m0) - BNW, inw2 = ew0 + c2 + (LODD ? A + m0 + 1 : A - m0) - BNW;
+    asm("" : "+v"(ish1), "+v"(ish2), "+v"(inw1), "+v"(inw2));
+    // template values of pair k (rows 2k, 2k+1) from the stream of natac_cand_table and the rows' size weights, requested two pairs
+    // ahead of their use: the L2 round trip of these loads is as long as the arithmetic of a pair and three waves per SIMD do not
+    // hide it.  A pair is 2048 bytes and a load's immediate reaches -4096 .. 4095: one running 32-bit offset beside the table's uniform
+    // base, standing at pair k + 4, serves the four requests of a trip (pairs k + 2 .. k + 5).  The weights s_r v^2 stay here: a stream
+    // that also carries them doubles the bytes every wave pulls through the CU's vector cache, and measured slower (EXPERIMENTS 8).
     struct PairT { double va0, va1, vb0, vb1, sa, sb; };
-    const double hm = h2 ? 1.0 : 0.0;                          // idle second column: clamped (valid) address, zero template
-    const unsigned o1 = (unsigned)c1 * 8u, o2 = (unsigned)c2 * 8u;      // byte offsets of the lane's two template columns
-    auto load_pair = [&](int k) {
-        PairT t;
-        t.sa = vm.srow[2 * k]; t.sb = vm.srow[2 * k + 1];
-        // uniform row base + the lane's byte offset (forcing the scalar-base form of the load -- an opaque 32-bit offset next to it --
-        // costs more in moves than the 64-bit address adds it saves: measured 2.25 against 2.19 ms per 20 k chunks)
-        const char *ra = (const char *)(vmat + (size_t)(2 * k) * (size_t)W), *rb = ra + (size_t)W * sizeof(double);
-        t.va0 = *(const double *)(ra + o1); t.va1 = *(const double *)(ra + o2);
-        t.vb0 = *(const double *)(rb + o1); t.vb1 = *(const double *)(rb + o2);
-        return t;
+    constexpr int PAIRB = CAND_TAB_PAIR * (int)sizeof(double);
+    const char *ctab = (const char *)vm.ctab;
+    unsigned vo = (unsigned)lane * 16u + 4u * PAIRB;
+    asm("" : "+v"(vo));
+    auto load_pair = [&](int kk, int imm) {                      // kk: the pair (clamped: srow has no padding), imm: its offset from vo
+        const double2 *p = (const double2 *)(ctab + (size_t)vo + (ptrdiff_t)imm);
+        const double2 a = p[0], b = p[WAVE];
+        return PairT{a.x, a.y, b.x, b.y, vm.srow[2 * kk], vm.srow[2 * kk + 1]};
     };
-    // one pair: row a multiplies the carried factor `cin`, row b the newly read one, which is handed on in `cout`
-    auto pair_step = [&](const PairT &t, const double (&cin)[Q][2], double (&cout)[Q][2]) {
-        const double va0 = t.va0, va1 = hm * t.va1, vb0 = t.vb0, vb1 = hm * t.vb1;
+    // one pair: row a multiplies the carried factor `cin`, row b the newly read one, which is handed on in `cout`; osh / onw: the
+    // pair's offsets from the running indices
+    auto pair_step = [&](const PairT &t, const double (&cin)[Q][2], double (&cout)[Q][2], auto osh, auto onw) {
+        const double va0 = t.va0, va1 = t.va1, vb0 = t.vb0, vb1 = t.vb1;
         const double wa0 = t.sa * (va0 * va0), wa1 = t.sa * (va1 * va1);     // weights of S_BV2: s_r v^2
         const double wb0 = t.sb * (vb0 * vb0), wb1 = t.sb * (vb1 * vb1);
         double s0[Q], s1[Q];
 #pragma unroll
         for (int q = 0; q < Q; ++q) {                          // all 16 LDS operands of the step are requested before the arithmetic
-            s0[q] = psh1[q * EWP]; s1[q] = psh2[q * EWP];
-            cout[q][0] = pnw1[q * EWP]; cout[q][1] = pnw2[q * EWP];
+            s0[q] = smem[ish1 + (q * EWP + osh)]; s1[q] = smem[ish2 + (q * EWP + osh)];
+            cout[q][0] = smem[inw1 + (q * EWP + onw)]; cout[q][1] = smem[inw2 + (q * EWP + onw)];
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -148,32 +178,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
             a2[q][0] = fma(s0[q], fma(wb0, n0, wa0 * cin[q][0]), a2[q][0]);
             a2[q][1] = fma(s1[q], fma(wb1, n1, wa1 * cin[q][1]), a2[q][1]);
         }
-        psh1 += DSH; psh2 += DSH; pnw1 += DNW; pnw2 += DNW;
     };
+#define NATAC_OFF(J, B, D) std::integral_constant<int, (B) + (J) * (D)>{}
     double carry2[Q][2];
     int k = 0;
-    PairT t0 = load_pair(0), t1 = load_pair(min(1, npair - 1));
+    PairT t0 = load_pair(0, -4 * PAIRB), t1 = load_pair(min(1, npair - 1), -3 * PAIRB);
     // four pairs per trip: two sets of template registers take turns and are loaded directly -- with two pairs per trip the prefetched
     // values were copied into place, 8 v_mov_b64 per trip (9.5 -> 9.0 ms per configs[2] step)
     for (; k + 4 <= npair; k += 4) {
-        const PairT u0 = load_pair(min(k + 2, npair - 1));
-        pair_step(t0, carry, carry2);
-        const PairT u1 = load_pair(min(k + 3, npair - 1));
-        pair_step(t1, carry2, carry);
-        t0 = load_pair(min(k + 4, npair - 1));
-        pair_step(u0, carry, carry2);
-        t1 = load_pair(min(k + 5, npair - 1));
-        pair_step(u1, carry2, carry);
+        const PairT u0 = load_pair(min(k + 2, npair - 1), -2 * PAIRB);
+        pair_step(t0, carry, carry2, NATAC_OFF(0, BSH, DSH), NATAC_OFF(0, BNW, DNW));
+        const PairT u1 = load_pair(min(k + 3, npair - 1), -PAIRB);
+        pair_step(t1, carry2, carry, NATAC_OFF(1, BSH, DSH), NATAC_OFF(1, BNW, DNW));
+        t0 = load_pair(min(k + 4, npair - 1), 0);
+        pair_step(u0, carry, carry2, NATAC_OFF(2, BSH, DSH), NATAC_OFF(2, BNW, DNW));
+        t1 = load_pair(min(k + 5, npair - 1), PAIRB);
+        pair_step(u1, carry2, carry, NATAC_OFF(3, BSH, DSH), NATAC_OFF(3, BNW, DNW));
+        ish1 += 4 * DSH; ish2 += 4 * DSH; inw1 += 4 * DNW; inw2 += 4 * DNW;
+        vo += 4u * PAIRB;
     }
+    ish1 += BSH; ish2 += BSH; inw1 += BNW; inw2 += BNW;         // the tails read at the running position itself
     for (; k + 2 <= npair; k += 2) {                          // two pairs per trip: the carried factor ping-pongs, no copies
-        const PairT u0 = load_pair(min(k + 2, npair - 1));
-        pair_step(t0, carry, carry2);
-        t0 = u0;
-        const PairT u1 = load_pair(min(k + 3, npair - 1));
-        pair_step(t1, carry2, carry);
-        t1 = u1;
+        pair_step(t0, carry, carry2, NATAC_OFF(0, 0, DSH), NATAC_OFF(0, 0, DNW));
+        t0 = load_pair(min(k + 2, npair - 1), -2 * PAIRB);
+        pair_step(t1, carry2, carry, NATAC_OFF(1, 0, DSH), NATAC_OFF(1, 0, DNW));
+        t1 = load_pair(min(k + 3, npair - 1), -PAIRB);
+        ish1 += 2 * DSH; ish2 += 2 * DSH; inw1 += 2 * DNW; inw2 += 2 * DNW;
+        vo += 2u * PAIRB;
     }
-    if (k < npair) pair_step(t0, carry, carry2);
+    if (k < npair) pair_step(t0, carry, carry2, NATAC_OFF(0, 0, DSH), NATAC_OFF(0, 0, DNW));
+#undef NATAC_OFF
     // ---- exact zero-cell test, only for windows whose exp(bias) values are small enough for a product to underflow
     // (the host launches natac_candidates4 instead when the template / size distribution hold exact zeros)
     bool zero[Q];

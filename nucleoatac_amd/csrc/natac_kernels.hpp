@@ -37,8 +37,9 @@ struct VMatDev {
     const double *matp;  // R x (W + 2 VPAD): the same rows between VPAD zero columns
     const double *srow;  // [R] sizes[lower + r]
     const double *lrt;   // R x W: log(V[r,c] / sizes[lower + r]) (natac_lr_table; models without exact zeros), or null
+    const double *ctab;  // the paired sweep's template stream (natac_cand_table, natac_cand.hpp), or null
     int lower, upper, w, R, W;
-    int has_zero;        // the template or srow holds an exact 0 (host-computed)
+    int has_zero;       // the template or srow holds an exact 0 (host-computed)
 };
 
 __device__ __forceinline__ int floor_half(int x) { return x >> 1; }  // arithmetic shift == python x//2

@@ -87,6 +87,8 @@ struct natac_ctx {
     PoolBuf<double> d_vmat, d_vmat_pad, d_srow, d_sizes;   // d_vmat_pad: VMatDev::matp
     PoolBuf<double> d_lrt;           // VMatDev::lrt (natac_lr_table), formed for model generation lrt_gen
     long long lrt_gen = -1;
+    PoolBuf<double> d_ctab;          // VMatDev::ctab (natac_cand_table), formed for model generation ctab_gen
+    long long ctab_gen = -1;
     int vlower = 0, vupper = 0, vw = 0, R = 0, W = 0, sizes_upper = 0;
     bool have_vmat = false, have_sizes = false, srow_dirty = true;
     bool vmat_zero = false, srow_zero = false;
