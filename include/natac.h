@@ -53,8 +53,9 @@ extern "C" {
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
- * 15: added natac_enriched_regions for `pyatac peaks`); the binding refuses another version */
-#define NATAC_ABI_VERSION 15
+ * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`); the binding refuses another
+ * version */
+#define NATAC_ABI_VERSION 16
 
 enum {
     NATAC_OK = 0,
@@ -432,6 +433,34 @@ int natac_enriched_regions(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, 
                            const int32_t *thr_large, int64_t *n_regions, int64_t capacity, int64_t *start, int64_t *end, int64_t *summit,
                            int32_t *pileup, int32_t *n_small, int32_t *n_large, int64_t *n_found, int64_t *n_significant,
                            double *kernel_ms);
+/* ---- the truncated SVD of the weighted cell-by-window matrix (this library's own; `pyatac cluster`) ----
+ * The counts come as natac_region_cell_counts writes them: m rows (windows), n columns (cells), row_ptr[m + 1] non-decreasing with
+ * row_ptr[0] >= 0 (the entries are col / count [row_ptr[0], row_ptr[m])), col strictly ascending within a row and in [0, n), count >= 1.
+ * row_weight[m] and col_scale[n] are finite and >= 0; a weight of 0 drops the row, a scale of 0 the column.  X is cells x windows (n x m):
+ * for an entry of count a in window w and cell c, a' = 1 if binarize else a, t = a' * col_scale[c] * row_weight[w], and
+ * X[c, w] = t (transform 0, linear) or log1p(t * scale) (transform 1, log; scale finite and >= 0).  1 <= r <= NATAC_LSI_MAX_R, r at most
+ * the number of live rows and of live columns (so m == 0 or n == 0 is refused), n_iter >= 1, q0[m * r] row-major and finite.
+ *   1. Q = orth(q0), the rows of dropped windows zeroed first;  2. n_iter times: Y = orth(X Q), Q = orth(X^T Y);
+ *   3. Y = X Q, G = Y^T Y = W diag(lam) W^T, lam descending;     4. sigma = sqrt(lam), U = Y W / sigma, V = Q W.
+ * orth is CholeskyQR2: the r x r Gram matrix on the device, its Cholesky factor on the host, the triangular solve on the device, twice.
+ * Step 3's eigenproblem is a cyclic Jacobi on the host.  Outputs: sigma[r], U[n * r], V[m * r] row-major; dropped rows and columns have
+ * zero vectors.  The signs of the components are whatever the iteration leaves (Context.sparse_lsi fixes them).
+ * *status = 1 with NATAC_OK: a Cholesky pivot was at most r * eps * the largest diagonal entry of its Gram matrix (or an eigenvalue of
+ * step 3 was not positive) -- the matrix has fewer than r independent directions.  The outputs are then zeros, nothing has faulted and
+ * the context is as usable as before.  *status = 0 otherwise.
+ * The operands are checked on the host before any launch (NATAC_E_ARG): row_ptr, col, count as above, r and n_iter, transform, negative
+ * or non-finite weights, scales, scale or q0, a null pointer where a size is positive.
+ * Both products run through one sparse-times-block kernel family (csrc/natac_lsi.hpp); for X Q the entry point makes a cell-order copy of
+ * the weighted entries once per call (the order by a stable counting sort on the host, integers only; the weighting on the device).  A
+ * row of the sparse operand goes by its number of entries L: L <= NATAC_LSI_SHORT_MAX a lane group, L <= NATAC_LSI_WAVE_MAX a wave,
+ * longer a workgroup.  Every sum has a fixed shape and there are no floating-point atomics: two calls give the same bytes.
+ * kernel_ms (may be NULL): device time from the first to the last kernel of the call, the host's r x r steps in between included. */
+#define NATAC_LSI_MAX_R 64
+#define NATAC_LSI_SHORT_MAX 32
+#define NATAC_LSI_WAVE_MAX 4096
+int natac_sparse_lsi(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
+                     const double *row_weight, const double *col_scale, double scale, int transform, int binarize, int r, int n_iter,
+                     const double *q0, double *sigma, double *U, double *V, int32_t *status, double *kernel_ms);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -27,6 +27,7 @@
 #include "natac_sites.hpp"
 #include "natac_cellcounts.hpp"
 #include "natac_cellqc.hpp"
+#include "natac_lsi.hpp"
 #include "natac_peakcall.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

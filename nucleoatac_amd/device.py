@@ -396,6 +396,48 @@ class Context(object):
         out = (indptr, col[:nnz].copy(), val[:nnz].copy())
         return out + (ms.value,) if with_kernel_ms else out
 
+    def sparse_lsi(self, indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter, q0, scale=1e4, transform="log", binarize=False,
+                   with_kernel_ms=False):
+        """the r leading singular triplets of the weighted cell-by-window matrix (natac_sparse_lsi; include/natac.h states the
+        algorithm): (sigma float64[r] descending, U float64[n_cells, r], V float64[n_windows, r]).  indptr / indices / data are the CSR
+        arrays of region_cell_counts (rows the windows, indices the cells, ascending within a row, data >= 1).  The entry of count a in
+        window w and cell c is t = a' * col_scale[c] * row_weight[w] (a' = 1 with binarize) or, with transform "log", log1p(t * scale); a
+        zero weight or scale drops the window or the cell, whose vector is then zero.  q0 float64[n_windows, r] starts the n_iter rounds of
+        subspace iteration.  Every component's sign is fixed here: the entry of largest magnitude in its column of U (the lowest index
+        among equals) is positive, the column of V is flipped with it.  ValueError("rank") when the matrix has fewer than r independent
+        directions.  with_kernel_ms: also return the device time of the call's kernels."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        da = np.ascontiguousarray(data, dtype=np.int32)
+        rw = _f64(row_weight)
+        cs = _f64(col_scale)
+        q = _f64(q0)
+        r, n, m = int(r), int(n_cells), ip.shape[0] - 1
+        if ip.ndim != 1 or m < 0 or ix.ndim != 1 or ix.shape != da.shape or rw.shape != (m,) or cs.shape != (max(n, 0),):
+            raise ValueError("indptr / indices / data must be CSR arrays, row_weight one per row and col_scale one per cell")
+        if transform not in ("log", "linear"):
+            raise ValueError("transform must be 'log' or 'linear' (got %r)" % (transform,))
+        if not 1 <= r <= L.LSI_MAX_R:       # before it sizes the outputs
+            raise ValueError("r must be in [1, %d] (got %d)" % (L.LSI_MAX_R, r))
+        if q.shape != (m, r):
+            raise ValueError("q0 must have one row per window and r columns")
+        if m and int(ip[-1]) > ix.shape[0]:
+            raise ValueError("indptr points past the %d entries given" % ix.shape[0])
+        sigma = np.zeros(r, dtype=np.float64)
+        U = np.zeros((n, r), dtype=np.float64)
+        V = np.zeros((m, r), dtype=np.float64)
+        status, ms = C.c_int32(0), C.c_double(0)
+        L.check(self._lib.natac_sparse_lsi(self._h, m, n, _ptr(ip), _ptr(ix), _ptr(da), _ptr(rw), _ptr(cs), float(scale),
+                                           1 if transform == "log" else 0, 1 if binarize else 0, r, int(n_iter), _ptr(q), _ptr(sigma),
+                                           _ptr(U), _ptr(V), C.byref(status), C.byref(ms)))
+        if status.value:
+            raise ValueError("rank")
+        top = np.argmax(np.abs(U), axis=0)
+        flip = np.where(U[top, np.arange(r)] < 0, -1.0, 1.0)
+        U *= flip
+        V *= flip
+        return (sigma, U, V, ms.value) if with_kernel_ms else (sigma, U, V)
+
     def cell_site_qc(self, pos, tlen, cell, n_cells, site_center=None, site_minus=None, flank=1000, center=500, edge=100, peak_start=None,
                      peak_end=None, with_kernel_ms=False):
         """per-cell TSS counts, the aggregate TSS profile and per-cell fragments in peaks of one chromosome (natac_cell_site_qc):

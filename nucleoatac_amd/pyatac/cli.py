@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | peaks` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | peaks` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -14,7 +14,10 @@ profile) and FRiP (the fraction of a cell's fragments in a BED of peaks), and wr
 on those.  `peaks`, this package's own as well, makes the peak set the other commands take (`counts --bed`, `cellqc --peaks`, `cellcounts
 --bed`, `nucleoatac run --bed`) from nothing but the fragments: regions whose insertion pileup is improbable at the genome-wide and at
 two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windows of one width; run per cell group behind `split`, it is
-the last link before `nucleoatac run`.  The other pyatac tools (vplot, bias_vplot) are not part of
+the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
+`cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
+k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
+`cluster` -> `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -187,6 +190,25 @@ def add_cellcounts_parser(sub):
                    help="BASE.cellcounts.mtx.gz with .barcodes.tsv and .regions.bed (default) or BASE.cellcounts.npz (CSR arrays)")
 
 
+def add_cluster_parser(sub):
+    p = sub.add_parser("cluster", help="cluster the cells of a cell-by-window count matrix: TF-IDF, LSI and k-means")
+    p.add_argument("--counts", metavar="matrix", required=True,
+                   help="BASE.cellcounts.npz or BASE.cellcounts.mtx.gz (with its .barcodes.tsv beside it) as `cellcounts` writes them")
+    p.add_argument("--clusters", metavar="int", required=True, type=int, help="Number of clusters")
+    p.add_argument("--components", metavar="int", default=30, type=int, help="LSI components kept for the embedding. Default is 30")
+    p.add_argument("--oversample", metavar="int", default=10, type=int,
+                   help="Further columns of the iterated block; components + oversample is at most 64. Default is 10")
+    p.add_argument("--iterations", metavar="int", default=4, type=int, help="Rounds of subspace iteration. Default is 4")
+    p.add_argument("--method", choices=("log", "linear"), default="log", help="log1p(10000 x TF-IDF) (default) or TF-IDF itself")
+    p.add_argument("--binarize", action="store_true", default=False, help="Every count becomes 1")
+    p.add_argument("--min_cells", metavar="int", default=1, type=int, help="Windows seen in fewer cells are dropped. Default is 1")
+    p.add_argument("--max_depth_cor", metavar="float", default=0.75, type=float,
+                   help="A component whose correlation with log10 of the cells' totals exceeds this in magnitude is removed. Default is 0.75")
+    p.add_argument("--max_iter", metavar="int", default=100, type=int, help="Most k-means steps. Default is 100")
+    p.add_argument("--seed", metavar="int", default=1, type=int, help="Seed of the block the iteration starts from. Default is 1")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the matrix file's name without .cellcounts and its suffix")
+
+
 def add_peaks_parser(sub):
     p = sub.add_parser("peaks", help="call enriched regions (peaks) from the insertions of a fragment store")
     p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
@@ -229,6 +251,7 @@ def pyatac_parser():
     add_cellqc_parser(sub)
     add_split_parser(sub)
     add_cellcounts_parser(sub)
+    add_cluster_parser(sub)
     add_peaks_parser(sub)
     return parser
 
@@ -337,6 +360,15 @@ def pyatac_main(args):
             get_cellcounts(args)
         except (CountsError, BedColumnError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac cellcounts: %s\n" % e)
+            return 1
+    elif args.call == "cluster":
+        from .._lib import NatacError
+        from .get_cluster import ClusterError, get_cluster
+        print("---------Clustering the cells of the count matrix---------------------------------------")
+        try:
+            get_cluster(args)
+        except (ClusterError, NatacError) as e:
+            sys.stderr.write("pyatac cluster: %s\n" % e)
             return 1
     elif args.call == "peaks":
         from .._lib import NatacError

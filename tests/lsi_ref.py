@@ -1,0 +1,163 @@
+"""natac_sparse_lsi and `pyatac cluster` restated in NumPy / scipy.sparse from the rules of include/natac.h and of the module docstring of
+nucleoatac_amd/pyatac/get_cluster.py, not from their code: the weighted matrix, the subspace iteration with numpy.linalg.qr for orth and
+numpy.linalg.eigh for the small eigenproblem, the sign rule, and -- independently of get_cluster.py -- the weights, the depth rule, the
+row normalisation, k-means and the naming of the clusters."""
+import numpy as np
+import scipy.sparse as sp
+
+EPS = np.finfo(np.float64).eps
+
+
+def weighted_matrix(indptr, indices, data, n_cells, row_weight, col_scale, scale=1e4, transform="log", binarize=False):
+    """X (cells x windows) as scipy CSR"""
+    indptr = np.asarray(indptr, np.int64)
+    m = len(indptr) - 1
+    a = np.ones(len(indices), np.float64) if binarize else np.asarray(data, np.float64)
+    rows = np.repeat(np.arange(m), np.diff(indptr))
+    t = a * np.asarray(col_scale, np.float64)[indices] * np.asarray(row_weight, np.float64)[rows]
+    v = np.log1p(t * scale) if transform == "log" else t
+    A = sp.csr_matrix((v, np.asarray(indices, np.int64), indptr), shape=(m, n_cells))
+    return A.T.tocsr()
+
+
+def fix_signs(U, V):
+    """the largest-magnitude entry of every column of U (lowest index among equals) is positive; V follows"""
+    U, V = U.copy(), V.copy()
+    for j in range(U.shape[1]):
+        k = int(np.argmax(np.abs(U[:, j])))
+        if U[k, j] < 0:
+            U[:, j] = -U[:, j]
+            V[:, j] = -V[:, j]
+    return U, V
+
+
+def _orth(B):
+    """the rank rule in QR's terms: a Cholesky pivot of B^T B is the square of a diagonal entry of R, the diagonal of B^T B the squared
+    column norms"""
+    q, rr = np.linalg.qr(B)
+    d = np.diag(rr) ** 2
+    if not np.all(np.isfinite(d)) or d.min() <= B.shape[1] * EPS * (B * B).sum(axis=0).max():
+        raise ValueError("rank")
+    return q
+
+
+def sparse_lsi(indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter, q0, scale=1e4, transform="log", binarize=False):
+    """(sigma, U, V) by the four steps of natac.h; ValueError("rank") when a block loses rank"""
+    X = weighted_matrix(indptr, indices, data, n_cells, row_weight, col_scale, scale, transform, binarize)
+    q0 = np.array(q0, np.float64)
+    q0[~(np.asarray(row_weight) > 0)] = 0.0
+    Q = _orth(q0)
+    for _ in range(n_iter):
+        Y = _orth(X.dot(Q))
+        Q = _orth(X.T.dot(Y))
+    Y = X.dot(Q)
+    lam, W = np.linalg.eigh(Y.T.dot(Y))
+    lam, W = lam[::-1], W[:, ::-1]
+    if not lam.min() > 0:
+        raise ValueError("rank")
+    sigma = np.sqrt(lam)
+    U, V = fix_signs(Y.dot(W) / sigma, Q.dot(W))
+    return sigma, U, V
+
+
+def dense_svd(X, k):
+    """the k leading triplets of numpy.linalg.svd with the sign rule, and all singular values"""
+    u, s, vt = np.linalg.svd(X.toarray() if sp.issparse(X) else X, full_matrices=False)
+    U, V = fix_signs(u[:, :k], vt[:k].T)
+    return s, U, V
+
+
+def qualifying(s_all, k, rel=1e-3):
+    """the components j < k whose gaps to both neighbours are at least rel * s_all[0]"""
+    out = []
+    for j in range(k):
+        up = s_all[j - 1] - s_all[j] if j else np.inf
+        down = s_all[j] - s_all[j + 1] if j + 1 < len(s_all) else s_all[j]
+        if min(up, down) >= rel * s_all[0]:
+            out.append(j)
+    return out
+
+
+# ---- the command's host part, restated ----
+def weights(indptr, indices, data, n_cells, binarize=False, min_cells=1):
+    """(total, row_weight, col_scale): loops over the entries, no vector tricks"""
+    m = len(indptr) - 1
+    total = [0] * n_cells
+    t_w = [0] * m
+    seen = [0] * m
+    for w in range(m):
+        for e in range(int(indptr[w]), int(indptr[w + 1])):
+            a = 1 if binarize else int(data[e])
+            total[int(indices[e])] += a
+            t_w[w] += a
+            seen[w] += 1
+    n_kept = sum(1 for t in total if t > 0)
+    col_scale = np.array([1.0 / t if t > 0 else 0.0 for t in total])
+    row_weight = np.array([float(n_kept) / t_w[w] if seen[w] >= min_cells and t_w[w] > 0 else 0.0 for w in range(m)])
+    return np.array(total, np.int64), row_weight, col_scale
+
+
+def embedding(sigma, U, total, components, max_depth_cor):
+    """(unit rows of the kept components for the cells with total > 0, depth_cor, kept component indices)"""
+    keep = total > 0
+    E = (U[:, :components] * sigma[:components])[keep]
+    d = np.log10(total[keep].astype(np.float64))
+    cor = np.zeros(components)
+    for j in range(components):
+        if E[:, j].std() > 0 and d.std() > 0:
+            cor[j] = np.corrcoef(E[:, j], d)[0, 1]
+    comp = [j for j in range(components) if not abs(cor[j]) > max_depth_cor]
+    Z = E[:, comp]
+    n = np.linalg.norm(Z, axis=1)
+    out = np.zeros_like(Z)
+    out[n > 0] = Z[n > 0] / n[n > 0, None]
+    return out, cor, comp
+
+
+def kmeans(X, k, max_iter=100):
+    """(names int[n]: 0 for c1, ...; sizes in naming order; steps) with explicit differences instead of the product form"""
+    def d2(c):
+        return ((X - c) ** 2).sum(axis=1)
+    centres = [X[int(np.argmax(d2(X.mean(axis=0))))].copy()]
+    while len(centres) < k:
+        near = np.min([d2(c) for c in centres], axis=0)
+        centres.append(X[int(np.argmax(near))].copy())
+    labels, steps = None, 0
+    while steps < max_iter:
+        new = np.argmin(np.stack([d2(c) for c in centres], axis=1), axis=1)
+        steps += 1
+        if labels is not None and np.array_equal(new, labels):
+            break
+        labels = new
+        for j in range(k):
+            if np.any(labels == j):
+                centres[j] = X[labels == j].mean(axis=0)
+    size = [int(np.sum(labels == j)) for j in range(k)]
+    first = [int(np.flatnonzero(labels == j)[0]) if size[j] else len(X) for j in range(k)]
+    order = sorted(range(k), key=lambda j: (-size[j], first[j], j))
+    name = {j: i for i, j in enumerate(order)}
+    return np.array([name[int(l)] for l in labels]), [size[j] for j in order], steps
+
+
+# ---- test matrices ----
+def csr_of(A):
+    """(indptr int64, indices int32, data int32) of a dense or sparse windows x cells count matrix"""
+    A = sp.csr_matrix(A)
+    A.sort_indices()
+    A.eliminate_zeros()
+    return A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.int32)
+
+
+def planted(n_groups=4, per_group=100, n_windows=3000, own=600, enrich=6.0, depth=(300, 3000), seed=1):
+    """windows x cells counts: every group is `enrich` times enriched in its own `own` windows; multinomial draws at depths spread evenly
+    in log over `depth`.  -> (counts as scipy CSR, group of every cell)"""
+    rng = np.random.default_rng(seed)
+    n = n_groups * per_group
+    group = np.repeat(np.arange(n_groups), per_group)
+    depths = np.exp(rng.uniform(np.log(depth[0]), np.log(depth[1]), n)).astype(np.int64)
+    cols = []
+    for c in range(n):
+        p = np.ones(n_windows)
+        p[group[c] * own:(group[c] + 1) * own] = enrich
+        cols.append(rng.multinomial(int(depths[c]), p / p.sum()))
+    return sp.csr_matrix(np.stack(cols, axis=1)), group
