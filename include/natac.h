@@ -447,7 +447,13 @@ int natac_enriched_regions(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, 
  * zero vectors.  The signs of the components are whatever the iteration leaves (Context.sparse_lsi fixes them).
  * *status = 1 with NATAC_OK: a Cholesky pivot was at most r * eps * the largest diagonal entry of its Gram matrix (or an eigenvalue of
  * step 3 was not positive) -- the matrix has fewer than r independent directions.  The outputs are then zeros, nothing has faulted and
- * the context is as usable as before.  *status = 0 otherwise.
+ * the context is as usable as before.
+ * *status = 2 with NATAC_OK: the operands' size took a Gram matrix out of fp64's range -- an entry of one was not finite (singular values
+ * above about 1e154, or q0 that large), or its largest diagonal entry was so small that the pivot floor r * eps * max(diag) lay below
+ * DBL_MIN (singular values below about 1e-146 / sqrt(r), or q0 that small: the pivots would sit among the denormals and lose bits without
+ * falling under the floor), or the block was not zero and all its squares were.  The outputs are zeros as for status 1.  Inside that range
+ * every step scales with the operands and every threshold is relative: a power of two in row_weight (linear transform), one moved between
+ * col_scale and scale (log), or one in q0 scales sigma (or nothing) exactly and changes no bit of U and V.  *status = 0 otherwise.
  * The operands are checked on the host before any launch (NATAC_E_ARG): row_ptr, col, count as above, r and n_iter, transform, negative
  * or non-finite weights, scales, scale or q0, a null pointer where a size is positive.
  * Both products run through one sparse-times-block kernel family (csrc/natac_lsi.hpp); for X Q the entry point makes a cell-order copy of

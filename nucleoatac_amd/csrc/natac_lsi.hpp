@@ -11,6 +11,10 @@
 //   4. sigma = sqrt(lam),  U = Y W / sigma,  V = Q W
 // orth is CholeskyQR2: G = B^T B on the device, G = R^T R on the host (plain C++, r <= 64), B <- B R^-1 on the device (a forward
 // substitution per row), and all of that once more.  A pivot of at most r * eps * max(diag G) means the block has lost rank: status 1.
+// Every step scales with the operands and every threshold is relative, so a power of two in row_weight, col_scale or q0 changes no bit
+// of U and V -- as long as the Gram matrices stay inside fp64.  One that does not (an entry not finite; max(diag G) so small that the
+// pivot floor r * eps * max(diag G) is below DBL_MIN, where the pivots sit among the denormals and lose bits without falling under the
+// floor; a block of non-zero entries whose squares all vanished) ends the call with status 2.
 //
 // Kernels:
 //   lsi_weight / lsi_transpose   one pass over the entries: the weighted values in window order, and the same values with their window
@@ -31,6 +35,8 @@
 //                   added in slab order.
 //   lsi_rows_small  B <- B R^-1 (forward substitution) or B <- B M / d: one row per thread, the row in registers, R or M read through
 //                   the scalar cache; rows go in and out through LDS so that global accesses stay coalesced.
+//   lsi_any_nonzero whether a block holds anything but zeros: asked only when a Gram diagonal is zero, to tell an empty block (status 1)
+//                   from one whose squares vanished (status 2).
 // Every sum has a fixed shape -- a row's entries, the groups, the waves, a slab's rows, the slabs -- and there are no floating-point
 // atomics: the result is a pure function of the operands.
 // Behind the kernels: the host's Cholesky and Jacobi, and the entry point.
@@ -80,6 +86,12 @@ __global__ void __launch_bounds__(LSI_BLOCK) lsi_mask_rows(double *__restrict__ 
     const long long total = N * r;
     for (long long t = (long long)blockIdx.x * LSI_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * LSI_BLOCK)
         if (!(row_weight[t / r] > 0.0)) B[t] = 0.0;
+}
+
+// *flag = 1 when B[0 .. total) holds anything but zeros (every writer stores the same word)
+__global__ void __launch_bounds__(LSI_BLOCK) lsi_any_nonzero(const double *__restrict__ B, long long total, int *__restrict__ flag) {
+    for (long long t = (long long)blockIdx.x * LSI_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * LSI_BLOCK)
+        if (B[t] != 0.0) *flag = 1;
 }
 
 // the sum over the entries p, p + stride, ... < p1 of val * B[idx, j], in that order, four loads of B in flight
@@ -260,6 +272,17 @@ __global__ void __launch_bounds__(LSI_ROWS) lsi_rows_small(double *__restrict__ 
 }
 
 // ---- the host's r x r linear algebra ----
+// Whether a Gram matrix G (r x r) is of a size the factorisation can work with: 0 yes; 2 no -- an entry is not finite, or the pivot floor
+// r * eps * max(diag G) is below the smallest normal number; 3 its diagonal is zero: the block is empty or every square vanished.
+static int lsi_gram_size(const std::vector<double> &G, int r) {
+    for (const double g : G)
+        if (!std::isfinite(g)) return 2;
+    double dmax = 0.0;
+    for (int i = 0; i < r; ++i) dmax = std::max(dmax, G[(size_t)i * r + i]);
+    if (dmax == 0.0) return 3;
+    return (double)r * std::numeric_limits<double>::epsilon() * dmax < std::numeric_limits<double>::min() ? 2 : 0;
+}
+
 // G (r x r, symmetric) = R^T R, R upper triangular, written into Rp (rp x rp, row-major, the identity past r).  false: a pivot is at most
 // r * eps * max(diag G), or not a number -- the block has lost rank.
 static bool lsi_cholesky(const std::vector<double> &G, int r, int rp, std::vector<double> &Rp) {
@@ -299,7 +322,8 @@ static void lsi_jacobi(std::vector<double> &A, int r, std::vector<double> &W, st
         for (int p = 0; p < r - 1; ++p)
             for (int q = p + 1; q < r; ++q) {
                 const double apq = A[(size_t)p * r + q], app = A[(size_t)p * r + p], aqq = A[(size_t)q * r + q];
-                if (apq == 0.0 || std::fabs(apq) <= 0.125 * eps * std::sqrt(std::fabs(app) * std::fabs(aqq))) continue;
+                // sqrt(|app|) * sqrt(|aqq|), not the root of the product: that is about sigma^4, out of range long before G is
+                if (apq == 0.0 || std::fabs(apq) <= 0.125 * eps * (std::sqrt(std::fabs(app)) * std::sqrt(std::fabs(aqq)))) continue;
                 rotated = true;
                 const double theta = (aqq - app) / (2.0 * apq);
                 const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
@@ -481,6 +505,7 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
     double *d_Q = dc.upload(q0, (size_t)m * r), *d_Y = dc.alloc<double>((size_t)n * r);
     double *d_part = dc.alloc<double>((size_t)n_slab_max * rp * rp), *d_G = dc.alloc<double>((size_t)r * r);
     double *d_M = dc.alloc<double>((size_t)rp * rp), *d_M2 = dc.alloc<double>((size_t)rp * rp), *d_sig = dc.alloc<double>((size_t)rp);
+    int *d_flag = dc.alloc<int>(1);
     hipStream_t st = c->stream;
     std::vector<double> hG((size_t)r * r), hR, hW, lam;
 
@@ -496,7 +521,20 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
         hipLaunchKernelGGL(lsi_mask_rows, dim3(bq), dim3(LSI_BLOCK), 0, st, d_Q, (long long)m, r, d_rw);
         dc.launched();
     }
-    // CholeskyQR2 of a block in place: 0, 1 (rank lost) or an error code.  hR is rewritten only behind a wait that has drained its last copy.
+    // a block whose Gram diagonal is zero: 1 it is zero itself (no direction), 2 it is not (its squares vanished), or an error code
+    auto vanished = [&](const double *d_B, long long total) -> int {
+        int h_flag = 0;
+        dc.zero(d_flag, 1);
+        if (dc.ok()) {
+            const unsigned bx = (unsigned)std::min<long long>((total + LSI_BLOCK - 1) / LSI_BLOCK, 16384);
+            hipLaunchKernelGGL(lsi_any_nonzero, dim3(bx), dim3(LSI_BLOCK), 0, st, d_B, total, d_flag);
+            dc.launched();
+        }
+        dc.fetch(&h_flag, d_flag, 1);
+        if (const int rc = dc.sync()) return rc;
+        return h_flag ? 2 : 1;
+    };
+    // CholeskyQR2 of a block in place: 0, 1 (rank lost), 2 (out of range) or an error code.  hR is rewritten only behind a wait that has drained its last copy.
     auto orth = [&](double *d_B, long long N) -> int {
         for (int pass = 0; pass < 2; ++pass) {
             if (dc.ok()) {
@@ -505,6 +543,7 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
             }
             dc.fetch(hG.data(), d_G, hG.size());
             if (const int rc = dc.sync()) return rc;
+            if (const int size = lsi_gram_size(hG, r)) return size == 3 ? vanished(d_B, N * r) : size;
             if (!lsi_cholesky(hG, r, rp, hR)) return 1;
             dc.send(d_M, hR.data(), hR.size());
             if (dc.ok()) {
@@ -519,10 +558,10 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
         NATAC_LSI_BY_WIDTH(rp, lsi_spmm<RP>(st, s, B, r, out));
         dc.launched();
     };
-    auto lost = [&]() -> int {                             // the call is well, the basis is not
+    auto lost = [&](int why) -> int {                      // the call is well, the basis is not
         dc.time_end();
         if (const int rc = dc.finish()) return rc;
-        *status = 1;
+        *status = why;
         for (int j = 0; j < r; ++j) sigma[j] = 0.0;
         for (int64_t i = 0; i < n * r; ++i) U[i] = 0.0;
         for (int64_t i = 0; i < m * r; ++i) V[i] = 0.0;
@@ -536,7 +575,7 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
         rc = orth(d_Q, m);
     }
     if (rc < 0) return rc;
-    if (rc == 1) return lost();
+    if (rc) return lost(rc);
     product(T, d_Q, d_Y);
     if (dc.ok()) {
         NATAC_LSI_BY_WIDTH(rp, lsi_gram<RP>(st, d_Y, n, r, d_part, d_G));
@@ -544,11 +583,13 @@ int natac_sparse_lsi(natac_ctx *c, int64_t m, int64_t n, const int64_t *row_ptr,
     }
     dc.fetch(hG.data(), d_G, hG.size());
     if ((rc = dc.sync())) return rc;
-    for (const double g : hG)
-        if (!std::isfinite(g)) return lost();
+    if (int size = lsi_gram_size(hG, r)) {
+        if (size == 3 && (size = vanished(d_Y, (long long)n * r)) < 0) return size;
+        return lost(size);
+    }
     lsi_jacobi(hG, r, hW, lam);
     for (int j = 0; j < r; ++j)
-        if (!(lam[(size_t)j] > 0.0)) return lost();        // no direction left to divide by
+        if (!(lam[(size_t)j] > 0.0)) return lost(1);        // no direction left to divide by
     std::vector<double> hM((size_t)rp * rp, 0.0), hS((size_t)rp, 1.0);
     for (int k = 0; k < r; ++k)
         for (int j = 0; j < r; ++j) hM[(size_t)k * rp + j] = hW[(size_t)k * r + j];

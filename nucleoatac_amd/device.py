@@ -405,7 +405,9 @@ class Context(object):
         zero weight or scale drops the window or the cell, whose vector is then zero.  q0 float64[n_windows, r] starts the n_iter rounds of
         subspace iteration.  Every component's sign is fixed here: the entry of largest magnitude in its column of U (the lowest index
         among equals) is positive, the column of V is flipped with it.  ValueError("rank") when the matrix has fewer than r independent
-        directions.  with_kernel_ms: also return the device time of the call's kernels."""
+        directions.  ValueError("range") when the size of the weights or of q0 takes a Gram matrix of the iteration out of fp64's range
+        (singular values above about 1e154 or below about 1e-146 / sqrt(r); natac.h has the rule) -- inside it a power of two in the
+        weights or in q0 changes no bit of U and V.  with_kernel_ms: also return the device time of the call's kernels."""
         ip = np.ascontiguousarray(indptr, dtype=np.int64)
         ix = np.ascontiguousarray(indices, dtype=np.int32)
         da = np.ascontiguousarray(data, dtype=np.int32)
@@ -431,7 +433,7 @@ class Context(object):
                                            1 if transform == "log" else 0, 1 if binarize else 0, r, int(n_iter), _ptr(q), _ptr(sigma),
                                            _ptr(U), _ptr(V), C.byref(status), C.byref(ms)))
         if status.value:
-            raise ValueError("rank")
+            raise ValueError("range" if status.value == 2 else "rank")
         top = np.argmax(np.abs(U), axis=0)
         flip = np.where(U[top, np.arange(r)] < 0, -1.0, 1.0)
         U *= flip

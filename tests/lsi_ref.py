@@ -33,7 +33,9 @@ def fix_signs(U, V):
 
 def _orth(B):
     """the rank rule in QR's terms: a Cholesky pivot of B^T B is the square of a diagonal entry of R, the diagonal of B^T B the squared
-    column norms"""
+    column norms.  Before it the range rule in the Gram matrix's own terms, since QR does not square: B^T B must be finite and its pivot
+    floor at least the smallest normal number; a block that is not zero while all its squares are is out of range too."""
+    _in_range(B)
     q, rr = np.linalg.qr(B)
     d = np.diag(rr) ** 2
     if not np.all(np.isfinite(d)) or d.min() <= B.shape[1] * EPS * (B * B).sum(axis=0).max():
@@ -41,8 +43,17 @@ def _orth(B):
     return q
 
 
+def _in_range(B):
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        G = B.T.dot(B)
+    dmax = np.diag(G).max() if np.all(np.isfinite(G)) else np.inf
+    if not np.isfinite(dmax) or (B.any() if dmax == 0 else B.shape[1] * EPS * dmax < np.finfo(np.float64).tiny):
+        raise ValueError("range")
+
+
 def sparse_lsi(indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter, q0, scale=1e4, transform="log", binarize=False):
-    """(sigma, U, V) by the four steps of natac.h; ValueError("rank") when a block loses rank"""
+    """(sigma, U, V) by the four steps of natac.h; ValueError("rank") when a block loses rank, ValueError("range") when a Gram matrix
+    leaves fp64's range"""
     X = weighted_matrix(indptr, indices, data, n_cells, row_weight, col_scale, scale, transform, binarize)
     q0 = np.array(q0, np.float64)
     q0[~(np.asarray(row_weight) > 0)] = 0.0
@@ -51,6 +62,7 @@ def sparse_lsi(indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter,
         Y = _orth(X.dot(Q))
         Q = _orth(X.T.dot(Y))
     Y = X.dot(Q)
+    _in_range(Y)
     lam, W = np.linalg.eigh(Y.T.dot(Y))
     lam, W = lam[::-1], W[:, ::-1]
     if not lam.min() > 0:
@@ -146,6 +158,38 @@ def csr_of(A):
     A.sort_indices()
     A.eliminate_zeros()
     return A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.int32)
+
+
+def block_counts(K, bw, bc):
+    """K disjoint all-ones blocks, block k the windows [k bw, (k + 1) bw) x the cells [k bc, (k + 1) bc), as CSR arrays.  With the linear
+    transform, row_weight s_k on block k and col_scale 1 the SVD is closed: sigma_k = s_k sqrt(bw bc), column k of U is 1 / sqrt(bc) on
+    the block's cells, column k of V is 1 / sqrt(bw) on its windows (block_truth)."""
+    w = np.arange(K * bw)
+    ip = np.arange(K * bw + 1, dtype=np.int64) * bc
+    ix = ((w // bw) * bc)[:, None] + np.arange(bc)[None, :]
+    return ip, ix.ravel().astype(np.int32), np.ones(K * bw * bc, np.int32)
+
+
+def block_truth(s, bw, bc):
+    """(row_weight, sigma, U, V) of block_counts(len(s), bw, bc) for the block values s, which must descend strictly or be all equal"""
+    s = np.asarray(s, np.float64)
+    K = len(s)
+    U, V = np.zeros((K * bc, K)), np.zeros((K * bw, K))
+    for k in range(K):
+        U[k * bc:(k + 1) * bc, k] = 1.0 / np.sqrt(bc)
+        V[k * bw:(k + 1) * bw, k] = 1.0 / np.sqrt(bw)
+    return np.repeat(s, bw), s * np.sqrt(bw * bc), U, V
+
+
+def circulant_counts(n, n_off, seed):
+    """n windows x n cells: window w holds the cells (w + d) mod n for n_off fixed random offsets d, counts 1 to 4 -- every row and every
+    column has exactly n_off entries"""
+    rng = np.random.default_rng(seed)
+    off = np.sort(rng.choice(n, n_off, replace=False))
+    ix = (np.arange(n)[:, None] + off[None, :]) % n
+    ix.sort(axis=1)
+    ip = np.arange(n + 1, dtype=np.int64) * n_off
+    return ip, ix.ravel().astype(np.int32), rng.integers(1, 5, n * n_off).astype(np.int32)
 
 
 def planted(n_groups=4, per_group=100, n_windows=3000, own=600, enrich=6.0, depth=(300, 3000), seed=1):
