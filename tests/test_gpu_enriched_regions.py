@@ -6,7 +6,6 @@ The constructed cases pass tables made by hand (the device sees nothing else of 
 significant exactly when its pileup reaches min_pileup, and one insertion with half_width 1 is a run of three significant bases."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -16,14 +15,10 @@ import pytest
 import peaks_ref as R
 from conftest import ROOT
 from helpers import bgzf_bytes
+from peaks_ref import FIRST_CAPACITY, OPEN, SEGMENT, SHORT_MAX, at, real_tables      # (natac.h's sizes; shared with the host checks)
 
 pytestmark = pytest.mark.gpu
 
-_HDR = open(os.path.join(ROOT, "include", "natac.h")).read()
-SEGMENT = int(re.search(r"#define NATAC_PEAKS_SEGMENT_DEFAULT (\d+)", _HDR).group(1))
-SHORT_MAX = int(re.search(r"#define NATAC_PEAKS_SHORT_MAX (\d+)", _HDR).group(1))
-FIRST_CAPACITY = int(re.search(r"#define NATAC_PEAKS_FIRST_CAPACITY (\d+)", _HDR).group(1))
-OPEN = np.full(64, 2 ** 31 - 1, np.int32)
 DEFAULT = (75, 500, 5000, 75, 150)           # half_width, small, large, max_gap, min_length
 
 
@@ -38,13 +33,6 @@ def _vp(a):
 
 def _i64(x):
     return np.ascontiguousarray(x, dtype=np.int64)
-
-
-def at(xs, n):
-    """records whose l are the sorted bases xs and whose r lies past the chromosome's end"""
-    xs = _i64(xs)
-    assert np.all(np.diff(xs) >= 0)
-    return xs - 4, np.full(len(xs), n + 100, np.int64)
 
 
 def assert_same(got, want):
@@ -63,11 +51,6 @@ def both(pos, tlen, n, geom, min_pile, ts, tl, **kw):
     got = _ctx().enriched_regions(pos, tlen, n, ts, tl, min_pile, h, S, L, gap, length, with_counts=True, **kw)
     assert_same(got, want)
     return want
-
-
-def real_tables(pos, tlen, n, h, S, L, q):
-    lam, ts, tl = R.tables(h, S, L, q)
-    return R.min_pileup(lam, (2 * h + 1.0) * len(R.insertions(pos, tlen, n)) / n), ts, tl
 
 
 def test_constants():
@@ -214,6 +197,7 @@ def _segment_cases():
     cases.append((pos, tlen, n, (1, 1, 1, 5, 1), 1, OPEN, OPEN))
     pos, tlen = at(np.arange(0, n, 2), n)                # one region over every segment
     cases.append((pos, tlen, n, (1, 1, 1, 0, 1), 1, OPEN, OPEN))
+    cases += R.long_piece_cases()[0]                     # (4, 5, 6) pieces above SHORT_MAX in several segments of 3000
     return cases
 
 
@@ -238,10 +222,11 @@ def test_segment_cases_at_the_default_segment(segment_cases):
     assert len(want[0][0]) >= 3 and len(want[1][0]) >= 3
 
 
-@pytest.mark.parametrize("segment", [1000, 7001, 64])
+@pytest.mark.parametrize("segment", [1000, 7001, 64, 3000, 2048])
 def test_segment_size_changes_nothing(segment_cases, segment, tmp_path):
     """NATAC_PEAKS_SEGMENT in a fresh child process: 1000 and 7001 are below 2 * large = 10000 of the default geometry, 1000 puts the
-    borders where the third case wants them, and 64 is below every halo there is"""
+    borders where the third case wants them, and 64 is below every halo there is.  3000 cuts the last three cases into the long and
+    short pieces they are made for; at 2048 = SHORT_MAX no piece is long"""
     cases, want, path = segment_cases
     out = str(tmp_path / "out.npz")
     env = dict(os.environ, NATAC_PEAKS_SEGMENT=str(segment))

@@ -285,3 +285,132 @@ def test_downstream_bed_readers_take_both_files(tmp_path):
         assert list(names) == ["chr1"] and chrom.tolist() == [0] and (start.tolist(), end.tolist()) == ([row[0]], [row[1]])
         chunks = ChunkList.read(str(tmp_path / name))
         assert [(c.chrom, c.start, c.end) for c in chunks] == [("chr1",) + row]
+
+
+# ---- the constructed cases of the device tests reach what they are built for (the restatement alone) ---------------------------------
+def _pairs(ans):
+    return list(zip(ans[0].tolist(), ans[1].tolist()))
+
+
+def test_scan_borders_of_the_default_segment():
+    hist, verdict, segment = R.scan_borders()
+    assert R.SEGMENT == 2 * R.SCAN_TRIP and R.BORDERS_N > 2 * R.SEGMENT           # three segments; the last has one trip
+    assert segment == [4194304, 8388608] and verdict == [2097152, 6291456]
+    assert hist == [2097152, 4194304, 6291455, 8388607]       # two more trips of the histogram's scan in each full segment
+
+
+@pytest.mark.parametrize("max_gap,kind", R.BORDER_CASES)
+def test_border_cases_lie_across_their_borders(max_gap, kind):
+    case, spots, ans = R.border_case_with_answer(max_gap, kind)
+    hist, verdict, segment = R.scan_borders()
+    regions, ins = set(_pairs(ans)), R.insertions(case[0], case[1], case[2])
+    assert len(regions) == ans[6] > R.FIRST_CAPACITY                             # the first sweep's buffer overflows
+    assert [B for B, _, _ in spots] == sorted(verdict + segment)
+    for B, what, want in spots:
+        assert all(w in regions for w in want), (B, what)
+        lo, hi = want[0][0], want[-1][1] - 1                  # the construction's first and last significant base
+        assert not np.any((ins >= lo - 100) & (ins <= lo)) and not np.any((ins >= hi) & (ins <= hi + 100))       # nothing else near it
+        if what in ("joined", "split"):
+            x = want[-1][0] if what == "split" else want[0][0] + 31 + max_gap   # the later run's first base
+            between = max_gap + (what == "split")
+            assert not np.any((ins >= x - between - 1) & (ins <= x - 1)) and np.any(ins == x + 1) and np.any(ins == x - between - 2)
+            assert len(want) == (2 if what == "split" else 1)
+            assert x - max_gap - 1 < B <= x                   # the bases that decide whether x starts a region: both sides of B
+        elif what == "dense":
+            assert lo < B - 1 and B + 1 < hi and (lo + hi) // 2 > B + 2           # across B - 1 | B, the summit not beside it
+        elif what == "ends":
+            assert hi == B - 1 and B == segment[0]            # ends on the last base of a segment
+        else:
+            assert what == "starts" and lo == B and B == segment[1]
+        assert all(lo < b < hi for b in hist if abs(b - B) <= 1) or what in ("ends", "starts")
+    assert all(any(0 <= B - b <= 1 for B, _, _ in spots) for b in hist)
+    if (max_gap, kind) in ((0, "joined"), (7, "dense")):      # a run across every border of the histogram's scan, between them
+        dense = [(B, want[0]) for B, what, want in spots if what in ("joined", "dense")]
+        if max_gap == 0:
+            assert len(dense) == 4 and all(a < b - 1 and b + 1 < e for b in hist for B, (a, e) in dense if abs(b - B) <= 1)
+        else:
+            assert [B for B, _ in dense] == verdict
+
+
+def test_long_piece_cases_have_the_pieces_they_are_made_for():
+    cases, summits = R.long_piece_cases()
+    for k, (case, (top_a, top_b)) in enumerate(zip(cases, summits)):
+        ans = R.regions_of(case, counts=False)
+        assert _pairs(ans) == [(999, 1002), (2500, 14300), (14699, 14702), (15099, 15102), (15500, 21500), (21999, 22002)]
+        per_segment = R.pieces(ans[0], ans[1], case[2], 3000)
+        assert per_segment == [[3, 500], [3000], [3000], [3000], [2300, 3], [3, 2500], [3000], [500, 3]]
+        long_ = [[p for p in seg if p > R.SHORT_MAX] for seg in per_segment]
+        assert [len(s) for s in long_] == [0, 1, 1, 1, 1, 1, 1, 0]             # the long list's offset grows from segment to segment
+        assert sum(1 for seg, l in zip(per_segment, long_) if seg == l) == 4 and sum(1 for seg, l in zip(per_segment, long_) if l and seg != l) == 2
+        assert max(max(seg, default=0) for seg in R.pieces(ans[0], ans[1], case[2], 2048)) <= R.SHORT_MAX
+        assert ans[2][1] == top_a and ans[2][4] == top_b and ans[3].tolist() == [1, 2 if k == 2 else 5, 1, 1, 5, 1]
+    assert summits == [(2700, 16000), (7000, 19000), (6350, 21200)]
+    assert 2500 < 2700 < 3000 < 6000 < 7000 < 9000 < 10000 < 12000 and 15500 < 16000 < 18000 < 19000 < 21000 < 21200 < 21500
+
+
+def test_piece_limit_case_has_regions_of_exactly_the_limit():
+    case, want = R.piece_limit_case()
+    ans = R.regions_of(case, counts=False)
+    assert list(zip(*(a.tolist() for a in ans[:3]))) == want
+    assert sorted(set((ans[1] - ans[0]).tolist())) == [R.SHORT_MAX - 1, R.SHORT_MAX, R.SHORT_MAX + 1] and len(want) == 15
+    assert ans[3].tolist() == [12, 12, 12, 12, 3] * 3         # one highest base, or two equal ones around a summit that is none
+    cum = np.concatenate([[0], np.cumsum(np.bincount(R.insertions(case[0], case[1], case[2]), minlength=case[2]))])
+    p = R.window_counts(cum, case[2], 1)
+    for (a, e, c), place in zip(want, ["first", "last", 63, 64, "both"] * 3):
+        top = a + np.flatnonzero(p[a:e] == 12)
+        assert top.tolist() == {"first": [a], "last": [e - 1], "both": [a, e - 1]}.get(place, [c]) and p[a:e].max() == 12
+    assert case[2] < R.SEGMENT                                # one segment: a region is one piece
+
+
+def test_reach_case_is_decided_by_its_far_records():
+    case = R.reach_case()
+    pos, tlen, n, geom = case[:4]
+    L, seg = geom[2], R.REACH_SEGMENT
+    assert pos[0] == -15 < pos[1] and tlen[0] == 5000 == tlen.max() and pos[0] + 4 < 0 and pos[0] + tlen[0] - 5 == 5 * seg - L
+    assert pos[-1] == 6024 > pos[-2] and tlen[-1] == -3000 == tlen.min() and pos[-1] + 4 >= n and pos[-1] + tlen[-1] - 5 == 3 * seg + L - 1
+    assert np.sum(tlen == 0) == 1 and np.sum((tlen >= 30) & (tlen <= 220)) > 0.8 * len(pos)
+    ins = R.insertions(pos, tlen, n)
+    assert np.sum(ins == 5 * seg - L) == 1 and np.sum(ins == 3 * seg + L - 1) == 1
+    full = R.regions_of(case)
+    at = {(a, e): (c, g) for a, e, c, g in zip(full[0].tolist(), full[1].tolist(), full[2].tolist(), full[5].tolist())}
+    assert at[(2997, 2999)] == (2997, 5) and at[(5001, 5003)] == (5001, 5)
+    assert at[(3037, 3042)] == (3039, 8) and at[(4958, 4963)] == (4960, 8)      # the far insertions at exactly large of the summits
+    assert not any(a < 4003 and e > 3998 for a, e in at)
+    for name, gone, there in (("far+", (5001, 5003), (4998, 5003)), ("far-", (2997, 2999), (2997, 3002)), ("zero", None, (3998, 4003))):
+        less = R.regions_of(R.reach_case(drop=(name,)))
+        assert there in _pairs(less) and gone not in _pairs(less) and there not in at
+    less = R.regions_of(R.reach_case(drop=("far+", "far-")))
+    assert less[5][_pairs(less).index((3037, 3042))] == 7 and less[5][_pairs(less).index((4958, 4963))] == 7
+
+
+def test_grid_stride_case_keeps_a_region_of_the_records_past_the_grid():
+    case = R.grid_stride_case()
+    assert len(case[0]) == R.GRID_RECORDS + 1000 and np.all(np.diff(case[0]) >= 0) and case[1].max() <= 220
+    ans = R.regions_of(case)
+    tail = ans[0] >= 99_000
+    assert tail.sum() == 1 and (~tail).sum() >= 6 and case[4] > 1000
+    less = R.regions_of(R.grid_stride_case(tail=False))       # the same tables without the last 1000 records
+    assert all(np.array_equal(a[~tail], b) for a, b in zip(ans[:6], less[:6]))
+
+
+def test_far_end_case_moves_with_a_shift():
+    case = R.far_end_case()
+    ans = R.regions_of(case)
+    assert len(ans[0]) >= 3 and ans[1][-1] == case[2] and (case[0] + 4).min() > case[3][2]
+    d = 3_000_000
+    moved = R.regions_of(R.shifted(case, d))
+    want = R.shift_answer(ans, d)
+    assert all(np.array_equal(a, b) and a.dtype == b.dtype for a, b in zip(moved[:6], want[:6])) and moved[6:] == want[6:]
+    assert R.shifted(case, 2 ** 31 - 1 - case[2])[2] == 2 ** 31 - 1
+
+
+def test_wide_window_cases_keep_regions_the_large_window_decides():
+    cases = R.wide_window_cases()
+    assert all(c[3][2] == R.MAX_WINDOW and c[2] == 120_000 < R.SEGMENT for c in cases)      # every dense range is the whole chromosome
+    assert [len(c[5]) for c in cases] == [64, 2, 2] and cases[2][3][0] == R.MAX_WINDOW
+    answers = [R.regions_of(c) for c in cases]
+    assert all(len(a[0]) >= 1 for a in answers)
+    assert all(np.array_equal(a, b) for a, b in zip(answers[0], answers[1]))
+    opened = R.regions_of(cases[0][:6] + (R.OPEN,))
+    assert opened[7] > answers[0][7]                          # thr_large takes significant bases away
+    assert (answers[2][1] - answers[2][0]).max() > R.SHORT_MAX
