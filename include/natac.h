@@ -77,7 +77,9 @@ enum {
     NATAC_T_BACKGROUND = 3, /* BiasTrack.calculateBackgroundSignal   NucleosomeCalling.py:49-64  (nucleoatac_background; an output only with
                              * --write_all: after the FFT kernel it is formed on the first download / track_ptr / writer request) */
     NATAC_T_NORM = 4,       /* NormSignalTrack                       NucleosomeCalling.py:38-43  (nucleoatac_signal) */
-    NATAC_T_SMOOTH = 5,     /* NucChunk.smoothSignal                 NucleosomeCalling.py:274-283 (nucleoatac_signal.smooth) */
+    NATAC_T_SMOOTH = 5,     /* NucChunk.smoothSignal                 NucleosomeCalling.py:274-283 (nucleoatac_signal.smooth; with smooth_sd 10
+                             * and chunks up to 4,096 bases it is formed by natac_run_peaks, or on the first other request, from the
+                             * T_NORM and the window natac_run_nuc ran with) */
     NATAC_T_OCC = 6,        /* OccupancyTrack.smoothed_vals AFTER call_peaks' in-place NaN fill (Occupancy.py:147-153, utils.py:86-91) */
     NATAC_T_OCC_LOWER = 7,  /* smoothed_lower */
     NATAC_T_OCC_UPPER = 8,  /* smoothed_upper */

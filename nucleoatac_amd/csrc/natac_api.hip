@@ -224,6 +224,8 @@ int natac_ctx_create(int device_id, natac_ctx **out) {
         c->occ_force_general = e && e[0] == '1';
         e = getenv("NATAC_OCC_ORDER");     // NATAC_OCC_ORDER=0: natac_occ_decide visits its tiles in chunk order (A-B timing of the ordering)
         c->occ_ordered = !(e && e[0] == '0');
+        e = getenv("NATAC_SMOOTH_FUSED");  // NATAC_SMOOTH_FUSED=0: T_SMOOTH is written by natac_run_nuc, never by the peak search (validation / A-B timing)
+        c->smooth_fused = !(e && e[0] == '0');
     }
     *out = c;
     return NATAC_OK;
@@ -548,13 +550,21 @@ static int ensure_window(natac_ctx *c, PoolBuf<double> &slot, int *slotM, double
     if (slot && *slotM == M && *slotsd == sd) return NATAC_OK;
     HIPCHK(sync_all(c));
     // scipy.signal.gaussian(M, sd): exp(-0.5 (n/sd)^2), n = arange(M) - (M-1)/2   (pyatac/utils.py:40)
-    std::vector<double> w((size_t)M);
+    std::vector<double> w((size_t)3 * M);
     for (int i = 0; i < M; ++i) {
         double n = (double)i - (M - 1) / 2.0;
         double q = n / sd;
         w[i] = std::exp(-0.5 * (q * q));
     }
-    int rc = dev_upload(c, slot, w.data(), (size_t)M);
+    // behind the window, the denominators of a base next to a chunk end, in the kernels' order (acc = fma(w, 1, acc) from 0):
+    // w[M + m] = w[0] + .. + w[m] (the taps left when the window hangs over the chunk's start), w[2 M + k] = w[k] + .. + w[M - 1] (its end)
+    for (int m = 0; m < M; ++m) w[M + m] = (m ? w[M + m - 1] : 0.0) + w[m];
+    for (int k = 0; k < M; ++k) {
+        double acc = 0.0;
+        for (int i = k; i < M; ++i) acc = acc + w[i];
+        w[2 * M + k] = acc;
+    }
+    int rc = dev_upload(c, slot, w.data(), (size_t)3 * M);
     if (rc) return rc;
     HIPCHK(sync_all(c));
     if (slotsum) {
@@ -762,6 +772,29 @@ static int ensure_track(natac_batch *b, int t) {
     return dev_alloc(b->d_track[t], (size_t)b->total_bp);  // INS uses the first half of a double slot (int32)
 }
 
+// SMOOTH = the clamped NaN-aware Gaussian of NORM, window c->d_win_nuc (M values); the caller has built d_tiles1k for M = 61
+static void launch_nuc_smooth(natac_batch *b, const ChunkTable &ct, int M) {
+    natac_ctx *c = b->ctx;
+    const int h = (M - 1) / 2;
+    if (h == 30) {      // the cli's smooth_sd = 10: four bases per lane
+        hipLaunchKernelGGL((natac_smooth_same4<true, 30>), dim3(b->n_tiles1k), dim3(256), (size_t)8 * SM4_S(30) * sizeof(double),
+                           c->stream, ct, b->d_tiles1k, c->d_win_nuc, c->win_nuc_sum, b->d_track[NATAC_T_NORM],
+                           b->d_track[NATAC_T_SMOOTH]);
+    } else {
+        const size_t lds = ((size_t)2 * (256 + 2 * h)) * sizeof(double);
+        hipLaunchKernelGGL((natac_smooth_same<true>), dim3(b->n_tiles256), dim3(256), lds, c->stream, ct, b->d_tiles256,
+                           c->d_win_nuc, M, c->win_nuc_sum, b->d_track[NATAC_T_NORM], b->d_track[NATAC_T_SMOOTH]);
+    }
+}
+
+// chunks natac_peaks_chunk_reg<NJ, 256> covers: the peak search can form SMOOTH itself
+static bool peaks_can_smooth(const natac_batch *b, int M) {
+    if (!b->ctx->smooth_fused || (M - 1) / 2 != PK_SM_H) return false;
+    for (int i = 0; i < b->nc; ++i)
+        if (b->h_len[i] > 4096) return false;
+    return true;
+}
+
 int natac_run_nuc(natac_batch *b, double smooth_sd) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     natac_ctx *c = b->ctx;
@@ -808,7 +841,9 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
     const VMatDev vm = make_vmat(c);
     natac_ctx::Ev ev;
     if (!b->d_ranges256 && (rc = dev_alloc(b->d_ranges256, (size_t)b->n_tiles256))) return rc;
-    if ((M - 1) / 2 == 30 && !b->d_tiles1k && (rc = build_tiles(b, 1024, b->d_tiles1k, &b->n_tiles1k))) return rc;
+    // the default pass reads SMOOTH in the peak search first, and that can form it from the chunk it holds: left pending then
+    const bool smooth_later = peaks_can_smooth(b, M);
+    if (!smooth_later && (M - 1) / 2 == 30 && !b->d_tiles1k && (rc = build_tiles(b, 1024, b->d_tiles1k, &b->n_tiles1k))) return rc;
     prof_begin(c, NATAC_K_FRAG_GATHER, ev);
     if (b->ranges256_w != c->vw) {
         hipLaunchKernelGGL(natac_tile_ranges256, dim3((b->n_tiles256 + 255) / 256), dim3(256), 0, c->stream, ct, b->d_tiles256,
@@ -849,22 +884,16 @@ int natac_run_nuc(natac_batch *b, double smooth_sd) {
                            b->d_track[NATAC_T_NORM], b->d_bnum, b->d_bcov);
     }
     prof_end(c, ev);
-    prof_begin(c, NATAC_K_SMOOTH_NUC, ev);
-    {
-        const int h = (M - 1) / 2;
-        if (h == 30) {      // the cli's smooth_sd = 10: four bases per lane
-            hipLaunchKernelGGL((natac_smooth_same4<true, 30>), dim3(b->n_tiles1k), dim3(256), (size_t)8 * SM4_S(30) * sizeof(double),
-                               c->stream, ct, b->d_tiles1k, c->d_win_nuc, c->win_nuc_sum, b->d_track[NATAC_T_NORM],
-                               b->d_track[NATAC_T_SMOOTH]);
-        } else {
-            const size_t lds = ((size_t)2 * (256 + 2 * h)) * sizeof(double);
-            hipLaunchKernelGGL((natac_smooth_same<true>), dim3(b->n_tiles256), dim3(256), lds, c->stream, ct, b->d_tiles256,
-                               c->d_win_nuc, M, c->win_nuc_sum, b->d_track[NATAC_T_NORM], b->d_track[NATAC_T_SMOOTH]);
-        }
+    if (!smooth_later) {
+        prof_begin(c, NATAC_K_SMOOTH_NUC, ev);
+        launch_nuc_smooth(b, ct, M);
+        prof_end(c, ev);
     }
-    prof_end(c, ev);
     HIPCHK(hipGetLastError());
     for (int t : {NATAC_T_NUC_COV, NATAC_T_NFR_COV, NATAC_T_RAW, NATAC_T_NORM, NATAC_T_SMOOTH}) b->out.track[t] = TS_RUN;
+    if (smooth_later) b->out.track[NATAC_T_SMOOTH] = TS_PENDING;
+    b->out.smooth_M = M;
+    b->out.smooth_sd = smooth_sd;
     b->out.track[NATAC_T_BACKGROUND] = use_fft ? TS_PENDING : TS_RUN;
     b->out.bg_gen = c->model_gen;
     b->out.nuc_w = c->vw;
@@ -954,6 +983,24 @@ static int materialise_prefill(natac_batch *b) {
     return NATAC_OK;
 }
 
+// SMOOTH that natac_run_nuc left to the peak search and another reader asks for first (a download, a writer, a peak search
+// the fused kernel does not cover, natac_batch_set_track about to replace NORM): the smoothing kernels natac_run_nuc would have run
+static int materialise_smooth(natac_batch *b) {
+    natac_ctx *c = b->ctx;
+    int rc;
+    // the window natac_run_nuc was asked for; the context's may be another batch's by now
+    if ((rc = ensure_window(c, c->d_win_nuc, &c->win_nuc_M, &c->win_nuc_sd, b->out.smooth_M, b->out.smooth_sd, &c->win_nuc_sum))) return rc;
+    if ((b->out.smooth_M - 1) / 2 == 30 && !b->d_tiles1k && (rc = build_tiles(b, 1024, b->d_tiles1k, &b->n_tiles1k))) return rc;
+    const ChunkTable ct = make_table(b);
+    natac_ctx::Ev ev;
+    prof_begin(c, NATAC_K_SMOOTH_NUC, ev);
+    launch_nuc_smooth(b, ct, b->out.smooth_M);
+    prof_end(c, ev);
+    HIPCHK(hipGetLastError());
+    b->out.track[NATAC_T_SMOOTH] = TS_RUN;
+    return NATAC_OK;
+}
+
 // Every read of an output track goes through here: NATAC_E_STATE (before any HIP call) if it holds nothing, formed if pending.
 static int need_track(natac_batch *b, int t) {
     static const char *const names[NATAC_T_COUNT] = {"NUC_COV", "NFR_COV", "RAW", "BACKGROUND", "NORM", "SMOOTH", "OCC", "OCC_LOWER",
@@ -967,6 +1014,7 @@ static int need_track(natac_batch *b, int t) {
         if (rc) return rc;
     }
     HIPCHK(hipSetDevice(b->ctx->device));
+    if (t == NATAC_T_SMOOTH) return materialise_smooth(b);
     return t == NATAC_T_BACKGROUND ? materialise_bg(b) : materialise_prefill(b);
 }
 
@@ -1430,8 +1478,23 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     return NATAC_OK;
 }
 
+// lists of the register variants of the peak search (natac_peaks_chunk_reg): slots per chunk, and whether a wave's share of them
+// holds its nj survivor masks (else the kernel keeps the masks in registers)
+static int peaks_list_cap(int maxL, int order) { return (std::min(PEAK_MAX, maxL / (order + 1) + 2) + 7) & ~7; }
+
+// natac_run_peaks with SMOOTH still pending (so peaks_can_smooth() held): does the search take the kernel arm that forms it?
+// The 256-thread register variant with its masks in LDS
+static bool peaks_smooth_arm(const natac_batch *b, int order) {
+    if (order < 1 || order > 255) return false;
+    int maxL = 0;
+    for (int i = 0; i < b->nc; ++i) maxL = std::max(maxL, b->h_len[i]);
+    const int region = peaks_list_cap(maxL, order) * (int)(sizeof(double) + sizeof(int) + 1), nj = (maxL + 255) / 256;
+    return ((region / 4) & ~7) >= nj * 8;
+}
+
+// form_smooth: sig_b is the batch's pending SMOOTH and peaks_smooth_arm() holds -- the search forms it from sig_a (the batch's NORM)
 static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig_b, bool with_stats, double min_signal, int sep,
-                          int boundary, int order, const double *jitter, int64_t n_jitter, int64_t *n_cand) {
+                          int boundary, int order, const double *jitter, int64_t n_jitter, int64_t *n_cand, bool form_smooth = false) {
     if (!b || !jitter || !n_cand) return fail(NATAC_E_ARG, "null argument");
     natac_ctx *c = b->ctx;
     if (order < 1 || order > 255 || sep < 1 || boundary < 0) return fail(NATAC_E_ARG, "bad peak parameters");
@@ -1462,6 +1525,9 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     }
     if (!b->d_pk_count && (rc = dev_alloc(b->d_pk_count, (size_t)b->nc))) return rc;
     if (!b->d_pk_offs && (rc = dev_alloc(b->d_pk_offs, (size_t)b->nc + 1))) return rc;
+    // the window natac_run_nuc was asked for; the context's may be another batch's by now
+    if (form_smooth &&
+        (rc = ensure_window(c, c->d_win_nuc, &c->win_nuc_M, &c->win_nuc_sd, b->out.smooth_M, b->out.smooth_sd, &c->win_nuc_sum))) return rc;
     const ChunkTable ct = make_table(b);
     const double *norm = sig_a, *sm = sig_b;
     natac_ctx::Ev ev;
@@ -1469,20 +1535,22 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     // bit 1 of the status words belongs to the peak search: it describes this one
     hipLaunchKernelGGL(natac_status_clear, dim3((b->nc + 255) / 256), dim3(256), 0, c->stream, b->d_status, b->nc, 2);
     {   // one workgroup per chunk: LDS = the jittered signal (or a segment of it) + the chunk's list of maxima
-        const int pk_cap = (std::min(PEAK_MAX, maxL / (order + 1) + 2) + 7) & ~7;
+        const int pk_cap = peaks_list_cap(maxL, order);
         const size_t lds_lists = (size_t)pk_cap * (sizeof(double) + sizeof(int) + 1);
         const int bt = maxL <= 4096 ? 256 : 1024;               // threads per workgroup of the register variant
         const int nj = (maxL + bt - 1) / bt;
-        const size_t lds_reg = (size_t)((bt * nj + 2 * order + 1) & ~1) * sizeof(double) + lds_lists;
+        const size_t lds_reg = (size_t)peaks_reg_ysn(bt * nj, order, form_smooth) * sizeof(double) + lds_lists;
+        double *sm_out = form_smooth ? b->d_track[NATAC_T_SMOOTH].get() : nullptr;
+        if (form_smooth) sm = nullptr;                           // not a signal yet
 #define NATAC_PEAKS_REG(NJ, BT)                                                                                                    \
     case NJ: {                                                                                                                     \
-        auto kfn = natac_peaks_chunk_reg<NJ, BT>;                                                                                  \
+        auto kfn = form_smooth ? natac_peaks_chunk_reg<NJ, BT, BT == 256> : natac_peaks_chunk_reg<NJ, BT, false>;                  \
         if (lds_reg > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg)); \
         hipLaunchKernelGGL(kfn, dim3(b->nc), dim3(BT), lds_reg, c->stream, ct, norm, sm, b->d_jitter, min_signal, boundary, order, sep, \
-                           pk_cap, b->d_cap_off, b->d_slot, b->d_pk_count, b->d_status);                                          \
+                           pk_cap, b->d_cap_off, b->d_slot, b->d_pk_count, b->d_status, c->d_win_nuc, c->win_nuc_sum, sm_out);     \
         break;                                                                                                                     \
     }
-        if (bt == 256) {
+        if (bt == 256) {        // form_smooth: these only (peaks_smooth_arm)
             switch (nj) {
                 NATAC_PEAKS_REG(1, 256) NATAC_PEAKS_REG(2, 256) NATAC_PEAKS_REG(3, 256) NATAC_PEAKS_REG(4, 256) NATAC_PEAKS_REG(5, 256)
                 NATAC_PEAKS_REG(6, 256) NATAC_PEAKS_REG(7, 256) NATAC_PEAKS_REG(8, 256) NATAC_PEAKS_REG(9, 256) NATAC_PEAKS_REG(10, 256)
@@ -1518,6 +1586,7 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     hipLaunchKernelGGL(natac_scan_counts, dim3(1), dim3(1024), 0, c->stream, b->d_pk_count, b->nc, b->d_pk_offs);
     long long total = 0;
     HIPCHK(hipGetLastError());
+    if (form_smooth) b->out.track[NATAC_T_SMOOTH] = TS_RUN;
     HIPCHK(hipMemcpyAsync(&total, b->d_pk_offs + b->nc, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (total > b->pk_cap) {      // pk_cap is the stride of all three: set once they all exist, 0 while they do not
@@ -1554,9 +1623,12 @@ int natac_run_peaks(natac_batch *b, double min_signal, int sep, int boundary, in
                     int64_t *n_cand) {
     if (!b) return fail(NATAC_E_ARG, "batch is NULL");
     int rc;
-    if ((rc = need_track(b, NATAC_T_SMOOTH)) || (rc = need_candidate_inputs(b)) || (rc = need_nuc_geometry(b, "natac_run_peaks"))) return rc;
+    // a SMOOTH that natac_run_nuc left pending (NORM is still its own then) is formed by the search where its kernel can, else here
+    const bool form_smooth = b->out.track[NATAC_T_SMOOTH] == TS_PENDING && peaks_smooth_arm(b, order);
+    if ((!form_smooth && (rc = need_track(b, NATAC_T_SMOOTH))) || (rc = need_candidate_inputs(b)) ||
+        (rc = need_nuc_geometry(b, "natac_run_peaks"))) return rc;
     return run_peaks_impl(b, b->d_track[NATAC_T_NORM], b->d_track[NATAC_T_SMOOTH], true, min_signal, sep, boundary, order, jitter,
-                          n_jitter, n_cand);
+                          n_jitter, n_cand, form_smooth);
 }
 
 int natac_run_track_peaks(natac_batch *b, int track, double min_signal, int sep, int boundary, int order, const double *jitter,
@@ -1698,6 +1770,8 @@ int natac_batch_set_track(natac_batch *b, int track, const double *vals, size_t 
     int rc;
     // a pending background is formed from NUC_COV: it keeps the values natac_run_nuc gave it
     if (track == NATAC_T_NUC_COV && b->out.track[NATAC_T_BACKGROUND] == TS_PENDING && (rc = materialise_bg(b))) return rc;
+    // ... and a pending SMOOTH is formed from NORM
+    if (track == NATAC_T_NORM && b->out.track[NATAC_T_SMOOTH] == TS_PENDING && (rc = materialise_smooth(b))) return rc;
     HIPCHK(sync_all(c));
     if ((rc = ensure_track(b, track))) return rc;
     HIPCHK(hipMemcpyAsync(b->d_track[track], vals, n * sizeof(double), hipMemcpyHostToDevice, c->stream));

@@ -1982,18 +1982,39 @@ __global__ void __launch_bounds__(256) natac_peaks_chunk(ChunkTable ct, const do
 // bases: gfx950 gives a workgroup up to 160 KB of LDS): every thread keeps its NJ bases in registers,
 // so the signal is read from memory once, with all loads of a thread in flight together (the general kernel above walks
 // the chunk three times with one dependent load per iteration).  LDS as above with seg = 256 NJ.
-template <int NJ, int BT>
+//
+// SMOOTH: the second signal does not exist yet -- it is natac_smooth_same<true> of `norm` for the window M = 2 PK_SM_H + 1, and this
+// workgroup forms it (it holds the whole chunk anyway), writes it to smooth_out and searches norm + that: one read of norm and one write
+// of the smoothed track instead of a smoothing kernel's read + write and two more reads here.  Same bits as natac_smooth_same:
+//   numerators   a thread takes NJ consecutive bases and slides over their NJ + 2 H inputs (clamped, NaN and beyond-the-chunk -> 0, staged
+//                where the jittered signal goes later), descending, so every output adds its taps in ascending n;
+//   denominators per base, after the numerators went through LDS back to the search's layout (lane = base: coalesced stores): which of
+//                a base's 2 H + 1 inputs hold a number is a bit field cut from the chunk's validity mask (ballots of the staging loop).
+//                All of them (a wave sees that for its 64 bases of a row in three words of the mask): the host-formed win_sum.  Only a
+//                chunk end missing: the host-formed sum of the taps that are left, win[M ..] / win[2 M ..] (ensure_window), one load.
+//                Else (a NaN under the window) the fma sum over the set bits.  The first cut ran that 61-trip loop for the 60 bases
+//                at a chunk's ends too, with a vector load per trip inside a divergent branch: 1.1 ms per step, the whole gain.
+// LDS: BT NJ + max(2 order + 1, 2 H) doubles (even) before the lists.
+constexpr int PK_SM_H = 30;      // the cli's smooth_sd = 10
+
+__host__ __device__ constexpr int peaks_reg_ysn(int bt_nj, int order, bool smooth) {
+    return (bt_nj + ((smooth && 2 * PK_SM_H > 2 * order + 1) ? 2 * PK_SM_H : 2 * order + 1)) & ~1;
+}
+
+template <int NJ, int BT, bool SMOOTH = false>
 __global__ void __launch_bounds__(BT) natac_peaks_chunk_reg(ChunkTable ct, const double *__restrict__ norm,
                                                                const double *__restrict__ smooth, const double *__restrict__ jitter,
                                                                double min_signal, int boundary, int order, int sep, int pk_cap,
                                                                const long long *__restrict__ cap_off, int *__restrict__ cand_slot,
-                                                               int *__restrict__ count, int *__restrict__ status) {
+                                                               int *__restrict__ count, int *__restrict__ status,
+                                                               const double *__restrict__ win, double win_sum,
+                                                               double *__restrict__ smooth_out) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int NW = BT / 64;
     __shared__ double red[NW];
     __shared__ int wave_cnt[16];
     __shared__ int row_cnt[NW * NJ];
-    const int ysn = (BT * NJ + 2 * order + 1) & ~1;
+    const int ysn = peaks_reg_ysn(BT * NJ, order, SMOOTH);
     double *ys = smem;                              // jittered signal, index u <-> base clip(u - order)
     double *sig = ys + ysn;
     int *pos = (int *)(sig + pk_cap);
@@ -2003,6 +2024,93 @@ __global__ void __launch_bounds__(BT) natac_peaks_chunk_reg(ChunkTable ct, const
     const long long ob = ct.out_off[chunk];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double v[NJ], jt[NJ];
+    if constexpr (SMOOTH) {
+        constexpr int H = PK_SM_H, M = 2 * H + 1;
+        static_assert(BT >= 2 * H && M < 64, "the halo is zeroed by one pass of the workgroup; a window's validity bits fit one word");
+        __shared__ unsigned long long okb[NW * NJ + 2];   // bit b & 63 of word 1 + (b >> 6): base b holds a number; first and last word: none do
+        double *xs = smem;                          // index u <-> base u - H; after the numerators are formed: their exchange, index = base
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int g = threadIdx.x + BT * j;
+            double x = __builtin_nan("");
+            if (g < L) x = norm[ob + g];
+            v[j] = x;
+            const bool okv = x == x;
+            xs[H + g] = okv ? (x < 0 ? 0.0 : x) : 0.0;
+            const unsigned long long m = __ballot(okv);
+            if (lane == 0) okb[1 + NW * j + wave] = m;
+        }
+        if (threadIdx.x < 2 * H) xs[threadIdx.x < H ? threadIdx.x : BT * NJ + threadIdx.x] = 0.0;
+        if (threadIdx.x == 0) { okb[0] = 0ull; okb[NW * NJ + 1] = 0ull; }
+        __syncthreads();
+        const int g0 = threadIdx.x * NJ;
+        double num[NJ];
+#pragma unroll
+        for (int o = 0; o < NJ; ++o) num[o] = 0.0;
+        if (g0 < L) {
+            // the window values are wave-uniform: scalar loads, SGPR operands of the FMAs
+#pragma unroll
+            for (int kk = 0; kk < 2 * H + NJ; ++kk) {
+                const int k = 2 * H + NJ - 1 - kk;          // inputs in descending order = taps n ascending for every output
+                const double r = xs[g0 + k];
+#pragma unroll
+                for (int o = 0; o < NJ; ++o) {
+                    const int n = o + 2 * H - k;
+                    if (n >= 0 && n < M) num[o] = fma(win[n], r, num[o]);
+                }
+            }
+        }
+        __syncthreads();
+        if (g0 < L) {
+#pragma unroll
+            for (int o = 0; o < NJ; ++o) xs[g0 + o] = num[o];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int g = threadIdx.x + BT * j;
+            const bool in = g < L;
+            jt[j] = 0.0;
+            if (in) jt[j] = jitter[g];
+            double den = win_sum;
+            // the windows of this wave's 64 bases of the row lie in three words of the mask: all set (most rows of most chunks),
+            // every denominator is win_sum
+            const int iw = NW * j + wave;
+            constexpr unsigned long long HM = (1ull << H) - 1ull;
+            const bool clean = (okb[iw] >> (64 - H)) == HM && okb[iw + 1] == ~0ull && (okb[iw + 2] & HM) == HM;
+            if (__ballot(!clean) != 0ull) {
+                constexpr unsigned long long FULL = (1ull << M) - 1ull;
+                const int p = g - H + 64, i = p >> 6, sh = p & 63;
+                unsigned long long f = okb[i] >> sh;
+                if (sh) f |= okb[i + 1] << (64 - sh);
+                f &= FULL;                              // bit q <-> base g - H + q <-> tap n = 2 H - q
+                bool generic = false;
+                if (in && f != FULL) {
+                    // a chunk end under the window and nothing else: the taps are n = 0 .. 2 H - k (the k bases before the chunk are
+                    // missing) or n = k .. 2 H (the k after it): the host-formed sums of exactly those, win[M + .] and win[2 M + .]
+                    const int lo = __builtin_ctzll(f | (1ull << M)), hi = __builtin_clzll(f | 1ull) - (64 - M);
+                    if (f == 0ull) den = 0.0;
+                    else if (f == ((FULL >> lo) << lo)) den = win[M + 2 * H - lo];
+                    else if (f == (FULL >> hi)) den = win[2 * M + hi];
+                    else generic = true;
+                }
+                if (__ballot(generic) != 0ull) {        // a NaN under a window.  Wave-uniform branch: the window values stay scalar loads
+                    double d = 0.0;
+#pragma unroll 8
+                    for (int n = 0; n < M; ++n) {
+                        const double wv = win[n];
+                        if ((f >> (2 * H - n)) & 1ull) d = fma(wv, 1.0, d);
+                    }
+                    if (generic) den = d;
+                }
+            }
+            if (in) {
+                const double s = (den == 0.0) ? __builtin_nan("") : xs[g] / den;
+                smooth_out[ob + g] = s;
+                v[j] += s;
+            }
+        }
+    } else {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int g = threadIdx.x + BT * j;
@@ -2012,6 +2120,7 @@ __global__ void __launch_bounds__(BT) natac_peaks_chunk_reg(ChunkTable ct, const
             v[j] = smooth ? norm[ob + g] + smooth[ob + g] : norm[ob + g];
             jt[j] = jitter[g];
         }
+    }
     }
     double mn = __builtin_inf();
 #pragma unroll

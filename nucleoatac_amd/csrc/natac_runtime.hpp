@@ -96,6 +96,7 @@ struct natac_ctx {
     // FFT background path: twiddles (once) and template spectra (per V-plot)
     PoolBuf<double> d_fft_tw, d_fft_k;
     PoolBuf<double> d_fft_mtab, d_fft_swt;   // natac_fft_edge_table_mfma (the edge pass of extended tiles)
+    bool smooth_fused = true;        // NATAC_SMOOTH_FUSED=0: natac_run_nuc smooths itself, the peak search reads both tracks (A-B timing / validation)
     bool bg_ext = true;              // NATAC_BG_EXT=0: no extended FFT tiles (A-B timing / validation of the edge pass)
     bool fft_dirty = true, bg_direct = false, occ_ordered = true, occ_zero_nfr = false;
     std::vector<double> h_sizes;
@@ -137,7 +138,8 @@ struct natac_ctx {
 };
 
 // What each output of a batch holds and who wrote it: the stages and natac_batch_set_track write it, every reader asks need_track().
-// PENDING: formed on the first request from what the stage left (BACKGROUND from d_bnum / d_bcov, OCC_PREFILL from the grids).
+// PENDING: formed on the first request from what the stage left (BACKGROUND from d_bnum / d_bcov, OCC_PREFILL from the grids, SMOOTH
+// from NORM with the window natac_run_nuc was asked for -- by the peak search itself if that is the first reader).
 enum TrackState : unsigned char { TS_EMPTY = 0, TS_PENDING, TS_RUN /* a natac_run_* stage */, TS_HOST /* natac_batch_set_track */ };
 struct BatchOutputs {
     TrackState track[NATAC_T_COUNT] = {};
@@ -145,6 +147,8 @@ struct BatchOutputs {
     long long bg_gen = -1;            // model generation d_bnum / d_bcov were formed with (natac_run_nuc); -1: none
     int nuc_w = -1, nuc_lower = -1, nuc_upper = -1;   // V-plot geometry natac_run_nuc ran with (its tracks depend on it); -1: no run
     bool occ_cov_by_nuc = false;      // OCC_COV holds natac_run_nuc's nuc_cov + nfr_cov for that geometry
+    int smooth_M = 0;                 // window (length, sd) natac_run_nuc was asked for: what a pending SMOOTH is formed with
+    double smooth_sd = 0;
     // occupancy geometry natac_run_occ ran with (the grids and the OCC tracks depend on it); -1: no run
     int occ_step = -1, occ_half = -1, occ_flank = -1, occ_upper = -1;
 };
