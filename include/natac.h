@@ -53,9 +53,9 @@ extern "C" {
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
- * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`); the binding refuses another
- * version */
-#define NATAC_ABI_VERSION 16
+ * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan); the binding
+ * refuses another version */
+#define NATAC_ABI_VERSION 17
 
 enum {
     NATAC_OK = 0,
@@ -259,6 +259,14 @@ int natac_download_peaks(natac_batch *b, int64_t n_cand, int32_t *cand_chunk, in
  * boundary = sep/2, order = 1).  Fetch positions with natac_download_peaks (lr / var / z may be NULL). */
 int natac_run_track_peaks(natac_batch *b, int track, double min_signal, int sep, int boundary, int order,
                           const double *jitter, int64_t n_jitter, int64_t *n_peaks);
+/* How the three searches above launch for a batch whose longest chunk has max_len bases (host only: no context, no GPU needed).
+ * *kernel: 0 = a register variant natac_peaks_chunk_reg<*nj, *bt>, 1 = the segmented natac_peaks_chunk (*bt 256, *nj 0, *mask -1);
+ * *mask: where the register variant keeps its row masks, 0 = registers, 1 = LDS with a two-phase survivor list, 2 = LDS, direct
+ * test; *global_lists: the segmented kernel keeps the lists of its long chunks in device memory; *forms_smooth: natac_run_peaks
+ * forms a pending NATAC_T_SMOOTH itself; *pk_cap: maxima per chunk held in LDS; lds_bytes[2]: dynamic LDS without / with that
+ * smoothing.  NATAC_E_ARG for max_len < 1 or an order outside 1..255. */
+int natac_peaks_plan(int32_t max_len, int32_t order, int32_t *kernel, int32_t *bt, int32_t *nj, int32_t *mask,
+                     int32_t *global_lists, int32_t *forms_smooth, int32_t *pk_cap, int64_t *lds_bytes);
 /* OccChunk.callPeaks + OccChunk.getNucDist for every chunk on the device (nucleoatac/Occupancy.py:225-240; needs natac_run_occ):
  * call_peaks(smoothed_vals, sep, min_signal = min_occ) as natac_run_track_peaks(NATAC_T_OCC, ...) does it, then per peak the
  * OccPeak values (occ, lower, upper, reads = cov) and keep = (lower > min_occ && reads > 0), and per chunk

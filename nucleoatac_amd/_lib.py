@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 16     # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 17    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -69,6 +69,7 @@ SIGNATURES = {
     "natac_run_peaks": (C.c_int, [_vp, _f64, C.c_int, C.c_int, C.c_int, _vp, _i64, C.POINTER(_i64)]),
     "natac_download_peaks": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "natac_run_track_peaks": (C.c_int, [_vp, C.c_int, _f64, C.c_int, C.c_int, C.c_int, _vp, _i64, C.POINTER(_i64)]),
+    "natac_peaks_plan": (C.c_int, [_i32, _i32] + [C.POINTER(_i32)] * 7 + [C.POINTER(_i64)]),
     "natac_run_occ_peaks": (C.c_int, [_vp, _f64, C.c_int, _vp, _i64, C.POINTER(_i64)]),
     "natac_download_occ_peaks": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "natac_download_nuc_dist": (C.c_int, [_vp, _vp, _sz]),

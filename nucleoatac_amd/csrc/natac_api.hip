@@ -29,6 +29,7 @@
 #include "natac_cellqc.hpp"
 #include "natac_lsi.hpp"
 #include "natac_peakcall.hpp"
+#include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"
 #include "natac_trackio.hpp"
@@ -655,6 +656,7 @@ int natac_batch_create(natac_ctx *c, int32_t nc, const int32_t *chunk_len, const
             delete b; return fail(NATAC_E_ARG, "bias slice of chunk %d must cover [start-%d, end+%d)", i, bias_left, bias_right);
         }
         b->h_out_off[i + 1] = b->h_out_off[i] + chunk_len[i];
+        b->max_len = std::max(b->max_len, chunk_len[i]);
     }
     b->total_bp = b->h_out_off[nc];
     b->nb = bias_off ? bias_off[nc] : 0;
@@ -719,8 +721,7 @@ int natac_batch_create_from_seq(natac_ctx *c, int32_t nc, const int32_t *chunk_l
     const unsigned char *d_n = dc.upload((const unsigned char *)nucleotides, (size_t)nrow);
     const double *d_p = dc.upload(log_pwm, (size_t)nrow * K);
     if (dc.ok()) {
-        int maxlen = 0;
-        for (int i = 0; i < nc; ++i) maxlen = std::max(maxlen, chunk_len[i] + bias_left + bias_right);
+        const int maxlen = b->max_len + bias_left + bias_right;
         const unsigned gx = (unsigned)std::min(16, (maxlen + 1023) / 1024);
         hipLaunchKernelGGL(natac_pwm_score_chunks, dim3(gx, (unsigned)nc), dim3(256), 0, c->stream, d_s, d_so, b->d_bias_off, d_p, d_n, nrow, K,
                            b->d_bias);
@@ -787,12 +788,9 @@ static void launch_nuc_smooth(natac_batch *b, const ChunkTable &ct, int M) {
     }
 }
 
-// chunks natac_peaks_chunk_reg<NJ, 256> covers: the peak search can form SMOOTH itself
+// the peak search can form SMOOTH itself for some `order`: order 1 keeps the longest lists, so if any order's arm can, its arm can
 static bool peaks_can_smooth(const natac_batch *b, int M) {
-    if (!b->ctx->smooth_fused || (M - 1) / 2 != PK_SM_H) return false;
-    for (int i = 0; i < b->nc; ++i)
-        if (b->h_len[i] > 4096) return false;
-    return true;
+    return b->ctx->smooth_fused && (M - 1) / 2 == PK_SM_H && peaks_plan(b->max_len, 1).forms_smooth;
 }
 
 int natac_run_nuc(natac_batch *b, double smooth_sd) {
@@ -1257,8 +1255,7 @@ static int ins_launch(natac_batch *b, int lower, int upper) {
     const ChunkTable ct = make_table(b);
     natac_ctx::Ev ev;
     prof_begin(c, NATAC_K_INS, ev, c->stream);
-    int maxL = 0;
-    for (int i = 0; i < b->nc; ++i) maxL = std::max(maxL, b->h_len[i]);
+    const int maxL = b->max_len;
     if ((size_t)maxL * sizeof(int) <= 60 * 1024) {
         hipLaunchKernelGGL(natac_insertions_lds, dim3(b->nc), dim3(256), (size_t)maxL * sizeof(int), c->stream, ct, lower, upper,
                            (int *)b->d_track[NATAC_T_INS].get());
@@ -1478,18 +1475,9 @@ int natac_run_candidates_cov(natac_batch *b, int64_t n_cand, const int32_t *cand
     return NATAC_OK;
 }
 
-// lists of the register variants of the peak search (natac_peaks_chunk_reg): slots per chunk, and whether a wave's share of them
-// holds its nj survivor masks (else the kernel keeps the masks in registers)
-static int peaks_list_cap(int maxL, int order) { return (std::min(PEAK_MAX, maxL / (order + 1) + 2) + 7) & ~7; }
-
-// natac_run_peaks with SMOOTH still pending (so peaks_can_smooth() held): does the search take the kernel arm that forms it?
-// The 256-thread register variant with its masks in LDS
+// natac_run_peaks with SMOOTH still pending (so peaks_can_smooth() held): does the search take a kernel arm that forms it?
 static bool peaks_smooth_arm(const natac_batch *b, int order) {
-    if (order < 1 || order > 255) return false;
-    int maxL = 0;
-    for (int i = 0; i < b->nc; ++i) maxL = std::max(maxL, b->h_len[i]);
-    const int region = peaks_list_cap(maxL, order) * (int)(sizeof(double) + sizeof(int) + 1), nj = (maxL + 255) / 256;
-    return ((region / 4) & ~7) >= nj * 8;
+    return order >= 1 && order <= 255 && peaks_plan(b->max_len, order).forms_smooth;
 }
 
 // form_smooth: sig_b is the batch's pending SMOOTH and peaks_smooth_arm() holds -- the search forms it from sig_a (the batch's NORM)
@@ -1498,8 +1486,7 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     if (!b || !jitter || !n_cand) return fail(NATAC_E_ARG, "null argument");
     natac_ctx *c = b->ctx;
     if (order < 1 || order > 255 || sep < 1 || boundary < 0) return fail(NATAC_E_ARG, "bad peak parameters");
-    int maxL = 0;
-    for (int i = 0; i < b->nc; ++i) maxL = std::max(maxL, b->h_len[i]);
+    const int maxL = b->max_len;
     if (n_jitter < maxL) return fail(NATAC_E_ARG, "jitter stream (%lld) shorter than the longest chunk (%d)", (long long)n_jitter, maxL);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(sync_all(c));
@@ -1528,62 +1515,19 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     // the window natac_run_nuc was asked for; the context's may be another batch's by now
     if (form_smooth &&
         (rc = ensure_window(c, c->d_win_nuc, &c->win_nuc_M, &c->win_nuc_sd, b->out.smooth_M, b->out.smooth_sd, &c->win_nuc_sum))) return rc;
-    const ChunkTable ct = make_table(b);
-    const double *norm = sig_a, *sm = sig_b;
+    const PeakPlan plan = peaks_plan(maxL, order);
+    PeakSearch s{sig_a, sig_b, b->d_jitter, min_signal, boundary, order, sep, b->d_cap_off, b->d_slot, b->d_pk_count, b->d_status,
+                 b->d_pk_offs, c->d_win_nuc, c->win_nuc_sum, form_smooth ? b->d_track[NATAC_T_SMOOTH].get() : nullptr};
+    if (plan.global_lists) {      // per slot: sig (8 bytes) + pos (4) + state (1), laid out as three arrays in one block
+        if (b->d_pk_big.size() < (size_t)b->slot_total * 2 + 2 && (rc = dev_alloc(b->d_pk_big, (size_t)b->slot_total * 2 + 2))) return rc;
+        s.big_sig = b->d_pk_big;
+        s.big_pos = (int *)(b->d_pk_big + b->slot_total);
+        s.big_state = (unsigned char *)(s.big_pos + b->slot_total);
+    }
     natac_ctx::Ev ev;
     prof_begin(c, NATAC_K_CAND, ev);
-    // bit 1 of the status words belongs to the peak search: it describes this one
-    hipLaunchKernelGGL(natac_status_clear, dim3((b->nc + 255) / 256), dim3(256), 0, c->stream, b->d_status, b->nc, 2);
-    {   // one workgroup per chunk: LDS = the jittered signal (or a segment of it) + the chunk's list of maxima
-        const int pk_cap = peaks_list_cap(maxL, order);
-        const size_t lds_lists = (size_t)pk_cap * (sizeof(double) + sizeof(int) + 1);
-        const int bt = maxL <= 4096 ? 256 : 1024;               // threads per workgroup of the register variant
-        const int nj = (maxL + bt - 1) / bt;
-        const size_t lds_reg = (size_t)peaks_reg_ysn(bt * nj, order, form_smooth) * sizeof(double) + lds_lists;
-        double *sm_out = form_smooth ? b->d_track[NATAC_T_SMOOTH].get() : nullptr;
-        if (form_smooth) sm = nullptr;                           // not a signal yet
-#define NATAC_PEAKS_REG(NJ, BT)                                                                                                    \
-    case NJ: {                                                                                                                     \
-        auto kfn = form_smooth ? natac_peaks_chunk_reg<NJ, BT, BT == 256> : natac_peaks_chunk_reg<NJ, BT, false>;                  \
-        if (lds_reg > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg)); \
-        hipLaunchKernelGGL(kfn, dim3(b->nc), dim3(BT), lds_reg, c->stream, ct, norm, sm, b->d_jitter, min_signal, boundary, order, sep, \
-                           pk_cap, b->d_cap_off, b->d_slot, b->d_pk_count, b->d_status, c->d_win_nuc, c->win_nuc_sum, sm_out);     \
-        break;                                                                                                                     \
-    }
-        if (bt == 256) {        // form_smooth: these only (peaks_smooth_arm)
-            switch (nj) {
-                NATAC_PEAKS_REG(1, 256) NATAC_PEAKS_REG(2, 256) NATAC_PEAKS_REG(3, 256) NATAC_PEAKS_REG(4, 256) NATAC_PEAKS_REG(5, 256)
-                NATAC_PEAKS_REG(6, 256) NATAC_PEAKS_REG(7, 256) NATAC_PEAKS_REG(8, 256) NATAC_PEAKS_REG(9, 256) NATAC_PEAKS_REG(10, 256)
-                NATAC_PEAKS_REG(11, 256) NATAC_PEAKS_REG(12, 256) NATAC_PEAKS_REG(13, 256) NATAC_PEAKS_REG(14, 256)
-                NATAC_PEAKS_REG(15, 256) NATAC_PEAKS_REG(16, 256)
-            }
-        } else if (nj <= 16 && lds_reg <= 150 * 1024) {        // chunks up to 16,384 bases: the whole chunk in LDS, 16 waves
-            switch (nj) {
-                NATAC_PEAKS_REG(5, 1024) NATAC_PEAKS_REG(6, 1024) NATAC_PEAKS_REG(7, 1024) NATAC_PEAKS_REG(8, 1024) NATAC_PEAKS_REG(9, 1024)
-                NATAC_PEAKS_REG(10, 1024) NATAC_PEAKS_REG(11, 1024) NATAC_PEAKS_REG(12, 1024) NATAC_PEAKS_REG(13, 1024)
-                NATAC_PEAKS_REG(14, 1024) NATAC_PEAKS_REG(15, 1024) NATAC_PEAKS_REG(16, 1024)
-            }
-        } else {   // longer still: segments of 4,096 bases, signal read per segment
-            const int seg = 4096;
-            const size_t lds = (size_t)((seg + 2 * order + 1) & ~1) * sizeof(double) + lds_lists;
-            double *big_sig = nullptr;
-            int *big_pos = nullptr;
-            unsigned char *big_state = nullptr;
-            if (maxL / (order + 1) + 2 > pk_cap) {      // some chunk can hold more maxima than the LDS lists: global lists for those
-                // per slot: sig (8 bytes) + pos (4) + state (1), laid out as three arrays in one block
-                if (b->d_pk_big.size() < (size_t)b->slot_total * 2 + 2 && (rc = dev_alloc(b->d_pk_big, (size_t)b->slot_total * 2 + 2)))
-                    return rc;
-                big_sig = b->d_pk_big;
-                big_pos = (int *)(b->d_pk_big + b->slot_total);
-                big_state = (unsigned char *)(big_pos + b->slot_total);
-            }
-            hipLaunchKernelGGL(natac_peaks_chunk, dim3(b->nc), dim3(256), lds, c->stream, ct, norm, sm, b->d_jitter, min_signal,
-                               boundary, order, sep, seg, pk_cap, b->d_cap_off, b->d_slot, b->d_pk_count, b->d_status, big_sig, big_pos,
-                               big_state);
-        }
-#undef NATAC_PEAKS_REG
-    }
-    hipLaunchKernelGGL(natac_scan_counts, dim3(1), dim3(1024), 0, c->stream, b->d_pk_count, b->nc, b->d_pk_offs);
+    const ChunkTable ct = make_table(b);
+    if ((rc = peaks_enqueue(plan, ct, b->nc, s, c->stream))) return rc;
     long long total = 0;
     HIPCHK(hipGetLastError());
     if (form_smooth) b->out.track[NATAC_T_SMOOTH] = TS_RUN;
@@ -1616,6 +1560,17 @@ static int run_peaks_impl(natac_batch *b, const double *sig_a, const double *sig
     HIPCHK(hipGetLastError());
     b->pk_n = total;
     *n_cand = total;
+    return NATAC_OK;
+}
+
+int natac_peaks_plan(int32_t max_len, int32_t order, int32_t *kernel, int32_t *bt, int32_t *nj, int32_t *mask, int32_t *global_lists,
+                     int32_t *forms_smooth, int32_t *pk_cap, int64_t *lds_bytes) {
+    if (!kernel || !bt || !nj || !mask || !global_lists || !forms_smooth || !pk_cap || !lds_bytes) return fail(NATAC_E_ARG, "null argument");
+    if (max_len < 1 || order < 1 || order > 255) return fail(NATAC_E_ARG, "natac_peaks_plan: a positive length and an order in 1..255");
+    const PeakPlan p = peaks_plan(max_len, order);
+    *kernel = p.kernel; *bt = p.bt; *nj = p.nj; *mask = p.mask; *global_lists = p.global_lists; *forms_smooth = p.forms_smooth;
+    *pk_cap = p.pk_cap;
+    lds_bytes[0] = (int64_t)p.lds; lds_bytes[1] = (int64_t)p.lds_smooth;
     return NATAC_OK;
 }
 

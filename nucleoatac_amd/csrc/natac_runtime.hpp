@@ -155,7 +155,7 @@ struct BatchOutputs {
 
 struct natac_batch {
     natac_ctx *ctx = nullptr;
-    int nc = 0;
+    int nc = 0, max_len = 0;          // chunks, and the longest one's bases
     long long nf = 0, nb = 0, total_bp = 0, total_grid = 0;
     int bias_left = 0, bias_right = 0;
     std::vector<int> h_len;

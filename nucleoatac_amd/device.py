@@ -60,6 +60,19 @@ def pool_trim():
     L.check(L.load().natac_pool_trim())
 
 
+def peaks_plan(max_len, order):
+    """how the peak searches launch for a batch whose longest chunk has max_len bases (natac_peaks_plan; needs no GPU): dict of
+    kernel ("reg" / "seg"), bt, nj (None for seg), mask ("registers" / "two_phase" / "direct", None for seg), global_lists,
+    forms_smooth, pk_cap, lds_bytes and lds_bytes_smooth"""
+    v = [C.c_int32() for _ in range(7)]
+    lds = (C.c_int64 * 2)()
+    L.check(L.load().natac_peaks_plan(int(max_len), int(order), *[C.byref(x) for x in v], lds))
+    kernel, bt, nj, mask, gl, fs, cap = [x.value for x in v]
+    seg = kernel == 1
+    return dict(kernel="seg" if seg else "reg", bt=bt, nj=None if seg else nj, mask=None if seg else ("registers", "two_phase", "direct")[mask],
+                global_lists=bool(gl), forms_smooth=bool(fs), pk_cap=cap, lds_bytes=lds[0], lds_bytes_smooth=lds[1])
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 

@@ -1,15 +1,13 @@
-"""Every dispatch arm of the device peak search (run_peaks_impl, nucleoatac_amd/csrc/natac_api.hip) against the host restatement
-of utils.call_peaks, chunk and position exact.
+"""Every dispatch arm of the device peak search (peaks_plan / peaks_enqueue, nucleoatac_amd/csrc/natac_peaks.hpp) against the host
+restatement of utils.call_peaks, chunk and position exact.
 
-run_peaks_impl picks the kernel from the LONGEST chunk of the batch (maxL) and `order`: natac_peaks_chunk_reg<NJ, 256> up to 4,096
+peaks_plan picks the kernel from the LONGEST chunk of the batch (maxL) and `order`: natac_peaks_chunk_reg<NJ, 256> up to 4,096
 bases, natac_peaks_chunk_reg<NJ, 1024> up to 16,384 bases while its LDS fits 150 KB, else the segmented natac_peaks_chunk with LDS
 or global peak lists.  Inside the register kernel the maxima test keeps the row masks in registers, runs two phases over a survivor
 list, or runs the direct test.  peak_arm() below restates that choice; test_cases_cover_every_arm (CPU) checks that the cases reach
-every arm and that the arms are the instances the source launches.  The register kernels keep at most PEAK_MAX maxima per chunk and
+every arm and that the restatement is the library's plan (natac_peaks_plan), field by field, for every maxL up to 20,000.  The register kernels keep at most PEAK_MAX maxima per chunk and
 flag a chunk with more (status value 2) for the drivers' host fallback: every search here predicts that flag on the host and checks
 it chunk by chunk."""
-import os
-import re
 from collections import namedtuple
 
 import numpy as np
@@ -19,23 +17,22 @@ from helpers import call_peaks_stable, golden
 from nucleoatac_amd import _lib as L
 from nucleoatac_amd.packing import PackedChunks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PEAK_MAX = 2048          # natac_kernels.hpp: constexpr int PEAK_MAX
+PEAK_MAX = 2048          # natac_peaks.hpp: constexpr int PEAK_MAX
 LDS_REG_MAX = 150 * 1024
 
 Arm = namedtuple("Arm", "kernel bt nj mask global_lists")
 
 
 def pk_cap_of(maxL, order):
-    """natac_api.hip, run_peaks_impl: const int pk_cap = (std::min(PEAK_MAX, maxL / (order + 1) + 2) + 7) & ~7"""
+    """natac_peaks.hpp, peaks_list_cap: min(PEAK_MAX, maxL / (order + 1) + 2) rounded up to a multiple of 8"""
     return (min(PEAK_MAX, maxL // (order + 1) + 2) + 7) & ~7
 
 
 def peak_arm(maxL, order):
-    """the kernel run_peaks_impl launches for a batch whose longest chunk has maxL bases (natac_api.hip, run_peaks_impl:
-    pk_cap / lds_lists / bt / nj / lds_reg and the `bt == 256` / `nj <= 16 && lds_reg <= 150 * 1024` / segmented branches with
-    `maxL / (order + 1) + 2 > pk_cap` for the global lists) and the maxima test inside the register kernel (natac_kernels.hpp,
-    natac_peaks_chunk_reg: region / stride / two_phase, and `stride < NJ * 8` for the masks in registers)"""
+    """the kernel the library launches for a batch whose longest chunk has maxL bases, written out here on its own (natac_peaks.hpp
+    states it in peaks_plan: pk_cap, the 13-byte list region, bt / nj, the register variants' LDS against 150 KB, the segmented kernel
+    with `maxL / (order + 1) + 2 > pk_cap` for the global lists) and the maxima test inside the register kernel (natac_peaks_chunk_reg:
+    the per-wave stride, two phases, and `stride < NJ * 8` for the masks in registers)"""
     pk_cap = pk_cap_of(maxL, order)
     lds_lists = pk_cap * (8 + 4 + 1)
     bt = 256 if maxL <= 4096 else 1024
@@ -72,26 +69,39 @@ NUC_LENGTHS = [256 * nj for nj in range(1, 17)] + [1024 * nj for nj in range(5, 
 NUC_PARAMS = [(12, 60, 25, 0.0), (1, 60, 2, 0.0)]
 
 
+ARM_ORDERS = (1, 2, 3, 4, 8, 12, 30, 150, 255)
+
+
 def all_arms():
     """every arm the dispatcher has: the 16 + 12 register instances, each with the mask modes it can take, the segmented kernel
     with LDS and with global lists"""
     arms = set()
     for maxL in range(1, 20001):
-        for order in (1, 2, 3, 4, 8, 12, 30, 150, 255):
+        for order in ARM_ORDERS:
             arms.add(peak_arm(maxL, order))
     return arms
 
 
+def library_arm(maxL, order):
+    """(Arm, pk_cap) of the library's own plan (natac_peaks_plan: host only)"""
+    from nucleoatac_amd.device import peaks_plan
+    p = peaks_plan(maxL, order)
+    return Arm(p["kernel"], p["bt"], p["nj"], p["mask"], p["global_lists"]), p["pk_cap"]
+
+
 def launched_instances():
-    """the natac_peaks_chunk_reg<NJ, BT> instances run_peaks_impl launches (its NATAC_PEAKS_REG cases)"""
-    src = open(os.path.join(ROOT, "nucleoatac_amd", "csrc", "natac_api.hip")).read()
-    body = src[src.index("static int run_peaks_impl("):src.index("int natac_run_peaks(")]
-    return set((int(bt), int(nj)) for nj, bt in re.findall(r"NATAC_PEAKS_REG\((\d+), (\d+)\)", body))
+    """the natac_peaks_chunk_reg<NJ, BT> instances the library's plan launches over the lengths and orders all_arms() walks"""
+    plans = (library_arm(maxL, order)[0] for maxL in range(1, 20001) for order in ARM_ORDERS)
+    return set((a.bt, a.nj) for a in plans if a.kernel == "reg")
 
 
 def test_cases_cover_every_arm():
-    """CPU: the instances in the model are those in the source, and the cases below reach every one of them, every mask mode,
-    both segmented variants and the fall-through of NJ = 16 at 1,024 threads to the segmented kernel (lds_reg > 150 KB)"""
+    """CPU: the model is the library's plan in every field (kernel, bt, nj, mask, global lists, pk_cap) for every maxL in 1..20000 and
+    every order all_arms() walks, and the cases below reach every instance, every mask mode, both segmented variants and the
+    fall-through of NJ = 16 at 1,024 threads to the segmented kernel (lds_reg > 150 KB)"""
+    for maxL in range(1, 20001):
+        for order in ARM_ORDERS:
+            assert library_arm(maxL, order) == (peak_arm(maxL, order), pk_cap_of(maxL, order)), (maxL, order)
     model = set((a.bt, a.nj) for a in all_arms() if a.kernel == "reg")
     assert model == launched_instances()
     assert model == set((256, nj) for nj in range(1, 17)) | set((1024, nj) for nj in range(5, 17))
@@ -111,7 +121,7 @@ def test_cases_cover_every_arm():
 
 
 def test_peak_arm_examples():
-    """CPU: spot values of the model worked out by hand from run_peaks_impl"""
+    """CPU: spot values of the model worked out by hand from peaks_plan"""
     assert peak_arm(4096, 150) == Arm("reg", 256, 16, "registers", False)        # pk_cap 32: 104-byte stride for 128 bytes of masks
     assert peak_arm(4096, 12) == Arm("reg", 256, 16, "two_phase", False)
     assert peak_arm(4096, 1) == Arm("reg", 256, 16, "direct", False)

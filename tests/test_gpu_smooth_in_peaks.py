@@ -19,7 +19,7 @@ from helpers import assert_track, golden, packed_from_golden
 from nucleoatac_amd import _lib as L
 from nucleoatac_amd.packing import PackedChunks
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu       # every test but the CPU check of the plan
 
 # 61 = the window, the shortest chunk natac_run_nuc takes; the edges of NJ = 1, 4, 16; 2120 (NJ = 9, the flagship's)
 LENS = [61, 62, 255, 256, 257, 1023, 1024, 1025, 2120, 4095, 4096]
@@ -176,6 +176,20 @@ def _scenarios(ctx):
     return res, launches
 
 
+def test_plan_forms_smooth_where_the_model_says():
+    """CPU: the library's plan (natac_peaks_plan, natac_peaks.hpp) forms SMOOTH in the search exactly where the model of
+    test_gpu_peak_arms says the 256-thread kernel runs with its masks in LDS -- for every length of LENS (and 4,097) as a batch's
+    longest chunk under every search of ARMS; natac_run_nuc leaves the track pending (order 1 can fuse) exactly up to 4,096 bases"""
+    from nucleoatac_amd.device import peaks_plan
+    from test_gpu_peak_arms import peak_arm
+    for maxL in LENS + [4097]:
+        for name, kw in ARMS:
+            want = maxL <= 4096 and peak_arm(maxL, kw["order"]).mask != "registers"
+            assert peaks_plan(maxL, kw["order"])["forms_smooth"] == want, (maxL, name)
+    assert [peaks_plan(4096, kw["order"])["forms_smooth"] for _, kw in ARMS] == [True, True, False]      # bench, order2, order150
+    assert all(peaks_plan(maxL, 1)["forms_smooth"] == (maxL <= 4096) for maxL in range(1, 5000))
+
+
 @pytest.fixture(scope="module")
 def both():
     out = {}
@@ -188,6 +202,7 @@ def both():
     return out
 
 
+@gpu
 def test_fused_equals_two_kernels(both):
     """every array of every scenario: chunk lengths 61 .. 4,096 in one ragged batch and 4,097 alone, NaN runs from the bias track, the
     bench's search parameters, order 2 and order 150, reads before and after the search, planted NORM, a foreign window"""
@@ -197,6 +212,7 @@ def test_fused_equals_two_kernels(both):
         assert fu[name].dtype == sp[name].dtype and np.array_equal(fu[name], sp[name], equal_nan=fu[name].dtype.kind == "f"), name
 
 
+@gpu
 def test_which_path_ran(both):
     """smoothing-kernel launches per scenario: the fused context runs none where the search forms the track, one where another
     reader comes first or the search's arm is not covered (the other batch of window_* adds its own)"""
@@ -206,6 +222,7 @@ def test_which_path_ran(both):
                              "window_download": 2, "4097": 1}
 
 
+@gpu
 def test_scenarios_hold_what_they_claim(both):
     """the NaN runs, zeros and candidates the comparison above relies on are there, and the state rules hold on the fused context"""
     fu = both[True][0]
@@ -238,6 +255,7 @@ def test_scenarios_hold_what_they_claim(both):
     assert len(fu["4097/0"]) > 10 and np.isnan(fu["4097/5"]).sum() > 250
 
 
+@gpu
 def test_fused_track_and_candidates_against_the_oracle():
     """the chunks_basic golden on a fused context: T_SMOOTH (formed by the search) against the oracle's smoothed track in the default
     tier of assert_track, the candidates == the oracle's call_peaks of norm + smoothed, and they hold the reference's own"""
