@@ -53,9 +53,9 @@ extern "C" {
  * natac_frag_open_cells / natac_bam_ref_cells and natac_region_cell_counts for `pyatac cellcounts`; 12: added natac_ctx_occ_route, and
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
- * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan); the binding
- * refuses another version */
-#define NATAC_ABI_VERSION 17
+ * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
+ * `pyatac motifs`); the binding refuses another version */
+#define NATAC_ABI_VERSION 18
 
 enum {
     NATAC_OK = 0,
@@ -443,6 +443,45 @@ int natac_enriched_regions(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, 
                            const int32_t *thr_large, int64_t *n_regions, int64_t capacity, int64_t *start, int64_t *end, int64_t *summit,
                            int32_t *pileup, int32_t *n_small, int32_t *n_large, int64_t *n_found, int64_t *n_significant,
                            double *kernel_ms);
+/* ---- the sites of integer position weight matrices in one chromosome (this library's own; `pyatac motifs`) ----
+ * seq[n] is the chromosome as natac_base_counts takes it: ASCII, case kept.  start[i] <= end[i] (0 <= start, end <= n) are the n_windows
+ * windows: they may overlap, repeat and come in any order; windows that overlap or abut are merged into SCAN INTERVALS.
+ * Motif m has widths[m] = W columns (1 <= W <= NATAC_MOTIF_MAX_WIDTH) of four int32 scores, base order A C G T = 0 1 2 3; the columns of
+ * all motifs follow each other in scores[4 * sum of widths]: S_m[j][b] = scores[4 * (widths[0] + .. + widths[m - 1] + j) + b].
+ * thresholds[m] = T is an int32.  The integers S and T are all the statistics the device sees (the caller derives them from counts, a
+ * background and a p-value: nucleoatac_amd/pyatac/get_motifs.py; NATAC_MOTIF_SCALE is the scale of its log-odds, 0.01 bit a unit).
+ *   Scoring: motif m is scored at x when [x, x + W) lies inside ONE scan interval and all W bases are one of ACGTacgt (lower case counts
+ *   as upper case; N and the IUPAC codes leave the window unscored).  With code(.) the base's number,
+ *     fwd = sum_j S[j][code(seq[x + j])],   rev = sum_j S[W - 1 - j][3 - code(seq[x + j])]   (the reverse complement read on the forward
+ *   strand), both exact int32.  A `+` hit is fwd >= T, a `-` hit is rev >= T; both can occur at one x.
+ *   Hits: four arrays, motif (int32), start = x (int64), strand (uint8, 0 = `+`, 1 = `-`), score (int32), sorted by (motif, start, strand)
+ *   by the device -- the host never sorts them.  A site appears once however many windows cover it.  *n_hits is always written; if it is
+ *   more than capacity, the four arrays stay as they were and the caller comes again with room (NATAC_MOTIF_FIRST_CAPACITY is the binding's
+ *   first guess).
+ *   Counts: counts[n_windows x n_motifs], int32, row-major, always written: entry (i, m) = the hits of motif m with start[i] <= x and
+ *   x + W_m <= end[i], per window: a site inside two overlapping windows counts in both, a site across the border of two abutting windows
+ *   is a hit and counts in neither.
+ * Refused (NATAC_E_ARG, every output untouched): a width outside the limits, more than NATAC_MOTIF_MAX_MOTIFS motifs, a NULL pointer where a
+ * size is positive, a window outside [0, n) or with end < start, n < 1 or n >= 2^31, a motif whose sums of column minima or maxima leave
+ * int32.  With no windows or no motifs nothing is launched and the counts are zero.
+ * The kernels (csrc/natac_motifs.hpp): the chromosome is packed once per call to 2 bits a base plus a validity bit.  A wave takes
+ * NATAC_MOTIF_TILE window starts at a time, a lane each, and NATAC_MOTIF_RUN_TILES such tiles in a row (twice that, and again, where
+ * motifs x runs would pass 2^27 counters; NATAC_MOTIF_MAX_COUNTERS in the environment sets a smaller bound: tests); the motifs are worked in groups of at most NATAC_MOTIF_GROUP whose tables (at most 32 KiB) lie in LDS.  Per motif
+ * the host takes one of two accumulators: both strands in the halves of one dword, offset by the column minima, when
+ * sum_j (max_b S[j][b] - min_b S[j][b]) <= 65535, else two int32 sums.  Hits are counted per (motif, run), the counts prefix-summed, and
+ * the marked (tile, motif) pairs scored again into their places.  Only integer arithmetic, no atomics: two calls give the same bytes.
+ * kernel_ms (may be NULL): device time from the first to the last kernel of the call; written only behind the checks. */
+#define NATAC_MOTIF_MAX_WIDTH 64
+#define NATAC_MOTIF_MAX_MOTIFS 4096
+#define NATAC_MOTIF_SCALE 100
+#define NATAC_MOTIF_TILE 64
+#define NATAC_MOTIF_RUN_TILES 16
+#define NATAC_MOTIF_GROUP 64
+#define NATAC_MOTIF_FIRST_CAPACITY 4194304
+int natac_motif_scan(natac_ctx *ctx, const uint8_t *seq, int64_t n, int64_t n_windows, const int64_t *start, const int64_t *end,
+                     int32_t n_motifs, const int32_t *widths, const int32_t *scores, const int32_t *thresholds, int64_t *n_hits,
+                     int64_t capacity, int32_t *hit_motif, int64_t *hit_start, uint8_t *hit_strand, int32_t *hit_score, int32_t *counts,
+                     double *kernel_ms);
 /* ---- the truncated SVD of the weighted cell-by-window matrix (this library's own; `pyatac cluster`) ----
  * The counts come as natac_region_cell_counts writes them: m rows (windows), n columns (cells), row_ptr[m + 1] non-decreasing with
  * row_ptr[0] >= 0 (the entries are col / count [row_ptr[0], row_ptr[m])), col strictly ascending within a row and in [0, n), count >= 1.

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 17    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 18    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -18,6 +18,9 @@ G_OCC, G_LOWER, G_UPPER = 0, 1, 2
 SIGNAL_SEG = 64      # NATAC_SIGNAL_SEG: sites per partial sum of natac_site_signal's aggregate
 CELLQC_MAX_FLANK = 2500     # NATAC_CELLQC_MAX_FLANK: the widest profile of natac_cell_site_qc
 PEAKS_MAX_WINDOW = 50000    # NATAC_PEAKS_MAX_WINDOW: the widest half-window of natac_enriched_regions
+MOTIF_MAX_WIDTH, MOTIF_MAX_MOTIFS, MOTIF_SCALE = 64, 4096, 100      # NATAC_MOTIF_*: the limits and the score scale of natac_motif_scan
+MOTIF_TILE, MOTIF_RUN_TILES, MOTIF_GROUP = 64, 16, 64               # its tile, run and motif group (the tests stand on their borders)
+MOTIF_FIRST_CAPACITY = 4194304      # NATAC_MOTIF_FIRST_CAPACITY: hits Context.motif_scan has room for at first
 LSI_MAX_R = 64              # NATAC_LSI_MAX_R: the widest block of natac_sparse_lsi
 SPLIT_MAX_BARCODES = 8388608        # NATAC_SPLIT_MAX_BARCODES: the most cells a barcode table holds
 K_FRAG_GATHER, K_BACKGROUND, K_SMOOTH_NUC, K_OCC_MLE, K_OCC_SMOOTH, K_OCC_FILL, K_INS, K_CAND, K_SIZE_HIST = range(9)
@@ -97,6 +100,8 @@ SIGNATURES = {
     "natac_enriched_regions": (C.c_int, [_vp, _i64, _vp, _vp, _i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32, _vp, _vp,
                                          C.POINTER(_i64), _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64),
                                          C.POINTER(_f64)]),
+    "natac_motif_scan": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(_i64), _i64, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(_f64)]),
     "natac_sparse_lsi": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                    C.POINTER(_i32), C.POINTER(_f64)]),
     "natac_site_seq_counts": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64),

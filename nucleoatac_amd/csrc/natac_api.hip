@@ -29,6 +29,7 @@
 #include "natac_cellqc.hpp"
 #include "natac_lsi.hpp"
 #include "natac_peakcall.hpp"
+#include "natac_motifs.hpp"
 #include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

@@ -4,6 +4,7 @@ All numerics run in libnatac_hip.so (HIP, gfx950).  numpy is only used for the h
 that cross the boundary.
 """
 import ctypes as C
+import os
 import weakref
 
 import numpy as np
@@ -515,6 +516,41 @@ class Context(object):
         res = tuple(o[:n.value].copy() for o in out)
         if with_counts:
             res += (int(found.value), int(nsig.value))
+        return res + (total_ms,) if with_kernel_ms else res
+
+    def motif_scan(self, seq, starts, ends, widths, scores, thresholds, with_kernel_ms=False, capacity=None):
+        """the sites of integer position weight matrices in one chromosome (natac_motif_scan; include/natac.h states the rule):
+        (motif int32, start int64, strand uint8, score int32, counts int32[n_windows, n_motifs]), the hits sorted by (motif, start,
+        strand) on the device, exact.  seq: the chromosome's bytes, case as in the FASTA; starts / ends: the windows (None: the whole
+        chromosome); widths[n_motifs]; scores: int32[sum of widths, 4], the motifs' columns one after the other, bases A C G T;
+        thresholds[n_motifs].  A window start x is a `+` hit of a motif when its forward score reaches the threshold, a `-` hit when the
+        reverse complement's does; counts[i, m] = the hits of motif m that lie inside window i.  capacity: the room of the first call
+        (default NATAC_MOTIF_FIRST_CAPACITY, or the environment's value of that name); a call that finds more is made again with room
+        for all.  with_kernel_ms: also the device time of the calls' kernels."""
+        sq = np.ascontiguousarray(seq, dtype=np.uint8)
+        st = np.ascontiguousarray([0] if starts is None else starts, dtype=np.int64)
+        en = np.ascontiguousarray([sq.shape[0]] if ends is None else ends, dtype=np.int64)
+        wd = np.ascontiguousarray(widths, dtype=np.int32)
+        sc = np.ascontiguousarray(scores, dtype=np.int32)
+        th = np.ascontiguousarray(thresholds, dtype=np.int32)
+        if sq.ndim != 1 or st.ndim != 1 or st.shape != en.shape or wd.ndim != 1 or th.shape != wd.shape:
+            raise ValueError("seq, starts / ends and widths / thresholds must be 1-d arrays, each pair of one length")
+        if sc.size != 4 * int(np.maximum(wd, 0).sum(dtype=np.int64)):
+            raise ValueError("scores must hold four numbers for every column of every motif")
+        if capacity is None:
+            capacity = int(os.environ.get("NATAC_MOTIF_FIRST_CAPACITY", L.MOTIF_FIRST_CAPACITY))
+        cap = max(int(capacity), 0)
+        counts = np.zeros((st.shape[0], wd.shape[0]), dtype=np.int32)
+        n, ms, total_ms = C.c_int64(0), C.c_double(0), 0.0
+        while True:
+            out = [np.empty(max(cap, 1), dtype=dt) for dt in (np.int32, np.int64, np.uint8, np.int32)]
+            L.check(self._lib.natac_motif_scan(self._h, _ptr(sq), sq.shape[0], st.shape[0], _ptr(st), _ptr(en), wd.shape[0], _ptr(wd),
+                                               _ptr(sc), _ptr(th), C.byref(n), cap, *[_ptr(o) for o in out], _ptr(counts), C.byref(ms)))
+            total_ms += ms.value
+            if n.value <= cap:
+                break
+            cap = int(n.value)
+        res = tuple(o[:n.value].copy() for o in out) + (counts,)
         return res + (total_ms,) if with_kernel_ms else res
 
     def site_seq_counts(self, seq, centers, minus, up, down, word=1, with_kernel_ms=False):

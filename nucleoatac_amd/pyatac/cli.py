@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | peaks` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -17,7 +17,9 @@ two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windo
 the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
 `cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
 k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
-`cluster` -> `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  The other pyatac tools (vplot, bias_vplot) are not part of
+`cluster` -> `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
+sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
+the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -228,6 +230,22 @@ def add_peaks_parser(sub):
                    help="Also write disjoint windows of this width around the summits, the most significant first")
 
 
+def add_motifs_parser(sub):
+    p = sub.add_parser("motifs", help="scan a genome, or the windows of a BED file, for the sites of TF motifs")
+    p.add_argument("--fasta", metavar="fasta_file", required=True, help="Accepts fasta file (or a FastaStore .npz)")
+    p.add_argument("--motifs", metavar="motif_file", required=True, help="Motifs in MEME minimal text format or JASPAR format")
+    p.add_argument("--bed", metavar="bed_file", help="Windows to scan and to count matches in. Default is every chromosome whole")
+    p.add_argument("--only", metavar="ID", nargs="+", help="Keep only the motifs with these ids")
+    p.add_argument("--pvalue", metavar="float", default=1e-4, type=float,
+                   help="A window is a hit when a score as high has at most this probability under the background. Default is 1e-4")
+    p.add_argument("--pseudocount", metavar="float", default=0.8, type=float, help="Pseudocount of every motif column. Default is 0.8")
+    p.add_argument("--bg", metavar="bg", nargs="+", default=["uniform"],
+                   help="Background: uniform (default), regions (the base content of the scanned intervals) or four numbers a c g t")
+    p.add_argument("--format", choices=("mtx", "npz"), default="mtx", help="Format of the window-by-motif matrix. Default is mtx")
+    p.add_argument("--no_sites", action="store_true", default=False, help="Don't write the sites file")
+    p.add_argument("--out", metavar="basename", help="Basename for output")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
@@ -235,7 +253,7 @@ def pyatac_parser():
                                                                 "nucleotide content and track signal around sites; a single-cell fragment file "
                                                                 "split by cell group, its cell-by-window count matrix, the discovery "
                                                                 "of its cells and their TSS enrichment and fraction of fragments in peaks; "
-                                                                "enriched regions (peaks) of a fragment store")
+                                                                "enriched regions (peaks) of a fragment store; the sites of TF motifs in a genome")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -253,6 +271,7 @@ def pyatac_parser():
     add_cellcounts_parser(sub)
     add_cluster_parser(sub)
     add_peaks_parser(sub)
+    add_motifs_parser(sub)
     return parser
 
 
@@ -378,6 +397,16 @@ def pyatac_main(args):
             get_peaks(args)
         except (PeaksError, NatacError) as e:
             sys.stderr.write("pyatac peaks: %s\n" % e)
+            return 1
+    elif args.call == "motifs":
+        from .._lib import NatacError
+        from .chunk import BedColumnError
+        from .get_motifs import MotifsError, get_motifs
+        print("---------Scanning for motif sites---------------------------------------")
+        try:
+            get_motifs(args)
+        except (MotifsError, BedColumnError, NatacError) as e:
+            sys.stderr.write("pyatac motifs: %s\n" % e)
             return 1
     return 0
 
