@@ -54,8 +54,9 @@ extern "C" {
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
  * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
- * `pyatac motifs`); the binding refuses another version */
-#define NATAC_ABI_VERSION 18
+ * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`); the binding refuses another
+ * version */
+#define NATAC_ABI_VERSION 19
 
 enum {
     NATAC_OK = 0,
@@ -349,6 +350,11 @@ int natac_insertion_seq_counts(natac_ctx *ctx, int32_t n_chunks, const int32_t *
  * case) of seq[start[i] .. end[i]) summed over the n_ranges ranges, int64, overwritten; overlapping ranges count once per range. */
 int natac_base_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int32_t n_ranges, const int64_t *start, const int64_t *end,
                       int64_t *counts);
+/* the per-range form of natac_base_counts, by the same rule: counts[n_ranges x 4] = the A, C, G, T bases (upper or lower case) of
+ * seq[start[i] .. end[i]) for every range on its own, int64, overwritten; 0 <= start[i] <= end[i] <= n (NATAC_E_ARG names the range);
+ * ranges may overlap, repeat, be empty and come in any order. */
+int natac_window_base_counts(natac_ctx *ctx, const uint8_t *seq, int64_t n, int64_t n_ranges, const int64_t *start, const int64_t *end,
+                             int64_t *counts);
 /* get_counts, pyatac/get_counts.py:30-45, for the regions of one chromosome: pos[n_frags] (non-decreasing) and tlen[n_frags] are the
  * chromosome's forward proper-pair records as the FragmentStore holds them.  A record is the fragment l = pos + 4, ilen = tlen - 8
  * (atac != 0) or l = pos, ilen = tlen (atac == 0), r = l + ilen - 1, and counts for region i if lower <= ilen < upper and
@@ -516,6 +522,47 @@ int natac_motif_scan(natac_ctx *ctx, const uint8_t *seq, int64_t n, int64_t n_wi
 int natac_sparse_lsi(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
                      const double *row_weight, const double *col_scale, double scale, int transform, int binarize, int r, int n_iter,
                      const double *q0, double *sigma, double *U, double *V, int32_t *status, double *kernel_ms);
+/* ---- per-cell motif accessibility deviations against background window sets (this library's own; `pyatac deviations`) ----
+ * The command's rule, whole.  X is the windows x cells count matrix of `pyatac cellcounts`, H the windows x motifs hit matrix of
+ * `pyatac motifs` over the same windows; window p is annotated with motif m when H[p, m] > 0.  Windows with row sum 0 and cells with
+ * column sum 0 are dropped, then motifs left without an annotated window; P windows and N cells stay.  rs[p] is a row sum, d[c] a
+ * column sum, T the total, T < 2^31.  gc[p] = (C + G) / (A + C + G + T) of the window's bases (natac_window_base_counts), 0.5 for a
+ * window with no such base.
+ * Background table (host, integers out): from n_g GC bins and n_a accessibility bins, while P / (n_g n_a) (floored) is below min_bin and
+ * n_g n_a > 1 the larger of the two is lowered by 1, n_a on a tie.  The windows ranked by (gc, index) are cut into GC bins, bin k the
+ * ranks [floor(k P / n_g), floor((k + 1) P / n_g)); inside each GC bin the windows ranked by (rs, index) are cut into n_a parts in the
+ * same way.  A window's candidates are the windows of its cell of that grid, itself included, in ascending index order; with
+ * r = numpy.random.default_rng(seed).random((B, P)), bg[b][p] = candidates(p)[int(r[b - 1, p] * len(candidates(p)))] for b = 1 .. B, and
+ * bg[0] is the identity.
+ * Device, integers: for b = 0 .. B, motif m and cell c,  O_b[m, c] = sum over the annotated p of X[bg[b][p], c]  and
+ * E_b[m] = sum over the annotated p of rs[bg[b][p]], both exact.
+ * Device, fp64, one rounded operation at a time, no contraction:  x = double(E_b[m]) * double(d[c]) / double(T),
+ * Y_b = (double(O_b[m, c]) - x) / x,  raw = Y_0, and over k = 1 .. B in that order  delta = Y_k - mean,  mean += delta / k,
+ * M2 += delta * (Y_k - mean)  (Welford's recurrence from zeros).
+ * Host: sd = sqrt(bg_m2 / (B - 1)), deviation = raw - bg_mean, z = deviation / sd or NaN where sd == 0; a motif's variability is the
+ * standard deviation (n - 1) of z over the cells whose z is finite; with a group table, the mean z per group and motif.
+ *
+ * This entry is the device part.  Operands: the counts as natac_region_cell_counts writes them after the dropping, m = P windows and
+ * n = N cells, under the CSR rules of natac_sparse_lsi (count >= 1), every window and every cell with at least one entry and the total
+ * below 2^31; the motif sets motif-major, mot_ptr[n_motifs + 1] from 0 and mot_win[] strictly ascending inside a set, no set empty;
+ * bg[n_bg x m] int32 row-major, the sets 1 .. B = n_bg (set 0 is implied), every value in [0, m); 2 <= n_bg <= NATAC_DEVIATIONS_MAX_B.
+ * Outputs: raw, bg_mean, bg_m2, float64 [n_motifs x n] each.  obs / expect (both or neither; may be NULL) are a testing output:
+ * O_b as int64 [(n_bg + 1) x n_motifs x n] and E_b as int64 [(n_bg + 1) x n_motifs]; refused when (n_bg + 1) n_motifs n exceeds
+ * NATAC_DEVIATIONS_MAX_DEBUG.  Everything is checked on the host before any launch; a failure returns NATAC_E_ARG, names the index and
+ * leaves the outputs untouched.  With n_motifs == 0 nothing is launched.
+ * Kernel (csrc/natac_deviations.hpp): a workgroup owns one motif and one tile of cells and loops over b itself; it gathers the rows
+ * bg[b][p] of X restricted to its tile (the entry splits every row by tile once per call) into integer counters in LDS with LDS atomics --
+ * 32-bit, or 64-bit when the largest motif times the largest count reaches 2^32 -- sums rs in int64 by a wave reduction, and behind a
+ * barrier turns the counters into Y_b and advances mean and M2, which stay in LDS over b.  The tile is NATAC_DEVIATIONS_TILE cells, halved
+ * while motifs x tiles is below twice the compute units; the environment's NATAC_DEVIATIONS_CELL_TILE (1 .. NATAC_DEVIATIONS_TILE) forces
+ * one, for the tests.  Every integer sum is exact, the order over b is sequential per element and there are no floating-point atomics: two
+ * calls give the same bytes, whatever the tile.  kernel_ms (may be NULL): device time of the call's kernel. */
+#define NATAC_DEVIATIONS_TILE 4096
+#define NATAC_DEVIATIONS_MAX_B 1024
+#define NATAC_DEVIATIONS_MAX_DEBUG 16777216
+int natac_motif_deviations(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
+                           int32_t n_motifs, const int64_t *mot_ptr, const int32_t *mot_win, int32_t n_bg, const int32_t *bg, double *raw,
+                           double *bg_mean, double *bg_m2, int64_t *obs, int64_t *expect, double *kernel_ms);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 18    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 19    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -22,6 +22,7 @@ MOTIF_MAX_WIDTH, MOTIF_MAX_MOTIFS, MOTIF_SCALE = 64, 4096, 100      # NATAC_MOTI
 MOTIF_TILE, MOTIF_RUN_TILES, MOTIF_GROUP = 64, 16, 64               # its tile, run and motif group (the tests stand on their borders)
 MOTIF_FIRST_CAPACITY = 4194304      # NATAC_MOTIF_FIRST_CAPACITY: hits Context.motif_scan has room for at first
 LSI_MAX_R = 64              # NATAC_LSI_MAX_R: the widest block of natac_sparse_lsi
+DEVIATIONS_TILE, DEVIATIONS_MAX_B, DEVIATIONS_MAX_DEBUG = 4096, 1024, 16777216      # NATAC_DEVIATIONS_*: natac_motif_deviations' limits
 SPLIT_MAX_BARCODES = 8388608        # NATAC_SPLIT_MAX_BARCODES: the most cells a barcode table holds
 K_FRAG_GATHER, K_BACKGROUND, K_SMOOTH_NUC, K_OCC_MLE, K_OCC_SMOOTH, K_OCC_FILL, K_INS, K_CAND, K_SIZE_HIST = range(9)
 K_INS_SMOOTH, K_CENTER_COV, K_PWM_TRACK = 9, 10, 11
@@ -92,6 +93,7 @@ SIGNATURES = {
     "natac_insertion_seq_counts": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp,
                                              C.POINTER(_i64), C.POINTER(_f64)]),
     "natac_base_counts": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "natac_window_base_counts": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "natac_region_counts": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_f64)]),
     "natac_region_cell_counts": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _i64, _vp, _vp,
                                            C.POINTER(_f64)]),
@@ -104,6 +106,8 @@ SIGNATURES = {
                                    C.POINTER(_f64)]),
     "natac_sparse_lsi": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f64, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp,
                                    C.POINTER(_i32), C.POINTER(_f64)]),
+    "natac_motif_deviations": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         C.POINTER(_f64)]),
     "natac_site_seq_counts": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64),
                                         C.POINTER(_f64)]),
     "natac_site_signal": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(_f64)]),

@@ -30,6 +30,7 @@
 #include "natac_lsi.hpp"
 #include "natac_peakcall.hpp"
 #include "natac_motifs.hpp"
+#include "natac_deviations.hpp"
 #include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

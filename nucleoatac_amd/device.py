@@ -352,14 +352,21 @@ class Context(object):
                                                      C.byref(ms)))
         return (counts, n.value, ms.value) if with_kernel_ms else (counts, n.value)
 
-    def base_counts(self, seq, starts=None, ends=None):
+    def base_counts(self, seq, starts=None, ends=None, per_range=False):
         """int64[4]: the A, C, G, T bases of seq[starts[i]:ends[i]] summed over the ranges (default: the whole array); the numerators of
-        seq.getNucFreqs / getNucFreqsFromChunkList (pyatac/seq.py:47-72)"""
+        seq.getNucFreqs / getNucFreqsFromChunkList (pyatac/seq.py:47-72).  per_range: int64[n_ranges, 4], every range on its own
+        (natac_window_base_counts), by the same rule."""
         sq = np.ascontiguousarray(seq, dtype=np.uint8)
         st = np.ascontiguousarray([0] if starts is None else starts, dtype=np.int64)
         en = np.ascontiguousarray([sq.shape[0]] if ends is None else ends, dtype=np.int64)
         if st.shape != en.shape:
             raise ValueError("starts and ends differ in length")
+        if per_range:
+            if st.ndim != 1:
+                raise ValueError("starts and ends must be 1-d")
+            out = np.zeros((st.shape[0], 4), dtype=np.int64)
+            L.check(self._lib.natac_window_base_counts(self._h, _ptr(sq), sq.shape[0], st.shape[0], _ptr(st), _ptr(en), _ptr(out)))
+            return out
         out = np.zeros(4, dtype=np.int64)
         L.check(self._lib.natac_base_counts(self._h, _ptr(sq), sq.shape[0], st.shape[0], _ptr(st), _ptr(en), _ptr(out)))
         return out
@@ -453,6 +460,50 @@ class Context(object):
         U *= flip
         V *= flip
         return (sigma, U, V, ms.value) if with_kernel_ms else (sigma, U, V)
+
+    def motif_deviations(self, indptr, indices, data, n_cells, hit_indptr, hit_indices, n_motifs, bg, with_kernel_ms=False, with_sums=False):
+        """the device part of `pyatac deviations` (natac_motif_deviations; include/natac.h states the rule): (raw, bg_mean, bg_m2), each
+        float64[n_motifs, n_cells].  indptr / indices / data are the CSR arrays of region_cell_counts after the dropping (rows the windows,
+        every window and every cell with an entry, data >= 1, the total below 2^31); hit_indptr / hit_indices the CSR pattern of the
+        window-by-motif hit matrix over the same windows (motifs ascending within a row; the values are not needed) -- it is turned
+        motif-major here with a stable sort by motif, so every motif's windows ascend; bg int32[B, n_windows] the background sets 1 .. B.
+        with_sums: also (O int64[B + 1, n_motifs, n_cells], E int64[B + 1, n_motifs]), the testing output.  with_kernel_ms: also the
+        kernel's device time.  The returned arrays are filled only by a call that succeeds."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        da = np.ascontiguousarray(data, dtype=np.int32)
+        hp = np.ascontiguousarray(hit_indptr, dtype=np.int64)
+        hx = np.ascontiguousarray(hit_indices, dtype=np.int64)
+        bgm = np.ascontiguousarray(bg, dtype=np.int32)
+        n, M, m = int(n_cells), int(n_motifs), ip.shape[0] - 1
+        if ip.ndim != 1 or m < 0 or ix.ndim != 1 or ix.shape != da.shape or hp.shape != (m + 1,) or hx.ndim != 1:
+            raise ValueError("indptr / indices / data and hit_indptr / hit_indices must be CSR arrays over the same windows")
+        if m and int(ip[-1]) > ix.shape[0]:
+            raise ValueError("indptr points past the %d entries given" % ix.shape[0])
+        if m and (int(hp[0]) != 0 or int(hp[-1]) != hx.shape[0] or np.any(np.diff(hp) < 0)):
+            raise ValueError("hit_indptr does not describe the %d hit entries given" % hx.shape[0])
+        if not 0 <= M <= 2147483647 or not 0 <= n <= 2147483647:
+            raise ValueError("n_motifs and n_cells must be in [0, 2^31)")
+        if len(hx) and (hx.min() < 0 or hx.max() >= M):
+            raise ValueError("hit_indices holds a motif outside [0, %d)" % M)
+        if bgm.ndim != 2 or bgm.shape[1] != m:
+            raise ValueError("bg must have one column per window")
+        B = bgm.shape[0]
+        # motif-major: a stable sort of the (window, motif) pairs by motif keeps the windows ascending
+        mot_ptr = np.zeros(M + 1, dtype=np.int64)
+        np.cumsum(np.bincount(hx, minlength=M), out=mot_ptr[1:])
+        win = np.repeat(np.arange(m, dtype=np.int32), np.diff(hp)) if m else np.zeros(0, np.int32)
+        mot_win = np.ascontiguousarray(win[np.argsort(hx, kind="stable")], dtype=np.int32)
+        out = [np.zeros((M, n), dtype=np.float64) for _ in range(3)]
+        sums = [np.zeros((B + 1, M, n), dtype=np.int64), np.zeros((B + 1, M), dtype=np.int64)] if with_sums else None
+        ms = C.c_double(0)
+        L.check(self._lib.natac_motif_deviations(self._h, m, n, _ptr(ip), _ptr(ix), _ptr(da), M, _ptr(mot_ptr), _ptr(mot_win), B, _ptr(bgm),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(sums[0]) if sums else None,
+                                                 _ptr(sums[1]) if sums else None, C.byref(ms)))
+        res = tuple(out)
+        if with_sums:
+            res += tuple(sums)
+        return res + (ms.value,) if with_kernel_ms else res
 
     def cell_site_qc(self, pos, tlen, cell, n_cells, site_center=None, site_minus=None, flank=1000, center=500, edge=100, peak_start=None,
                      peak_end=None, with_kernel_ms=False):

@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | peaks | motifs` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -19,7 +19,10 @@ the last link before `nucleoatac run`.  `cluster`, this package's own too, makes
 k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
 `cluster` -> `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
 sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
-the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  The other pyatac tools (vplot, bias_vplot) are not part of
+the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  `deviations`, this package's
+own too, joins that matrix with the `cellcounts` matrix: per-cell motif accessibility deviations and z-scores against background window
+sets matched in GC content and accessibility, summed on the GPU, with a variability ranking of the motifs and, with the table `cluster`
+writes, the mean z-score per cluster.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -246,6 +249,25 @@ def add_motifs_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output")
 
 
+def add_deviations_parser(sub):
+    p = sub.add_parser("deviations", help="per-cell motif accessibility deviations and z-scores from the count and the motif matrix")
+    p.add_argument("--counts", metavar="matrix", required=True,
+                   help="BASE.cellcounts.npz or BASE.cellcounts.mtx.gz (with its .barcodes.tsv and .regions.bed) as `cellcounts` writes them")
+    p.add_argument("--motifs", metavar="matrix", required=True,
+                   help="BASE.motifs.npz or BASE.motifs.mtx.gz (with its .names.tsv and .regions.bed) as `motifs --bed` writes them, "
+                        "over the same BED")
+    p.add_argument("--fasta", metavar="fasta_file", required=True, help="Accepts fasta file (or a FastaStore .npz): the windows' GC content")
+    p.add_argument("--groups", metavar="table", help="TAB-separated: barcode, group (the table `cluster` writes): also write the mean z per group")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--iterations", metavar="int", default=50, type=int, help="Background window sets, 2 to 1024. Default is 50")
+    p.add_argument("--gc_bins", metavar="int", default=25, type=int, help="GC content bins of the background grid. Default is 25")
+    p.add_argument("--acc_bins", metavar="int", default=25, type=int, help="Accessibility bins of the background grid. Default is 25")
+    p.add_argument("--min_bin", metavar="int", default=10, type=int,
+                   help="The grid is reduced until a bin holds at least this many windows on average. Default is 10")
+    p.add_argument("--seed", metavar="int", default=1, type=int, help="Seed of the background draws. Default is 1")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the count matrix's name without .cellcounts and its suffix")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
@@ -253,7 +275,8 @@ def pyatac_parser():
                                                                 "nucleotide content and track signal around sites; a single-cell fragment file "
                                                                 "split by cell group, its cell-by-window count matrix, the discovery "
                                                                 "of its cells and their TSS enrichment and fraction of fragments in peaks; "
-                                                                "enriched regions (peaks) of a fragment store; the sites of TF motifs in a genome")
+                                                                "enriched regions (peaks) of a fragment store; the sites of TF motifs in a genome; "
+                                                                "per-cell motif accessibility deviations")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -270,6 +293,7 @@ def pyatac_parser():
     add_split_parser(sub)
     add_cellcounts_parser(sub)
     add_cluster_parser(sub)
+    add_deviations_parser(sub)
     add_peaks_parser(sub)
     add_motifs_parser(sub)
     return parser
@@ -388,6 +412,16 @@ def pyatac_main(args):
             get_cluster(args)
         except (ClusterError, NatacError) as e:
             sys.stderr.write("pyatac cluster: %s\n" % e)
+            return 1
+    elif args.call == "deviations":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .get_deviations import DeviationsError, get_deviations
+        print("---------Getting motif deviations per cell---------------------------------------")
+        try:
+            get_deviations(args)
+        except (DeviationsError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac deviations: %s\n" % e)
             return 1
     elif args.call == "peaks":
         from .._lib import NatacError

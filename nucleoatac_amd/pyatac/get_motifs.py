@@ -417,7 +417,8 @@ def get_motifs(args, timing=None):
         bgzip_file(txt)
     if args.format == "npz":
         np.savez_compressed(base + ".npz", indptr=indptr, indices=indices, data=data, shape=np.array([len(start), M], np.int64),
-                            motifs=np.array(ids, dtype="S"), region_chrom=region_chrom.astype("U"), region_start=start, region_end=end)
+                            motifs=np.array(ids, dtype="S"), alts=np.array([m[1] for m in motifs], dtype="U"),
+                            region_chrom=region_chrom.astype("U"), region_start=start, region_end=end)
     else:
         text = mtx_text(indptr, indices, data, M)
         bed = "".join(["%s\t%d\t%d\n" % r for r in zip(region_chrom.tolist(), start.tolist(), end.tolist())])
