@@ -54,9 +54,9 @@ extern "C" {
  * natac_set_occ_model refuses alphas below 2^-500 under a model with a zero nfr probability; 13: added natac_frag_cells /
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
  * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
- * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`); the binding refuses another
- * version */
-#define NATAC_ABI_VERSION 19
+ * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`; 20: added
+ * natac_motif_deviations_plan); the binding refuses another version */
+#define NATAC_ABI_VERSION 20
 
 enum {
     NATAC_OK = 0,
@@ -563,6 +563,16 @@ int natac_sparse_lsi(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_pt
 int natac_motif_deviations(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
                            int32_t n_motifs, const int64_t *mot_ptr, const int32_t *mot_win, int32_t n_bg, const int32_t *bg, double *raw,
                            double *bg_mean, double *bg_m2, int64_t *obs, int64_t *expect, double *kernel_ms);
+/* How natac_motif_deviations launches for a matrix of m windows, n cells and nnz entries, n_motifs motifs the largest of max_set windows,
+ * the largest count max_count, on a device of n_cu compute units (host only: no context, no GPU needed; it reads
+ * NATAC_DEVIATIONS_CELL_TILE as the call does).  *tile: the cells of a workgroup -- the forced one, else NATAC_DEVIATIONS_TILE halved, down
+ * to 256, while n_motifs x tiles is below 2 n_cu, then evened out over that number of tiles to a multiple of 64; *n_tiles =
+ * ceil(n / *tile); *lanes: the lanes of a wave that share a row's piece inside a tile, the smallest power of two with
+ * lanes * m * n_tiles >= nnz, at most 64; *wide: 1 = 64-bit counters (max_set * max_count >= 2^32), 0 = 32-bit; *lds_bytes: a workgroup's
+ * dynamic LDS, *tile * (16 + (8 or 4)) + 128.  NATAC_E_ARG for a size below 1, for m, n, max_set or max_count of 2^31 or more, and where
+ * the call refuses the shape: n_motifs * n_tiles >= 2^31 or m * (n_tiles + 1) > 2^33. */
+int natac_motif_deviations_plan(int64_t m, int64_t n, int64_t nnz, int32_t n_motifs, int64_t max_set, int64_t max_count, int32_t n_cu,
+                                int32_t *tile, int64_t *n_tiles, int32_t *lanes, int32_t *wide, int64_t *lds_bytes);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 19    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 20    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -108,6 +108,8 @@ SIGNATURES = {
                                    C.POINTER(_i32), C.POINTER(_f64)]),
     "natac_motif_deviations": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          C.POINTER(_f64)]),
+    "natac_motif_deviations_plan": (C.c_int, [_i64, _i64, _i64, _i32, _i64, _i64, _i32, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32),
+                                              C.POINTER(_i32), C.POINTER(_i64)]),
     "natac_site_seq_counts": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64),
                                         C.POINTER(_f64)]),
     "natac_site_signal": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(_f64)]),

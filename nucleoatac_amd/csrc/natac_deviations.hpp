@@ -185,6 +185,31 @@ static int dev_tile_size(long long n, long long M, int n_cu) {
     return (int)std::min<long long>(tile, ((n + n_tiles - 1) / n_tiles + 63) / 64 * 64);
 }
 
+// how a call launches: what natac_motif_deviations runs and natac_motif_deviations_plan reports
+struct DevPlan {
+    int tile;              // cells per workgroup
+    long long n_tiles;     // the grid is n_motifs * n_tiles workgroups
+    int lanes;             // the lanes that share a piece of a row: the power of two at or above the mean piece of a row inside a tile
+    bool wide;             // 64-bit counters: the largest motif times the largest count reaches 2^32
+    size_t lds;            // dynamic LDS of a workgroup, bytes
+};
+
+// the plan for m windows, n cells, nnz entries and M motifs, the largest of max_set windows, the largest count max_count, on n_cu compute
+// units (all positive); false when motifs x tiles or windows x tiles are too many for one call (tile and n_tiles are set all the same)
+static bool dev_plan(long long m, long long n, long long nnz, long long M, long long max_set, long long max_count, int n_cu, DevPlan *p) {
+    p->tile = dev_tile_size(n, M, n_cu);
+    p->n_tiles = (n + p->tile - 1) / p->tile;
+    p->lanes = 0;
+    p->wide = false;
+    p->lds = 0;
+    if (M * p->n_tiles > 2147483647LL || m * (p->n_tiles + 1) > (1LL << 33)) return false;
+    p->lanes = 1;
+    while (p->lanes < 64 && (long long)p->lanes * m * p->n_tiles < nnz) p->lanes *= 2;
+    p->wide = max_set * max_count >= (1LL << 32);
+    p->lds = p->wide ? dev_lds_bytes<unsigned long long>(p->tile) : dev_lds_bytes<unsigned>(p->tile);
+    return true;
+}
+
 }  // namespace natac_dev
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
@@ -279,10 +304,13 @@ int natac_motif_deviations(natac_ctx *c, int64_t m, int64_t n, const int64_t *ro
 
     int n_cu = 256;
     hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-    const int tile = dev_tile_size(n, M, n_cu);
-    const long long n_tiles = (n + tile - 1) / tile;
-    if (M * n_tiles > 2147483647LL || (m + 0LL) * (n_tiles + 1) > (1LL << 33))
-        return fail(NATAC_E_ARG, "%lld motifs x %lld cell tiles of %d x %lld windows are too many for one call", (long long)M, n_tiles, tile, (long long)m);
+    DevPlan plan;
+    if (!dev_plan(m, n, nnz, M, max_set, max_count, n_cu, &plan))
+        return fail(NATAC_E_ARG, "%lld motifs x %lld cell tiles of %d x %lld windows are too many for one call", (long long)M, plan.n_tiles, plan.tile, (long long)m);
+    const int tile = plan.tile, lanes = plan.lanes;
+    const long long n_tiles = plan.n_tiles;
+    const bool wide = plan.wide;
+    const size_t lds = plan.lds;
     // every row split by tile: split[p][t] = the first entry of row p (counted from e0) whose cell is in tile t or later
     std::vector<int> split((size_t)m * (size_t)(n_tiles + 1));
     for (int64_t i = 0; i < m; ++i) {
@@ -293,12 +321,6 @@ int natac_motif_deviations(natac_ctx *c, int64_t m, int64_t n, const int64_t *ro
             sp[t] = (int)(e - e0);
         }
     }
-    // the lanes that share a window: the power of two at or above the mean piece of a row inside a tile
-    int lanes = 1;
-    while (lanes < 64 && (long long)lanes * m * n_tiles < nnz) lanes *= 2;
-    const bool wide = max_set * max_count >= (1LL << 32);
-    const size_t lds = wide ? dev_lds_bytes<unsigned long long>(tile) : dev_lds_bytes<unsigned>(tile);
-
     DeviceCall dc(c, "motif_deviations");
     const int *d_split = dc.upload(split.data(), split.size());
     const int *d_col = dc.upload((const int *)(col + e0), (size_t)nnz), *d_cnt = dc.upload((const int *)(count + e0), (size_t)nnz);
@@ -336,6 +358,24 @@ int natac_motif_deviations(natac_ctx *c, int64_t m, int64_t n, const int64_t *ro
         std::copy(h_obs.begin(), h_obs.end(), (long long *)obs);
         std::copy(h_exp.begin(), h_exp.end(), (long long *)expect);
     }
+    return NATAC_OK;
+}
+
+int natac_motif_deviations_plan(int64_t m, int64_t n, int64_t nnz, int32_t n_motifs, int64_t max_set, int64_t max_count, int32_t n_cu,
+                                int32_t *tile, int64_t *n_tiles, int32_t *lanes, int32_t *wide, int64_t *lds_bytes) {
+    using namespace natac_dev;
+    if (!tile || !n_tiles || !lanes || !wide || !lds_bytes) return fail(NATAC_E_ARG, "null argument");
+    if (m < 1 || n < 1 || nnz < 1 || n_motifs < 1 || max_set < 1 || max_count < 1 || n_cu < 1 || m > 2147483647LL || n > 2147483647LL ||
+        max_set > 2147483647LL || max_count > 2147483647LL)
+        return fail(NATAC_E_ARG, "natac_motif_deviations_plan: positive sizes; m, n, max_set and max_count below 2^31");
+    DevPlan p;
+    if (!dev_plan(m, n, nnz, n_motifs, max_set, max_count, n_cu, &p))
+        return fail(NATAC_E_ARG, "%lld motifs x %lld cell tiles of %d x %lld windows are too many for one call", (long long)n_motifs, p.n_tiles, p.tile, (long long)m);
+    *tile = p.tile;
+    *n_tiles = p.n_tiles;
+    *lanes = p.lanes;
+    *wide = p.wide ? 1 : 0;
+    *lds_bytes = (int64_t)p.lds;
     return NATAC_OK;
 }
 

@@ -74,6 +74,17 @@ def peaks_plan(max_len, order):
                 global_lists=bool(gl), forms_smooth=bool(fs), pk_cap=cap, lds_bytes=lds[0], lds_bytes_smooth=lds[1])
 
 
+def motif_deviations_plan(n_windows, n_cells, nnz, n_motifs, max_set, max_count, n_cu=256):
+    """how motif_deviations launches for a matrix of n_windows x n_cells with nnz entries, n_motifs motifs the largest of max_set windows
+    and the largest count max_count, on n_cu compute units (natac_motif_deviations_plan; needs no GPU, reads NATAC_DEVIATIONS_CELL_TILE as
+    the call does): dict of tile, n_tiles, lanes, wide (64-bit counters) and lds_bytes"""
+    tile, lanes, wide = C.c_int32(), C.c_int32(), C.c_int32()
+    n_tiles, lds = C.c_int64(), C.c_int64()
+    L.check(L.load().natac_motif_deviations_plan(int(n_windows), int(n_cells), int(nnz), int(n_motifs), int(max_set), int(max_count), int(n_cu),
+                                                 C.byref(tile), C.byref(n_tiles), C.byref(lanes), C.byref(wide), C.byref(lds)))
+    return dict(tile=tile.value, n_tiles=n_tiles.value, lanes=lanes.value, wide=bool(wide.value), lds_bytes=lds.value)
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 

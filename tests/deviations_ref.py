@@ -237,8 +237,36 @@ def make_case(seed, P=300, N=65, M=5, B=7, big=True, collapse=False):
     return dict(X=X, H=H, bg=bg, csr=csr_of(X), hits=(hp, hx), sets=[np.flatnonzero(H[:, m]) for m in range(M)], heavy=heavy)
 
 
+def make_arm_case(seed, P, N, B, sizes, density, full=0.01, planted=None, to_planted=False):
+    """a live matrix made to select one arm of the kernel (tests/test_gpu_deviations_arms.py): every entry present with probability
+    `density`, a share `full` of the windows with an entry in every cell, every window and cell left empty patched with one entry, counts
+    of 1 .. 8; planted: the value of one entry put at a random place (case["heavy"], case["heavy_cell"]).  Motif k is the first sizes[k]
+    windows of a random permutation, sorted.  bg holds arbitrary windows; to_planted: set 1 maps every window to the planted entry's
+    window.  -> the dict of make_case()"""
+    rng = np.random.default_rng(seed)
+    X = np.where(rng.random((P, N)) < density, rng.integers(1, 9, (P, N)), 0).astype(np.int64)
+    rows = rng.choice(P, int(round(full * P)), replace=False)
+    X[rows] = rng.integers(1, 9, (len(rows), N))
+    empty = np.flatnonzero(X.sum(axis=1) == 0)
+    X[empty, rng.integers(0, N, len(empty))] = rng.integers(1, 9, len(empty))
+    empty = np.flatnonzero(X.sum(axis=0) == 0)
+    X[rng.integers(0, P, len(empty)), empty] = rng.integers(1, 9, len(empty))
+    heavy, heavy_cell = int(rng.integers(0, P)), int(rng.integers(0, N))
+    if planted is not None:
+        X[heavy, heavy_cell] = planted
+    sets = [np.sort(rng.permutation(P)[:k]) for k in sizes]
+    H = np.zeros((P, len(sizes)), np.int64)
+    for m, s in enumerate(sets):
+        H[s, m] = 1
+    bg = rng.integers(0, P, (B, P)).astype(np.int32)
+    if to_planted:
+        bg[0] = heavy
+    hp, hx, _ = csr_of(H)
+    return dict(X=X, H=H, bg=bg, csr=csr_of(X), hits=(hp, hx), sets=sets, heavy=heavy, heavy_cell=heavy_cell)
+
+
 def reference_of(case):
-    """(O, E, raw, bg_mean, bg_m2, s) of a make_case() result"""
+    """(O, E, raw, bg_mean, bg_m2, s) of a make_case() or make_arm_case() result"""
     full = np.vstack([np.arange(case["X"].shape[0])[None, :], case["bg"].astype(np.int64)])
     O, E = sums(case["X"], case["sets"], full)
     return (O, E) + statistics(O, E, case["X"].sum(axis=0), int(case["X"].sum()))
