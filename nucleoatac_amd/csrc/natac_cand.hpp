@@ -94,24 +94,60 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     double *Ew = smem + wave * Q * EWP;                       // Ew[q * EWP + u] <-> coordinate p_q - w - A + u
     const int k0 = (blockIdx.x * 4 + wave) * Q;
     if (k0 >= ncand) return;                                   // wave-uniform; no block-level synchronisation below
+    // ---- window staging.  Every address is known up front, so the loads go out in three rounds instead of one chain per candidate
+    // and entry: the wave's candidates, their chunks' lengths and bias offsets, then all NT entries a lane holds of all Q windows;
+    // nothing is used before the last one is requested.  The ev[][] registers are dead before the sweep's accumulators are live.
+    constexpr int NT = (CANDP_STRIDE + WAVE - 1) / WAVE;       // entries per lane and window (host-checked: EW <= CANDP_STRIDE)
     int chunk[Q], pos[Q];
-    bool esmall = false;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int k = (k0 + q < ncand) ? k0 + q : k0;          // tail: recompute candidate k0 (result discarded)
         chunk[q] = cand_chunk[k];
         pos[q] = cand_pos[k];
-        const int L = ct.chunk_len[chunk[q]];
-        const double *b = ct.bias ? ct.ebias + ct.bias_off[chunk[q]] : nullptr;     // exp(bias), natac_exp_bias
-        const int nb = L + ct.bias_left + ct.bias_right;
-        const int j0 = pos[q] - vm.w - A + ct.bias_left;
+    }
+    double ev[Q][NT];
+    if (ct.bias) {
+        int nb[Q];
+        const double *b[Q];                                    // exp(bias), natac_exp_bias
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            nb[q] = ct.chunk_len[chunk[q]] + ct.bias_left + ct.bias_right;
+            b[q] = ct.ebias + ct.bias_off[chunk[q]];
+        }
+        // an entry outside [0, nb) of the chunk's own slice is 0.0: its load reads the slice's nearest entry instead (nb >= 1:
+        // natac_batch_create refuses empty chunks), so no load is predicated and none leaves the slice
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int j0 = pos[q] - vm.w - A + ct.bias_left + lane;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) ev[q][t] = b[q][min(max(j0 + WAVE * t, 0), nb[q] - 1)];
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const int j0 = pos[q] - vm.w - A + ct.bias_left + lane;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int j = j0 + WAVE * t;
+                ev[q][t] = (j >= 0 && j < nb[q]) ? ev[q][t] : 0.0;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < Q; ++q)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) ev[q][t] = 1.0;
+    }
+    bool esmall = false;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
         double emin = __builtin_inf();
-        for (int u = lane; u < EW; u += WAVE) {
-            const int j = j0 + u;
-            double e = 1.0;
-            if (b) e = (j >= 0 && j < nb) ? b[j] : 0.0;
-            Ew[q * EWP + u] = e;
-            emin = fmin(emin, e);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int u = lane + WAVE * t;
+            if (u < EW) {                                      // entries u >= EW: neither written nor in the minimum
+                Ew[q * EWP + u] = ev[q][t];
+                emin = fmin(emin, ev[q][t]);
+            }
         }
         esmall |= !(wave_min(emin) > 0x1p-500);                // no product of two window values can underflow to 0 above this
     }
