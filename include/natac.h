@@ -55,8 +55,9 @@ extern "C" {
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
  * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
  * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`; 20: added
- * natac_motif_deviations_plan); the binding refuses another version */
-#define NATAC_ABI_VERSION 20
+ * natac_motif_deviations_plan; 21: added natac_group_rank_sums and natac_group_rank_sums_plan for `pyatac markers`); the binding refuses
+ * another version */
+#define NATAC_ABI_VERSION 21
 
 enum {
     NATAC_OK = 0,
@@ -573,6 +574,72 @@ int natac_motif_deviations(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *
  * the call refuses the shape: n_motifs * n_tiles >= 2^31 or m * (n_tiles + 1) > 2^33. */
 int natac_motif_deviations_plan(int64_t m, int64_t n, int64_t nnz, int32_t n_motifs, int64_t max_set, int64_t max_count, int32_t n_cu,
                                 int32_t *tile, int64_t *n_tiles, int32_t *lanes, int32_t *wide, int64_t *lds_bytes);
+/* ---- rank-sum marker windows per cell group (this library's own; `pyatac markers`) ----
+ * The command's rule, whole: a Wilcoxon rank-sum test of depth-normalised accessibility, one group against all other kept cells, for
+ * every window and every group.
+ * Cells and groups.  X is the windows x cells count matrix of `pyatac cellcounts`.  A cell is kept when the group table lists its
+ * barcode and its column sum is positive; unlisted cells are in no group and not in "the rest" either.  N cells stay,
+ * 2 <= N <= NATAC_MARKERS_MAX_CELLS.  d[c] is the kept cell's column sum over all windows, 1 <= d[c] < 2^31; grp[c] is in [0, G),
+ * G <= NATAC_MARKERS_MAX_GROUPS, and n_g is the group's number of kept cells.  A group with n_g = 0 or n_g = N gets NA everywhere.
+ * Values and ranks.  Window p has L entries (c, a) among the kept cells and z0 = N - L cells at value 0.  The value of an entry is the
+ * exact rational a / d[c]; order and ties are decided by comparing a_i * d_j with a_j * d_i in 64-bit integers (both factors are below
+ * 2^31, so no product overflows).  Midranks, with less_i / eq_i counted among the window's entries and eq_i including i itself: a zero
+ * cell has 2 * rank = z0 + 1, an entry has 2 * rank_i = 2 z0 + 2 less_i + eq_i + 1.
+ * Device outputs, exact integers.  detected[p, g] int32: the entries of group g.  total[p, g] int64: the sum of their counts.
+ * rank2[p, g] int64 = (n_g - detected)(z0 + 1) + the sum over the group's entries of 2 rank_i.  ties[p] int64 = (z0^3 - z0) + the sum over
+ * the entries of (eq_i^2 - 1), which is the sum over tie groups of (t^3 - t) without a sort.  An empty row is legal: rank2 = n_g (N + 1),
+ * ties = N^3 - N.
+ * Host, fp64, one window and group at a time, with n_r = N - n_g:  U = rank2 / 2 - n_g (n_g + 1) / 2,  mu = n_g n_r / 2,
+ * var = n_g n_r / 12 * ((N + 1) - ties / (N (N - 1))),  z = (U - mu - 0.5 sign(U - mu)) / sqrt(var), NaN where var == 0,
+ * p = min(1, 2 * norm.sf(|z|)) (scipy's asymptotic two-sided test with tie and continuity correction),  auc = U / (n_g n_r),
+ * pct_in = detected / n_g,  pct_rest = (row detected - detected) / n_r,
+ * log2fc = log2(((total + 1) / D_g) / ((row total - total + 1) / D_r)) with D_g the sum of d over the group's cells and D_r the sum over
+ * the rest (a pseudo-bulk ratio: integers in, no order-dependent float sum).  A window is tested when at least min_cells kept cells have
+ * an entry; untested windows are NA and do not enter the correction.  q is Benjamini-Hochberg per group over that group's tested
+ * windows with finite p, ties in p in index order, with a running minimum from the largest down.  A marker of g has q <= fdr,
+ * log2fc >= min_log2fc and auc > 0.5.
+ * Not done: bias-matched background cells, a logistic-regression or negative-binomial test, pairwise group contrasts, a test of motif
+ * deviations.
+ *
+ * This entry is the device part.  Operands: the counts of the kept cells, m windows and n = N cells, under the CSR rules of
+ * natac_sparse_lsi (count >= 1, columns strictly ascending in a row); empty rows are allowed.  depth[n] int64 is checked for [1, 2^31)
+ * only -- it need not be the matrix's column sum.  group[n] int32 in [0, n_groups), 1 <= n_groups <= NATAC_MARKERS_MAX_GROUPS,
+ * 2 <= n <= NATAC_MARKERS_MAX_CELLS, m * n_groups <= NATAC_MARKERS_MAX_OUT (Context.group_rank_sums cuts the rows into blocks under it;
+ * the result does not depend on the cut).  Outputs: detected int32, total and rank2 int64, each [m x n_groups] row-major, ties int64[m];
+ * arm_rows int64[3] (may be NULL): the rows the short, block and long arm took.  Everything is checked on the host before any launch; a
+ * failure returns NATAC_E_ARG, names the index and leaves the outputs untouched.
+ * Kernels (csrc/natac_markers.hpp), by a row's number of entries L: L <= short_max (NATAC_MARKERS_SHORT_CAP unless forced) a lane group
+ * of 16 / 32 / 64 lanes, one entry a lane, all pairs through cross-lane reads; L <= block_max (NATAC_MARKERS_BLOCK_CAP unless forced) a
+ * workgroup that sorts the row in LDS by the exact comparison and gives every entry the start and the length of its run of equal values
+ * by two binary searches; longer rows are sorted chunk by chunk in LDS into a work buffer, and every entry's less / eq come from a
+ * lower- and an upper-bound search in each sorted chunk of its row, a workgroup per chunk of entries.  The
+ * per-group sums are integer counters in LDS, the partial sums of a long row meet in the outputs through global integer atomics; there
+ * is no floating point on the device, so two calls give the same bytes under every threshold.  The environment's
+ * NATAC_MARKERS_SHORT_MAX (1 .. NATAC_MARKERS_SHORT_CAP) and NATAC_MARKERS_BLOCK_MAX (1 .. NATAC_MARKERS_BLOCK_CAP; below short_max it
+ * counts as short_max) force the thresholds, for the tests.  kernel_ms (may be NULL): device time of the call's kernels. */
+#define NATAC_MARKERS_MAX_OUT 33554432
+#define NATAC_MARKERS_MAX_CELLS 1048576
+#define NATAC_MARKERS_MAX_GROUPS 255
+#define NATAC_MARKERS_SHORT_CAP 64
+#define NATAC_MARKERS_BLOCK_CAP 8192
+int natac_group_rank_sums(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
+                          const int64_t *depth, const int32_t *group, int32_t n_groups, int32_t *detected, int64_t *total, int64_t *rank2,
+                          int64_t *ties, int64_t *arm_rows, double *kernel_ms);
+/* How natac_group_rank_sums launches for a matrix of m windows, n cells and nnz entries whose longest row has longest_row entries, with
+ * n_groups groups on a device of n_cu compute units (host only: no context, no GPU needed; it reads NATAC_MARKERS_SHORT_MAX and
+ * NATAC_MARKERS_BLOCK_MAX as the call does).  *short_max, *block_max: a row of L entries takes the short arm when L <= *short_max, else
+ * the block arm when L <= *block_max, else the long arm.  *lanes: the lanes of a row of the short arm, the least of 16 / 32 / 64 that
+ * holds min(*short_max, longest_row).  *chunk: the entries the long arm sorts at once, the largest power of two up to
+ * min(*block_max, 4096), at least 16.  wg[3]: the threads of a workgroup of the short, block and long arm.  lds_bytes[3]: a workgroup's
+ * dynamic LDS -- short: (256 / *lanes) rows' counters of 20 bytes a group; block: one row's counters, 16 bytes and 9 bytes an entry of
+ * the power of two at or above min(longest_row, *block_max) entries (at least 16); long: the larger of 8 bytes an entry of *chunk and one
+ * row's counters + 16; the counters rounded up to 16 bytes, and 0 for the block and long arm when longest_row leaves them no row.
+ * grid[2]: the workgroups of the short and the block kernel if every row took that arm, at most 8 n_cu each (both walk their rows with
+ * that stride).  NATAC_E_ARG for m < 1, n
+ * outside [2, NATAC_MARKERS_MAX_CELLS], longest_row above n or nnz, nnz above m n, n_groups outside [1, NATAC_MARKERS_MAX_GROUPS],
+ * m * n_groups above NATAC_MARKERS_MAX_OUT, n_cu < 1. */
+int natac_group_rank_sums_plan(int64_t m, int64_t n, int64_t nnz, int64_t longest_row, int32_t n_groups, int32_t n_cu, int32_t *short_max,
+                               int32_t *block_max, int32_t *lanes, int32_t *chunk, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -31,6 +31,7 @@
 #include "natac_peakcall.hpp"
 #include "natac_motifs.hpp"
 #include "natac_deviations.hpp"
+#include "natac_markers.hpp"
 #include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

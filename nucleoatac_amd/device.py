@@ -85,6 +85,20 @@ def motif_deviations_plan(n_windows, n_cells, nnz, n_motifs, max_set, max_count,
     return dict(tile=tile.value, n_tiles=n_tiles.value, lanes=lanes.value, wide=bool(wide.value), lds_bytes=lds.value)
 
 
+def group_rank_sums_plan(n_windows, n_cells, nnz, longest_row, n_groups, n_cu=256):
+    """how group_rank_sums launches for a matrix of n_windows x n_cells with nnz entries whose longest row has longest_row entries, with
+    n_groups groups on n_cu compute units (natac_group_rank_sums_plan; needs no GPU, reads NATAC_MARKERS_SHORT_MAX / NATAC_MARKERS_BLOCK_MAX
+    as the call does): dict of short_max, block_max, lanes, chunk, and per arm ("short", "block", "long") wg and lds_bytes, and grid
+    for the short and the block arm"""
+    v = [C.c_int32() for _ in range(4)]
+    wg, lds, grid = (C.c_int32 * 3)(), (C.c_int64 * 3)(), (C.c_int32 * 2)()
+    L.check(L.load().natac_group_rank_sums_plan(int(n_windows), int(n_cells), int(nnz), int(longest_row), int(n_groups), int(n_cu),
+                                                *[C.byref(x) for x in v], wg, lds, grid))
+    arms = ("short", "block", "long")
+    return dict(short_max=v[0].value, block_max=v[1].value, lanes=v[2].value, chunk=v[3].value, wg=dict(zip(arms, list(wg))),
+                lds_bytes=dict(zip(arms, list(lds))), grid=dict(zip(arms, list(grid))))
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 
@@ -515,6 +529,46 @@ class Context(object):
         if with_sums:
             res += tuple(sums)
         return res + (ms.value,) if with_kernel_ms else res
+
+    def group_rank_sums(self, indptr, indices, data, n_cells, depth, group, n_groups, with_kernel_ms=False, with_arm_rows=False, max_out=None):
+        """the device part of `pyatac markers` (natac_group_rank_sums; include/natac.h states the rule): (detected int32, total int64,
+        rank2 int64, each [n_windows, n_groups], ties int64[n_windows]).  indptr / indices / data are the CSR arrays of
+        region_cell_counts restricted to the kept cells (rows the windows, empty rows allowed, indices ascending within a row, data >= 1);
+        depth[n_cells] in [1, 2^31) and group[n_cells] in [0, n_groups) belong to the cells.  The rows go to the device in blocks of at
+        most max_out // n_groups (max_out defaults to NATAC_MARKERS_MAX_OUT and may only be lowered); the result does not depend on the
+        cut.  with_arm_rows: also int64[3], the rows the short, block and long arm took; with_kernel_ms: also the kernels' device time.
+        The returned arrays are filled only by blocks that succeed; a refused operand raises before anything is returned."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        da = np.ascontiguousarray(data, dtype=np.int32)
+        dp = np.ascontiguousarray(depth, dtype=np.int64)
+        gr = np.ascontiguousarray(group, dtype=np.int32)
+        n, G, m = int(n_cells), int(n_groups), ip.shape[0] - 1
+        if ip.ndim != 1 or m < 0 or ix.ndim != 1 or ix.shape != da.shape or dp.shape != (max(n, 0),) or gr.shape != dp.shape:
+            raise ValueError("indptr / indices / data must be CSR arrays, depth and group one per cell")
+        if m and int(ip[-1]) > ix.shape[0]:
+            raise ValueError("indptr points past the %d entries given" % ix.shape[0])
+        cap = L.MARKERS_MAX_OUT if max_out is None else int(max_out)
+        if not 1 <= cap <= L.MARKERS_MAX_OUT:
+            raise ValueError("max_out must be in [1, %d] (got %d)" % (L.MARKERS_MAX_OUT, cap))
+        step = max(1, cap // max(G, 1))
+        detected = np.zeros((m, max(G, 0)), dtype=np.int32)
+        total = np.zeros((m, max(G, 0)), dtype=np.int64)
+        rank2 = np.zeros((m, max(G, 0)), dtype=np.int64)
+        ties = np.zeros(m, dtype=np.int64)
+        arms, ms_all = np.zeros(3, dtype=np.int64), 0.0
+        for r0 in range(0, max(m, 1), step):          # m == 0 still makes the one call that checks the operands
+            r1 = min(m, r0 + step)
+            part, ms = np.zeros(3, dtype=np.int64), C.c_double(0)
+            L.check(self._lib.natac_group_rank_sums(self._h, r1 - r0, n, _ptr(ip[r0:r1 + 1]), _ptr(ix), _ptr(da), _ptr(dp), _ptr(gr), G,
+                                                    _ptr(detected[r0:r1]), _ptr(total[r0:r1]), _ptr(rank2[r0:r1]), _ptr(ties[r0:r1]),
+                                                    _ptr(part), C.byref(ms)))
+            arms += part
+            ms_all += ms.value
+        res = (detected, total, rank2, ties)
+        if with_arm_rows:
+            res += (arms,)
+        return res + (ms_all,) if with_kernel_ms else res
 
     def cell_site_qc(self, pos, tlen, cell, n_cells, site_center=None, site_minus=None, flank=1000, center=500, edge=100, peak_start=None,
                      peak_end=None, with_kernel_ms=False):

@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | peaks | motifs` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -17,12 +17,15 @@ two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windo
 the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
 `cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
 k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
-`cluster` -> `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
+`cluster` -> `deviations` / `markers` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
 sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
 the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  `deviations`, this package's
 own too, joins that matrix with the `cellcounts` matrix: per-cell motif accessibility deviations and z-scores against background window
 sets matched in GC content and accessibility, summed on the GPU, with a variability ranking of the motifs and, with the table `cluster`
-writes, the mean z-score per cluster.  The other pyatac tools (vplot, bias_vplot) are not part of
+writes, the mean z-score per cluster.  `markers`, this package's own as well, answers which windows distinguish a cluster from the rest:
+a Wilcoxon rank-sum test of depth-normalised accessibility, one group of that table against all other cells, for every window and group,
+the ranking done on the GPU in exact integers, with Benjamini-Hochberg q-values, a marker table and one BED file per group that the
+commands above take through --bed.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -268,6 +271,21 @@ def add_deviations_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output. Default is the count matrix's name without .cellcounts and its suffix")
 
 
+def add_markers_parser(sub):
+    p = sub.add_parser("markers", help="the windows that distinguish every cell group from the rest, by a rank-sum test")
+    p.add_argument("--counts", metavar="matrix", required=True,
+                   help="BASE.cellcounts.npz or BASE.cellcounts.mtx.gz (with its .barcodes.tsv and .regions.bed) as `cellcounts` writes them")
+    p.add_argument("--groups", metavar="table", required=True, help="TAB-separated: barcode, group (the table `cluster` writes)")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--min_cells", metavar="int", default=10, type=int,
+                   help="A window is tested when at least this many kept cells have a count in it. Default is 10")
+    p.add_argument("--fdr", metavar="float", default=0.05, type=float, help="A marker has a q-value of at most this. Default is 0.05")
+    p.add_argument("--min_log2fc", metavar="float", default=0.5, type=float,
+                   help="A marker has a pseudo-bulk log2 fold change of at least this. Default is 0.5")
+    p.add_argument("--top", metavar="int", default=None, type=int, help="Cut every group's BED file at this many markers")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the count matrix's name without .cellcounts and its suffix")
+
+
 def pyatac_parser():
     from .. import __version__
     parser = argparse.ArgumentParser(prog="pyatac", description="pyatac: the Tn5 PWM, the fragment-size distribution, the per-base "
@@ -276,7 +294,7 @@ def pyatac_parser():
                                                                 "split by cell group, its cell-by-window count matrix, the discovery "
                                                                 "of its cells and their TSS enrichment and fraction of fragments in peaks; "
                                                                 "enriched regions (peaks) of a fragment store; the sites of TF motifs in a genome; "
-                                                                "per-cell motif accessibility deviations")
+                                                                "per-cell motif accessibility deviations; marker windows of cell groups")
     parser.add_argument("--version", action="version", version="%(prog)s " + __version__)
     sub = parser.add_subparsers(dest="call")
     sub.required = True
@@ -294,6 +312,7 @@ def pyatac_parser():
     add_cellcounts_parser(sub)
     add_cluster_parser(sub)
     add_deviations_parser(sub)
+    add_markers_parser(sub)
     add_peaks_parser(sub)
     add_motifs_parser(sub)
     return parser
@@ -422,6 +441,16 @@ def pyatac_main(args):
             get_deviations(args)
         except (DeviationsError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac deviations: %s\n" % e)
+            return 1
+    elif args.call == "markers":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .get_markers import MarkersError, get_markers
+        print("---------Getting marker windows per cell group-----------------------------------")
+        try:
+            get_markers(args)
+        except (MarkersError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac markers: %s\n" % e)
             return 1
     elif args.call == "peaks":
         from .._lib import NatacError
