@@ -55,9 +55,9 @@ extern "C" {
  * natac_frag_cells_device and natac_cells_counts / _read / _close for `pyatac cells`; 14: added natac_cell_site_qc for `pyatac cellqc`;
  * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
  * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`; 20: added
- * natac_motif_deviations_plan; 21: added natac_group_rank_sums and natac_group_rank_sums_plan for `pyatac markers`); the binding refuses
- * another version */
-#define NATAC_ABI_VERSION 21
+ * natac_motif_deviations_plan; 21: added natac_group_rank_sums and natac_group_rank_sums_plan for `pyatac markers`; 22: added
+ * natac_window_pair_sums and natac_window_pair_sums_plan for `pyatac coaccess`); the binding refuses another version */
+#define NATAC_ABI_VERSION 22
 
 enum {
     NATAC_OK = 0,
@@ -640,6 +640,64 @@ int natac_group_rank_sums(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *r
  * m * n_groups above NATAC_MARKERS_MAX_OUT, n_cu < 1. */
 int natac_group_rank_sums_plan(int64_t m, int64_t n, int64_t nnz, int64_t longest_row, int32_t n_groups, int32_t n_cu, int32_t *short_max,
                                int32_t *block_max, int32_t *lanes, int32_t *chunk, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
+/* ---- co-accessible window pairs (this library's own; `pyatac coaccess`) ----
+ * The command's rule, whole: the Pearson correlation over the cells of every two windows of one chromosome that lie within a genomic
+ * distance of each other, with a t-test, Benjamini-Hochberg q-values and a list of links.
+ * Cells.  X is the windows x cells count matrix of `pyatac cellcounts`.  A cell is kept when its column sum is positive.  With a group
+ * table (--aggregate: the table `pyatac cluster` writes, at most 255 groups) the columns are first summed per group on the host: the
+ * "cells" are then the groups that have a count, and unlisted barcodes are dropped (the metacell form).  With --binarize every entry
+ * counts as 1, before the aggregation.  N cells stay, 3 <= N <= NATAC_COACCESS_MAX_CELLS.
+ * Windows.  Window p has entries a[p, c] >= 1 and det[p] = their number, S1[p] = sum a, S2[p] = sum a^2, all int64 on the host.  A window
+ * is tested when det[p] >= min_cells; its centre is (start + end) // 2.
+ * Pairs.  Per chromosome the tested windows are ranked by (centre, index).  A pair is two tested windows of one chromosome whose centres
+ * differ by at most max_distance (in [0, 10^8]); it is listed once, under the member that ranks first (its owner), in rank order of the
+ * partner; the chromosomes go in order of first appearance in the region list.
+ * Device outputs, exact integers, per pair (p, q):  sxy int64 = the sum over the cells of a[p, c] * a[q, c],  both int32 = the number of
+ * cells with an entry in both.
+ * The bound.  With a_max the largest count of the matrix and L_max the longest listed row, a call needs N * a_max^2 * L_max < 2^62: then
+ * every sxy, N * sxy, S1[p] * S1[q] and N * S2 - S1^2 fit in int64.
+ * Host, fp64, one pair at a time:  num = N * sxy - S1[p] * S1[q] and D[p] = N * S2[p] - S1[p]^2 in int64;
+ * r = float(num) / sqrt(float(D[p]) * float(D[q])) clipped to [-1, 1], NaN where a D is 0;  t = r * sqrt((N - 2) / ((1 - r) * (1 + r)));
+ * p = 2 * t.sf(|t|, N - 2), and 0 where |r| == 1;  q is Benjamini-Hochberg over all pairs with a finite p (as `markers` forms it).  A link
+ * has r >= min_cor (in [-1, 1]) and q <= fdr (in (0, 1]).
+ * Not done: kNN metacells picked by the command itself, a depth or GC covariate, graphical-lasso regularisation as in Cicero, a
+ * cross-chromosome background, a peak-to-gene step (the package has no gene model or expression input).
+ *
+ * This entry is the device part.  Operands: the counts as natac_group_rank_sums takes them -- CSR, m rows and n cells, count >= 1,
+ * columns strictly ascending in a row, empty rows allowed; 1 <= n <= NATAC_COACCESS_MAX_CELLS, m < 2^31.  order[k] int32: the row ids of
+ * the listed windows in rank sequence, in [0, m), not necessarily distinct; k < 2^31.  hi[k] int64: the partners of order[i] are
+ * order[i + 1 .. hi[i]), i < hi[i] <= k.  pair_ptr[k + 1] int64: pair_ptr[0] == 0 and pair_ptr[i + 1] - pair_ptr[i] == hi[i] - i - 1; the
+ * pairs of owner i start at pair_ptr[i], and pair_ptr[k] <= NATAC_COACCESS_MAX_PAIRS (Context.window_pair_sums cuts the owners into
+ * blocks under it; the result does not depend on the cut).  Outputs: sxy int64 and both int32, [pair_ptr[k]] each; arm_owners int64[2]
+ * (may be NULL): the owners with at least one partner that the table and the search arm took.  Everything is checked on the host before
+ * any launch, the bound above included (its message names N, a_max and L_max); a failure returns NATAC_E_ARG, names the index and leaves
+ * the outputs untouched.  k == 0 or pair_ptr[k] == 0 returns NATAC_OK without a launch.
+ * Kernels (csrc/natac_coaccess.hpp): a workgroup of 256 threads owns one window at a time, at most 8 n_cu workgroups with a grid stride
+ * over the owners; the owner's row sits in LDS and every partner row goes to a lane group of 16 / 32 / 64 lanes (the least that holds
+ * ceil(listed entries / k)), a lane taking the partner's entries with that stride; the group's sums meet by cross-lane reads and one
+ * lane stores the pair.  Table arm, n <= table_max (NATAC_COACCESS_TABLE_CAP unless forced): a dense LDS table of the owner's counts over
+ * all cells, zeroed once per workgroup, written and cleared at the owner's columns only, one LDS read per partner entry.  Search arm,
+ * any n: the owner's (cell, count) pairs in LDS, at most chunk (NATAC_COACCESS_CHUNK_CAP unless forced) at a time, a binary search per
+ * partner entry; the first chunk of an owner stores the pair, later chunks add to it with plain loads and stores.  No atomics and no
+ * floating point: two calls give the same bytes under every table_max and chunk.  The environment's NATAC_COACCESS_TABLE_MAX
+ * (1 .. NATAC_COACCESS_TABLE_CAP) and NATAC_COACCESS_CHUNK (a power of two in 16 .. NATAC_COACCESS_CHUNK_CAP; any other value is ignored)
+ * force them, for the tests.  kernel_ms (may be NULL): device time of the call's kernel. */
+#define NATAC_COACCESS_MAX_PAIRS 33554432
+#define NATAC_COACCESS_MAX_CELLS 1048576
+#define NATAC_COACCESS_TABLE_CAP 16384
+#define NATAC_COACCESS_CHUNK_CAP 8192
+int natac_window_pair_sums(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *row_ptr, const int32_t *col, const int32_t *count,
+                           int64_t k, const int32_t *order, const int64_t *hi, const int64_t *pair_ptr,
+                           int64_t *sxy, int32_t *both, int64_t *arm_owners, double *kernel_ms);
+/* How natac_window_pair_sums launches for a matrix of m windows, n cells and nnz entries of which k windows are listed, with
+ * listed_entries entries between them (counted with multiplicity), on a device of n_cu compute units (host only: no context, no GPU
+ * needed; it reads NATAC_COACCESS_TABLE_MAX and NATAC_COACCESS_CHUNK as the call does).  *arm: 0 the table arm (n <= *table_max), 1 the
+ * search arm.  *lanes: the lanes of a partner row, the least of 16 / 32 / 64 that holds ceil(listed_entries / k).  *chunk: the owner's
+ * entries the search arm holds at once.  *wg: the threads of a workgroup.  *lds_bytes: a workgroup's dynamic LDS -- table: 4 n rounded
+ * up to 16; search: 8 *chunk.  *grid: the workgroups of the launch if every listed window has a partner, min(k, 8 n_cu).  NATAC_E_ARG
+ * for m or k outside [1, 2^31), n outside [1, NATAC_COACCESS_MAX_CELLS], nnz above m n, listed_entries above k n, n_cu < 1. */
+int natac_window_pair_sums_plan(int64_t m, int64_t n, int64_t nnz, int64_t k, int64_t listed_entries, int32_t n_cu, int32_t *arm,
+                                int32_t *table_max, int32_t *lanes, int32_t *chunk, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

@@ -32,6 +32,7 @@
 #include "natac_motifs.hpp"
 #include "natac_deviations.hpp"
 #include "natac_markers.hpp"
+#include "natac_coaccess.hpp"
 #include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

@@ -99,6 +99,18 @@ def group_rank_sums_plan(n_windows, n_cells, nnz, longest_row, n_groups, n_cu=25
                 lds_bytes=dict(zip(arms, list(lds))), grid=dict(zip(arms, list(grid))))
 
 
+def window_pair_sums_plan(n_windows, n_cells, nnz, n_listed, listed_entries, n_cu=256):
+    """how window_pair_sums launches for a matrix of n_windows x n_cells with nnz entries of which n_listed windows are listed, with
+    listed_entries entries between them, on n_cu compute units (natac_window_pair_sums_plan; needs no GPU, reads NATAC_COACCESS_TABLE_MAX /
+    NATAC_COACCESS_CHUNK as the call does): dict of arm ("table" / "search"), table_max, lanes, chunk, wg, lds_bytes and grid"""
+    v = [C.c_int32() for _ in range(5)]
+    lds, grid = C.c_int64(), C.c_int32()
+    L.check(L.load().natac_window_pair_sums_plan(int(n_windows), int(n_cells), int(nnz), int(n_listed), int(listed_entries), int(n_cu),
+                                                 *([C.byref(x) for x in v] + [C.byref(lds), C.byref(grid)])))
+    return dict(arm=("table", "search")[v[0].value], table_max=v[1].value, lanes=v[2].value, chunk=v[3].value, wg=v[4].value,
+                lds_bytes=lds.value, grid=grid.value)
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 
@@ -567,6 +579,70 @@ class Context(object):
             ms_all += ms.value
         res = (detected, total, rank2, ties)
         if with_arm_rows:
+            res += (arms,)
+        return res + (ms_all,) if with_kernel_ms else res
+
+    def window_pair_sums(self, indptr, indices, data, n_cells, order, hi, with_arm_owners=False, with_kernel_ms=False, max_pairs=None):
+        """the device part of `pyatac coaccess` (natac_window_pair_sums; include/natac.h states the rule): (sxy int64, both int32), one
+        element per pair.  indptr / indices / data are the CSR arrays of region_cell_counts (rows the windows, empty rows allowed, indices
+        ascending within a row, data >= 1).  order[k] lists rows in rank sequence; owner i is paired with order[i + 1 .. hi[i]),
+        i < hi[i] <= k, and its pairs follow those of owner i - 1.  The owners go to the device in consecutive blocks of at most
+        max_pairs pairs (max_pairs defaults to NATAC_COACCESS_MAX_PAIRS and may only be lowered; ValueError if one owner alone has more),
+        one call per block with the slice of `order` its partners need; the result does not depend on the cut.  ValueError as well for
+        an hi outside its range and where N * a_max^2 * L_max reaches 2^62 (n_cells, the largest count, the longest listed row).
+        with_arm_owners: also int64[2], the owners with a partner that the table and the search arm took; with_kernel_ms: also the
+        kernels' device time.  A refused operand raises before anything is returned."""
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        da = np.ascontiguousarray(data, dtype=np.int32)
+        od = np.ascontiguousarray(order, dtype=np.int32)
+        h = np.ascontiguousarray(hi, dtype=np.int64)
+        n, m, k = int(n_cells), ip.shape[0] - 1, od.shape[0]
+        if ip.ndim != 1 or m < 0 or ix.ndim != 1 or ix.shape != da.shape or od.ndim != 1 or h.shape != od.shape:
+            raise ValueError("indptr / indices / data must be CSR arrays, order and hi one per listed window")
+        if m and int(ip[-1]) > ix.shape[0]:
+            raise ValueError("indptr points past the %d entries given" % ix.shape[0])
+        cap = L.COACCESS_MAX_PAIRS if max_pairs is None else int(max_pairs)
+        if not 1 <= cap <= L.COACCESS_MAX_PAIRS:
+            raise ValueError("max_pairs must be in [1, %d] (got %d)" % (L.COACCESS_MAX_PAIRS, cap))
+        own = np.arange(k, dtype=np.int64)
+        bad = np.flatnonzero((h <= own) | (h > k))
+        if len(bad):
+            raise ValueError("hi[%d] = %d outside (%d, %d]" % (bad[0], h[bad[0]], bad[0], k))
+        if k and m and ((od < 0) | (od >= m)).any():
+            w = int(np.flatnonzero((od < 0) | (od >= m))[0])
+            raise ValueError("order[%d] = %d outside [0, %d)" % (w, od[w], m))
+        if k and m and len(da):
+            a_max, l_max = int(da.max()), int(np.diff(ip)[od].max())
+            if n * a_max * a_max * l_max >= 1 << 62:
+                raise ValueError("N * a_max^2 * L_max must be below 2^62: N = %d cells, a_max = %d the largest count, L_max = %d the longest "
+                                 "listed row" % (n, a_max, l_max))
+        n_part = h - own - 1
+        if k and int(n_part.max()) > cap:
+            w = int(np.argmax(n_part > cap))
+            raise ValueError("owner %d alone has %d partners, more than max_pairs = %d" % (w, n_part[w], cap))
+        ptr = np.zeros(k + 1, dtype=np.int64)
+        np.cumsum(n_part, out=ptr[1:])
+        sxy, both = np.zeros(int(ptr[-1]), dtype=np.int64), np.zeros(int(ptr[-1]), dtype=np.int32)
+        arms, ms_all = np.zeros(2, dtype=np.int64), 0.0
+        i0 = 0
+        while True:                                   # k == 0 still makes the one call that checks the operands
+            i1 = min(k, max(i0 + 1, int(np.searchsorted(ptr, ptr[i0] + cap, side="right")) - 1))
+            end = int(h[i0:i1].max()) if i1 > i0 else i0                   # the block's partners reach order[end - 1]
+            # the partners past the block's owners are listed without partners of their own
+            h_blk = np.concatenate([h[i0:i1] - i0, np.arange(i1 - i0 + 1, end - i0 + 1, dtype=np.int64)])
+            p_blk = np.concatenate([ptr[i0:i1 + 1] - ptr[i0], np.full(end - i1, ptr[i1] - ptr[i0], dtype=np.int64)])
+            o_blk = np.ascontiguousarray(od[i0:end])
+            part, ms = np.zeros(2, dtype=np.int64), C.c_double(0)
+            L.check(self._lib.natac_window_pair_sums(self._h, m, n, _ptr(ip), _ptr(ix), _ptr(da), end - i0, _ptr(o_blk), _ptr(h_blk), _ptr(p_blk),
+                                                     _ptr(sxy[ptr[i0]:ptr[i1]]), _ptr(both[ptr[i0]:ptr[i1]]), _ptr(part), C.byref(ms)))
+            arms += part
+            ms_all += ms.value
+            i0 = i1
+            if i0 >= k:
+                break
+        res = (sxy, both)
+        if with_arm_owners:
             res += (arms,)
         return res + (ms_all,) if with_kernel_ms else res
 

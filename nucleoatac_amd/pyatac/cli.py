@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | peaks | motifs` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | coaccess | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -17,7 +17,7 @@ two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windo
 the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
 `cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
 k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
-`cluster` -> `deviations` / `markers` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
+`cluster` -> `deviations` / `markers` / `coaccess` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
 sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
 the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  `deviations`, this package's
 own too, joins that matrix with the `cellcounts` matrix: per-cell motif accessibility deviations and z-scores against background window
@@ -25,7 +25,10 @@ sets matched in GC content and accessibility, summed on the GPU, with a variabil
 writes, the mean z-score per cluster.  `markers`, this package's own as well, answers which windows distinguish a cluster from the rest:
 a Wilcoxon rank-sum test of depth-normalised accessibility, one group of that table against all other cells, for every window and group,
 the ranking done on the GPU in exact integers, with Benjamini-Hochberg q-values, a marker table and one BED file per group that the
-commands above take through --bed.  The other pyatac tools (vplot, bias_vplot) are not part of
+commands above take through --bed.  `coaccess`, this package's own too, answers which windows open and close together: the Pearson
+correlation over the cells (or, with --aggregate, over the clusters of that table as metacells) of every two windows of a chromosome
+within --max_distance of each other, the sparse row intersections done on the GPU in exact integers, with a t-test, Benjamini-Hochberg
+q-values and a BEDPE file of links.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -217,6 +220,23 @@ def add_cluster_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output. Default is the matrix file's name without .cellcounts and its suffix")
 
 
+def add_coaccess_parser(sub):
+    p = sub.add_parser("coaccess", help="the pairs of nearby windows that open and close together, by a correlation over the cells")
+    p.add_argument("--counts", metavar="matrix", required=True,
+                   help="BASE.cellcounts.npz or BASE.cellcounts.mtx.gz (with its .barcodes.tsv and .regions.bed) as `cellcounts` writes them")
+    p.add_argument("--aggregate", metavar="table", help="TAB-separated: barcode, group (the table `cluster` writes). The counts are summed "
+                   "per group first and the groups are the cells (metacells)")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--binarize", action="store_true", default=False, help="Every entry of the matrix counts as 1 (before --aggregate)")
+    p.add_argument("--min_cells", metavar="int", default=10, type=int,
+                   help="A window is tested when at least this many cells have a count in it. Default is 10")
+    p.add_argument("--max_distance", metavar="int", default=250000, type=int,
+                   help="Two windows are paired when their centres are at most this far apart. Default is 250000")
+    p.add_argument("--min_cor", metavar="float", default=0.5, type=float, help="A link has a correlation of at least this. Default is 0.5")
+    p.add_argument("--fdr", metavar="float", default=0.05, type=float, help="A link has a q-value of at most this. Default is 0.05")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the count matrix's name without .cellcounts and its suffix")
+
+
 def add_peaks_parser(sub):
     p = sub.add_parser("peaks", help="call enriched regions (peaks) from the insertions of a fragment store")
     p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
@@ -313,6 +333,7 @@ def pyatac_parser():
     add_cluster_parser(sub)
     add_deviations_parser(sub)
     add_markers_parser(sub)
+    add_coaccess_parser(sub)
     add_peaks_parser(sub)
     add_motifs_parser(sub)
     return parser
@@ -451,6 +472,16 @@ def pyatac_main(args):
             get_markers(args)
         except (MarkersError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac markers: %s\n" % e)
+            return 1
+    elif args.call == "coaccess":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .get_coaccess import CoaccessError, get_coaccess
+        print("---------Getting co-accessible window pairs----------------------------------------")
+        try:
+            get_coaccess(args)
+        except (CoaccessError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac coaccess: %s\n" % e)
             return 1
     elif args.call == "peaks":
         from .._lib import NatacError
