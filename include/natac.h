@@ -56,8 +56,9 @@ extern "C" {
  * 15: added natac_enriched_regions for `pyatac peaks`; 16: added natac_sparse_lsi for `pyatac cluster`; 17: added natac_peaks_plan; 18: added natac_motif_scan for
  * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`; 20: added
  * natac_motif_deviations_plan; 21: added natac_group_rank_sums and natac_group_rank_sums_plan for `pyatac markers`; 22: added
- * natac_window_pair_sums and natac_window_pair_sums_plan for `pyatac coaccess`); the binding refuses another version */
-#define NATAC_ABI_VERSION 22
+ * natac_window_pair_sums and natac_window_pair_sums_plan for `pyatac coaccess`; 23: added natac_gene_cell_scores and
+ * natac_gene_cell_scores_plan for `pyatac genescores`); the binding refuses another version */
+#define NATAC_ABI_VERSION 23
 
 enum {
     NATAC_OK = 0,
@@ -661,7 +662,7 @@ int natac_group_rank_sums_plan(int64_t m, int64_t n, int64_t nnz, int64_t longes
  * p = 2 * t.sf(|t|, N - 2), and 0 where |r| == 1;  q is Benjamini-Hochberg over all pairs with a finite p (as `markers` forms it).  A link
  * has r >= min_cor (in [-1, 1]) and q <= fdr (in (0, 1]).
  * Not done: kNN metacells picked by the command itself, a depth or GC covariate, graphical-lasso regularisation as in Cicero, a
- * cross-chromosome background, a peak-to-gene step (the package has no gene model or expression input).
+ * cross-chromosome background, a peak-to-gene step (`genescores` has the genes, but the package has no expression input).
  *
  * This entry is the device part.  Operands: the counts as natac_group_rank_sums takes them -- CSR, m rows and n cells, count >= 1,
  * columns strictly ascending in a row, empty rows allowed; 1 <= n <= NATAC_COACCESS_MAX_CELLS, m < 2^31.  order[k] int32: the row ids of
@@ -698,6 +699,65 @@ int natac_window_pair_sums(natac_ctx *ctx, int64_t m, int64_t n, const int64_t *
  * for m or k outside [1, 2^31), n outside [1, NATAC_COACCESS_MAX_CELLS], nnz above m n, listed_entries above k n, n_cu < 1. */
 int natac_window_pair_sums_plan(int64_t m, int64_t n, int64_t nnz, int64_t k, int64_t listed_entries, int32_t n_cu, int32_t *arm,
                                 int32_t *table_max, int32_t *lanes, int32_t *chunk, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
+/* ---- distance-weighted gene activity per cell (this library's own; `pyatac genescores`) ----
+ * The command's rule, whole: per gene and cell, the sum over the cell's Tn5 insertions around the gene of an integer weight that falls
+ * with the distance to the gene body (the gene-score model ArchR made usual), as a sparse matrix in the layout of `pyatac cellcounts`.
+ * Genes.  A BED row (chrom, start, end, name, strand), end - start >= 1; rows stay in file order, names need not be unique.
+ * Extended body, with u = --upstream in [0, 2^20]:  [bs, be) = [max(0, start - u), end) for a plus gene, [start, end + u) for a minus gene.
+ * Window, with 0 <= e_min <= e_max <= 2^20, per chromosome:  prev(g) = the largest be_h over the other genes h with be_h <= bs_g
+ * (-infinity if none), next(g) = the smallest bs_h over the other genes with bs_h >= be_g (+infinity if none);
+ * wl = max(0, max(bs - e_max, min(bs - e_min, prev))),  wh = min(be + e_max, max(be + e_min, next)):  the window reaches up to e_max on
+ * either side, stops at the nearest gene that lies wholly beyond, and always reaches at least e_min; genes that overlap g do not limit
+ * it, and --no_boundaries takes prev = -infinity, next = +infinity.  Integer work on the host.
+ * Weights, with D = --decay in [1, 10^7] and U = --unit in [4, 65536]:  w[d] = int(rint(U * (exp(-d / D) + exp(-1)))) for d = 0 .. e_max,
+ * int32, formed once on the host in fp64; every w[d] >= 1.
+ * Records.  A record is the fragment l = pos + 4, ilen = tlen - 8, r = l + ilen - 1 (the ATAC offsets of natac_region_counts) and counts
+ * when lower <= ilen < upper.  Its two insertions are l and r; each counts on its own, also when r == l or r == l - 1.
+ * Score.  An insertion x with wl <= x < wh has the distance d = 0 when bs <= x < be, d = bs - x to the left of the body and
+ * d = x - be + 1 to the right, and adds w[d] to entry (gene, cell).  An entry exists where at least one insertion hit; its value is the
+ * exact integer sum.
+ * Not done: gene-length scale factors (a constant per gene, without effect on a per-gene rank test), the 500-base tiles ArchR sums over,
+ * a ceiling per tile, depth normalisation of the written values (`markers` divides by the column sum itself), an expression input,
+ * peak-to-gene links, GTF or GFF parsing.
+ *
+ * This entry is the device part, one chromosome per call, and follows natac_region_cell_counts throughout.  Operands: pos[n_frags]
+ * non-decreasing, tlen, cell in [0, n_cells), n_cells in [1, NATAC_SPLIT_MAX_BARCODES].  Per gene win_lo <= body_lo <= body_hi <= win_hi,
+ * body_lo - win_lo < n_w and win_hi - body_hi < n_w; genes may overlap, repeat and come in any order.  1 <= n_w <= 2^20 + 1 and
+ * 1 <= weight[d] <= NATAC_GENESCORES_MAX_WEIGHT.  0 <= lower < upper <= 50000.
+ * Outputs: CSR with one row per gene in the given order, col (the cell) strictly ascending within a row, val the sum.  row_ptr[n_genes + 1]
+ * is written by every call that passes the checks.  col == val == NULL with cap == 0 is the sizing call; a cap below row_ptr[n_genes]
+ * returns NATAC_E_ARG with col and val untouched.  hits[n_genes] (may be NULL): the insertions that counted per gene.  arm_rows[2] (may
+ * be NULL): the non-empty rows the short and the table arm took.  kernel_ms (may be NULL): device time from the first to the last kernel.
+ * Checks: everything above on the host before any launch; a failure returns NATAC_E_ARG, names the index and leaves the outputs
+ * untouched.  The one bound that needs the device, hits[g] * max(weight) < 2^31, is checked by the entry between the counting pass and
+ * the first sum (the message names the gene, nothing is written): with it no 32-bit counter and no val can wrap.  n_genes == 0 or
+ * n_frags == 0 writes zeros and launches nothing.
+ * Kernels (csrc/natac_genescores.hpp).  The candidates of a row are one contiguous range of records (natac_region_ranges with
+ * start = win_lo, end = win_hi).  Rows go by their hits h.  Short arm, h <= short_max (NATAC_GENESCORES_SHORT_CAP unless forced): one wave
+ * per row, the (cell, weight) pairs sorted by cell by a bitonic network over the lanes, run heads by one ballot, a run's sum by a
+ * segmented cross-lane scan.  Table arm, every other row: one workgroup of 256 threads per (row, cell tile); a tile is at most
+ * NATAC_GENESCORES_TILE_CAP cells, one 32-bit LDS counter each, and there are ceil(n_cells / tile) tiles; the threads walk the row's
+ * candidates and add with integer LDS atomics, then every thread scans its contiguous run of the tile's words and a block scan places
+ * the (cell, value) pairs in ascending order.  Both arms run a count pass and, behind a scan of the counts, a fill pass; there is no
+ * staging area.  No floating point, no global atomics on the sums: the same bytes from two calls, under every short_max and tile, and
+ * from any split of the genes into calls.  The environment's NATAC_GENESCORES_SHORT_MAX (1 .. NATAC_GENESCORES_SHORT_CAP) and
+ * NATAC_GENESCORES_TILE (a power of two in 16 .. NATAC_GENESCORES_TILE_CAP; any other value is ignored) force them, for the tests. */
+#define NATAC_GENESCORES_SHORT_CAP 64
+#define NATAC_GENESCORES_TILE_CAP 16384
+#define NATAC_GENESCORES_MAX_WEIGHT 1048576
+int natac_gene_cell_scores(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, const int64_t *tlen, const int32_t *cell, int32_t n_cells,
+                           int64_t n_genes, const int64_t *win_lo, const int64_t *win_hi, const int64_t *body_lo, const int64_t *body_hi,
+                           int32_t n_w, const int32_t *weight, int lower, int upper,
+                           int64_t *row_ptr, int64_t cap, int32_t *col, int32_t *val, int64_t *hits, int64_t *arm_rows, double *kernel_ms);
+/* How natac_gene_cell_scores launches for n_genes genes and n_cells cells of which table_rows rows take the table arm, on a device of
+ * n_cu compute units (host only: no context, no GPU needed; it reads NATAC_GENESCORES_SHORT_MAX and NATAC_GENESCORES_TILE as the call
+ * does).  *short_max: rows of at most this many hits take the short arm.  *tile: the cells of a table tile -- unless forced, the least
+ * power of two that holds n_cells, between 256 and NATAC_GENESCORES_TILE_CAP.  *n_tiles: ceil(n_cells / *tile).  *wg: the threads of a
+ * workgroup.  *lds_bytes: a table workgroup's dynamic LDS, 4 *tile.  *grid: the workgroups of the table launch,
+ * min(table_rows * *n_tiles, 8 n_cu).  NATAC_E_ARG for n_genes outside [1, 2^40), n_cells outside [1, NATAC_SPLIT_MAX_BARCODES],
+ * table_rows outside [0, n_genes], n_cu < 1. */
+int natac_gene_cell_scores_plan(int64_t n_genes, int32_t n_cells, int64_t table_rows, int32_t n_cu, int32_t *short_max, int32_t *tile,
+                                int32_t *n_tiles, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

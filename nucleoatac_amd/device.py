@@ -111,6 +111,17 @@ def window_pair_sums_plan(n_windows, n_cells, nnz, n_listed, listed_entries, n_c
                 lds_bytes=lds.value, grid=grid.value)
 
 
+def gene_cell_scores_plan(n_genes, n_cells, table_rows, n_cu=256):
+    """how gene_cell_scores launches for n_genes genes and n_cells cells of which table_rows rows take the table arm, on n_cu compute
+    units (natac_gene_cell_scores_plan; needs no GPU, reads NATAC_GENESCORES_SHORT_MAX / NATAC_GENESCORES_TILE as the call does): dict of
+    short_max, tile, n_tiles, wg, lds_bytes and grid"""
+    v = [C.c_int32() for _ in range(4)]
+    lds, grid = C.c_int64(), C.c_int32()
+    L.check(L.load().natac_gene_cell_scores_plan(int(n_genes), int(n_cells), int(table_rows), int(n_cu),
+                                                 *([C.byref(x) for x in v] + [C.byref(lds), C.byref(grid)])))
+    return dict(short_max=v[0].value, tile=v[1].value, n_tiles=v[2].value, wg=v[3].value, lds_bytes=lds.value, grid=grid.value)
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 
@@ -453,6 +464,45 @@ class Context(object):
         nnz = int(indptr[-1])
         out = (indptr, col[:nnz].copy(), val[:nnz].copy())
         return out + (ms.value,) if with_kernel_ms else out
+
+    def gene_cell_scores(self, pos, tlen, cell, n_cells, win_lo, win_hi, body_lo, body_hi, weight, lower, upper, with_hits=False,
+                         with_arm_rows=False, with_kernel_ms=False):
+        """the device part of `pyatac genescores` for one chromosome (natac_gene_cell_scores; include/natac.h states the rule): CSR with
+        one row per gene in the given order, (indptr int64[n_genes + 1], indices int32[nnz], data int32[nnz]); within a row the cell
+        indices ascend, data is the exact sum of weight[d] over the cell's insertions in [win_lo, win_hi), d the distance to
+        [body_lo, body_hi).  pos (sorted) / tlen / cell as region_cell_counts takes them; weight int32[n_w], every element in
+        [1, NATAC_GENESCORES_MAX_WEIGHT].  A sizing call, then the filling call.  with_hits: also int64[n_genes], the insertions that
+        counted per gene; with_arm_rows: also int64[2], the non-empty rows the short and the table arm took; with_kernel_ms: also the
+        kernels' device time of both calls.  A refused operand raises before anything is returned."""
+        p = np.ascontiguousarray(pos, dtype=np.int64)
+        t = np.ascontiguousarray(tlen, dtype=np.int64)
+        ce = np.ascontiguousarray(cell, dtype=np.int32)
+        g = [np.ascontiguousarray(a, dtype=np.int64) for a in (win_lo, win_hi, body_lo, body_hi)]
+        w = np.ascontiguousarray(weight, dtype=np.int32)
+        if p.ndim != 1 or p.shape != t.shape or p.shape != ce.shape or g[0].ndim != 1 or any(a.shape != g[0].shape for a in g) or w.ndim != 1:
+            raise ValueError("pos / tlen / cell, the four gene arrays and weight must be 1-d arrays of one length each")
+        ng = g[0].shape[0]
+        indptr = np.zeros(ng + 1, dtype=np.int64)
+        hits, arms = np.zeros(ng, dtype=np.int64), np.zeros(2, dtype=np.int64)
+        ms, ms_all = C.c_double(0), 0.0
+
+        def call(cap, col, val):
+            L.check(self._lib.natac_gene_cell_scores(self._h, p.shape[0], _ptr(p), _ptr(t), _ptr(ce), int(n_cells), ng, _ptr(g[0]), _ptr(g[1]),
+                                                     _ptr(g[2]), _ptr(g[3]), w.shape[0], _ptr(w), int(lower), int(upper), _ptr(indptr), cap,
+                                                     _ptr(col), _ptr(val), _ptr(hits), _ptr(arms), C.byref(ms)))
+            return ms.value
+
+        ms_all += call(0, None, None)
+        nnz = int(indptr[-1])
+        col, val = np.empty(nnz, dtype=np.int32), np.empty(nnz, dtype=np.int32)
+        if nnz:
+            ms_all += call(nnz, col, val)
+        res = (indptr, col, val)
+        if with_hits:
+            res += (hits,)
+        if with_arm_rows:
+            res += (arms,)
+        return res + (ms_all,) if with_kernel_ms else res
 
     def sparse_lsi(self, indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter, q0, scale=1e4, transform="log", binarize=False,
                    with_kernel_ms=False):

@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | coaccess | peaks | motifs` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | coaccess | genescores | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -17,7 +17,7 @@ two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windo
 the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
 `cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
 k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
-`cluster` -> `deviations` / `markers` / `coaccess` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
+`cluster` -> `deviations` / `markers` / `coaccess` / `genescores` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
 sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
 the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  `deviations`, this package's
 own too, joins that matrix with the `cellcounts` matrix: per-cell motif accessibility deviations and z-scores against background window
@@ -28,7 +28,10 @@ the ranking done on the GPU in exact integers, with Benjamini-Hochberg q-values,
 commands above take through --bed.  `coaccess`, this package's own too, answers which windows open and close together: the Pearson
 correlation over the cells (or, with --aggregate, over the clusters of that table as metacells) of every two windows of a chromosome
 within --max_distance of each other, the sparse row intersections done on the GPU in exact integers, with a t-test, Benjamini-Hochberg
-q-values and a BEDPE file of links.  The other pyatac tools (vplot, bias_vplot) are not part of
+q-values and a BEDPE file of links.  `genescores`, this package's own as well, is the bridge from windows to genes: per gene and cell
+the sum over the cell's insertions around the gene of an integer weight that falls with the distance to the gene body, the window capped
+at the neighbouring genes, summed on the GPU in exact integers and written in the `cellcounts` layout, so that `markers --counts
+BASE.genescores.npz` names the genes that distinguish a cluster.  The other pyatac tools (vplot, bias_vplot) are not part of
 this package."""
 import argparse
 import sys
@@ -237,6 +240,34 @@ def add_coaccess_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output. Default is the count matrix's name without .cellcounts and its suffix")
 
 
+def add_genescores_parser(sub):
+    p = sub.add_parser("genescores", help="gene activity per cell: insertions around every gene weighted by distance to the gene body")
+    p.add_argument("--fragments", metavar="fragment_file", required=True, help="Fragment file with the cell barcode in its fourth column")
+    p.add_argument("--cells", metavar="table", required=True,
+                   help="TAB-separated table whose first column lists the barcodes: the columns of the matrix, in order of first appearance "
+                        "(the table `cellcounts --cells` takes)")
+    p.add_argument("--header", action="store_true", default=False, help="The table's first line is a header")
+    p.add_argument("--genes", metavar="bed_file", required=True,
+                   help="TAB-separated BED of genes: chrom, start, end, a name and a strand: the rows of the matrix, in file order")
+    p.add_argument("--name", metavar="int", default=4, type=int, help="Column of the gene name, 1-based. Default is 4")
+    p.add_argument("--strand", metavar="int", default=6, type=int, help="Column of the strand (`-` is minus, anything else plus). Default is 6")
+    p.add_argument("--upstream", metavar="int", default=5000, type=int,
+                   help="The gene body is extended this far upstream of the gene's start. Default is 5000")
+    p.add_argument("--min_extend", metavar="int", default=1000, type=int,
+                   help="The window reaches at least this far beyond the extended body. Default is 1000")
+    p.add_argument("--max_extend", metavar="int", default=100000, type=int,
+                   help="The window reaches at most this far beyond the extended body. Default is 100000")
+    p.add_argument("--decay", metavar="int", default=5000, type=int, help="Distance over which the weight falls by e. Default is 5000")
+    p.add_argument("--no_boundaries", action="store_true", default=False, help="Neighbouring genes do not stop a gene's window")
+    p.add_argument("--unit", metavar="int", default=256, type=int,
+                   help="The integer a weight of 1 is written as, 4 to 65536; lower it if a sum could pass 2^31. Default is 256")
+    p.add_argument("--lower", metavar="int", default=0, type=int, help="lower limit on insert size. Default is 0")
+    p.add_argument("--upper", metavar="int", default=1000, type=int, help="upper limit on insert size. Default is 1000")
+    p.add_argument("--format", choices=("npz", "mtx"), default="npz",
+                   help="BASE.genescores.npz (default; carries the gene names) or BASE.genescores.mtx.gz with .barcodes.tsv and .regions.bed")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the gene file's name without its last extension")
+
+
 def add_peaks_parser(sub):
     p = sub.add_parser("peaks", help="call enriched regions (peaks) from the insertions of a fragment store")
     p.add_argument("--bam", metavar="bam_file", required=True, help="Aligned reads (BAM, fragment file or FragmentStore .npz)")
@@ -334,6 +365,7 @@ def pyatac_parser():
     add_deviations_parser(sub)
     add_markers_parser(sub)
     add_coaccess_parser(sub)
+    add_genescores_parser(sub)
     add_peaks_parser(sub)
     add_motifs_parser(sub)
     return parser
@@ -482,6 +514,16 @@ def pyatac_main(args):
             get_coaccess(args)
         except (CoaccessError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac coaccess: %s\n" % e)
+            return 1
+    elif args.call == "genescores":
+        from .._lib import NatacError
+        from .cellgroups import CellGroupError
+        from .get_genescores import GenescoresError, get_genescores
+        print("---------Getting gene activity scores per cell-------------------------------------")
+        try:
+            get_genescores(args)
+        except (GenescoresError, CellGroupError, NatacError) as e:
+            sys.stderr.write("pyatac genescores: %s\n" % e)
             return 1
     elif args.call == "peaks":
         from .._lib import NatacError

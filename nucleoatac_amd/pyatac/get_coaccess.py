@@ -29,7 +29,7 @@ p = 2 * scipy.stats.t.sf(|t|, N - 2), and 0 where |r| == 1;  q is Benjamini-Hoch
 (get_markers.benjamini_hochberg).  A link has r >= --min_cor (in [-1, 1]) and q <= --fdr (in (0, 1]).
 
 Not done here: kNN metacells picked by the command itself, a depth or GC covariate, graphical-lasso regularisation as in Cicero, a
-cross-chromosome background, a peak-to-gene step (the package has no gene model or expression input).
+cross-chromosome background, a peak-to-gene step (`genescores` has the genes, but the package has no expression input).
 
 Files.  BASE.coaccess.npz (fixed timestamps: both forms of the matrix give the same bytes): region_chrom / _start / _end, tested, detected,
 s1, s2, n_cells, pair_a and pair_b (window indices in file order, the owner first), sxy, both, r, p, q.  BASE.coaccess.bedpe: the links

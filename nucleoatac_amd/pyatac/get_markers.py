@@ -39,7 +39,9 @@ _end, tested, the [windows x groups] arrays detected, total, rank2, z, p, q, log
 index.  BASE.markers.<group>.bed, one per group: that group's markers in that order, cut at --top when given, `chrom start end name
 score` with name <group>_marker_<i> and score min(1000, int(-10 log10 q)) -- `motifs --bed`, `counts --bed`, `cellcounts --bed` and
 `run --bed` take it unchanged; a group without markers gets an empty file.  BASE.markers.txt: cells listed / kept / dropped, windows,
-tested windows, and per group its cells, tested windows and markers.
+tested windows, and per group its cells, tested windows and markers.  When the --counts .npz holds region_name (`pyatac genescores` writes
+it: the rows are genes) that array is written into BASE.markers.npz and the table gets a last column `name`; every other input gives the
+files as they always were.
 
 Measured on the MI355X box (tools/bench_markers.py, one box, one process, three runs after a warm-up: 10,000 cells x 100,000 windows,
 8.07 M entries, 1,000 of the windows open in every second cell): the device call 7.5 to 36 ms with 8 groups and 45 to 69 ms with 64 (the
@@ -166,17 +168,19 @@ def rank_sum_markers(indptr, indices, data, barcodes, groups, min_cells=10, fdr=
     return st
 
 
-def output_texts(res, names, chrom, start, end, n_listed, n_all, top=None):
-    """(markers.tsv, [one BED text per group], summary) as text"""
-    rows = ["group\tchrom\tstart\tend\tlog2fc\tauc\tpct_in\tpct_rest\tz\tp\tq\n"]
+def output_texts(res, names, chrom, start, end, n_listed, n_all, top=None, region_name=None):
+    """(markers.tsv, [one BED text per group], summary) as text.  region_name (one per window, or None): a last column `name` of the
+    table"""
+    named = region_name is not None
+    rows = ["group\tchrom\tstart\tend\tlog2fc\tauc\tpct_in\tpct_rest\tz\tp\tq%s\n" % ("\tname" if named else "")]
     beds = []
     for g, name in enumerate(names):
         bed = []
         for i, w in enumerate(res["markers"][g].tolist(), 1):
             q = res["q"][w, g]
-            rows.append("%s\t%s\t%d\t%d\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%.3e\t%.3e\n"
+            rows.append("%s\t%s\t%d\t%d\t%.4f\t%.4f\t%.4f\t%.4f\t%.4f\t%.3e\t%.3e%s\n"
                         % (name, chrom[w], start[w], end[w], res["log2fc"][w, g], res["auc"][w, g], res["pct_in"][w, g], res["pct_rest"][w, g],
-                           res["z"][w, g], res["p"][w, g], q))
+                           res["z"][w, g], res["p"][w, g], q, "\t%s" % region_name[w] if named else ""))
             if top is None or i <= top:
                 score = 1000 if q <= 1e-100 else min(1000, int(-10.0 * np.log10(q)))
                 bed.append("%s\t%d\t%d\t%s_marker_%d\t%d\n" % (chrom[w], start[w], end[w], name, i, score))
@@ -188,6 +192,19 @@ def output_texts(res, names, chrom, start, end, n_listed, n_all, top=None):
     for g, name in enumerate(names):
         summary += "%s\t%d\t%d\t%d\n" % (name, res["n_in_group"][g], int(np.isfinite(res["p"][:, g]).sum()), len(res["markers"][g]))
     return "".join(rows), beds, summary
+
+
+def read_region_names(path, n_rows):
+    """the region_name array of a count matrix .npz (`pyatac genescores` writes one) as a list of str, or None where the file has none"""
+    if not path.endswith(".npz"):
+        return None
+    with np.load(path, allow_pickle=False) as z:
+        if "region_name" not in z.files:
+            return None
+        names = [n.decode("latin-1") if isinstance(n, bytes) else str(n) for n in z["region_name"].tolist()]
+    if len(names) != n_rows:
+        raise MarkersError("%s: %d region names for %d rows" % (path, len(names), n_rows))
+    return names
 
 
 def get_markers(args, rank=None):
@@ -207,15 +224,17 @@ def get_markers(args, rank=None):
         raise MarkersError(str(e))
     if len(start) != len(indptr) - 1:
         raise MarkersError("%s: %d regions for %d rows" % (args.counts, len(start), len(indptr) - 1))
+    region_name = read_region_names(args.counts, len(start))
     groups = read_groups(args.groups, header=args.header)
     res = rank_sum_markers(indptr, indices, data, barcodes, groups, args.min_cells, args.fdr, args.min_log2fc, rank=rank)
-    table, beds, summary = output_texts(res, groups.names, chrom, start, end, len(groups.barcodes), len(barcodes), args.top)
+    table, beds, summary = output_texts(res, groups.names, chrom, start, end, len(groups.barcodes), len(barcodes), args.top, region_name=region_name)
+    extra = {} if region_name is None else dict(region_name=np.array(region_name, dtype="U"))
     base = (args.out if args.out else default_base(args.counts)) + ".markers"
     paths = [base + ".npz", base + ".tsv", base + ".txt"] + [base + ".%s.bed" % name for name in groups.names]
     _savez_fixed(paths[0], groups=np.array([n.encode("latin-1") for n in groups.names], dtype="S"), n_cells=res["n_in_group"],
                  region_chrom=np.array(chrom), region_start=start, region_end=end, tested=res["tested"], detected=res["detected"],
                  total=res["total"], rank2=res["rank2"], z=res["z"], p=res["p"], q=res["q"], log2fc=res["log2fc"], auc=res["auc"],
-                 ties=res["ties"])
+                 ties=res["ties"], **extra)
     for path, text in zip(paths[1:], [table, summary] + beds):
         with open(path, "w") as f:
             f.write(text)
