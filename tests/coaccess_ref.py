@@ -2,7 +2,7 @@
 the MatrixMarket writer of `cellcounts` is used, for the command's input files): the pair lists by a plain double loop (pair_lists), the
 two integer arrays of natac_window_pair_sums in Python integers (pair_sums) and from scipy.sparse int64 products restricted to the pairs
 (pair_sums_sparse), r by the stated operation order one pair at a time (r_of) and in 50-digit decimal from the exact integers
-(r_decimal), the cases of the device tests (make_case) and the command's inputs (write_counts, command_case).  include/natac.h states the
+(r_decimal), the cases of the device tests (make_case; stride_case for a second trip of the grid) and the command's inputs (write_counts, command_case).  include/natac.h states the
 rule."""
 import math
 from decimal import Decimal, getcontext
@@ -107,14 +107,15 @@ def p_of(r, N):
     return 2.0 * float(student.sf(abs(t), N - 2))
 
 
-def make_case(seed, m, N, mean_len, partners=10, max_count=5, long_rows=()):
+def make_case(seed, m, N, mean_len, partners=10, max_count=5, long_rows=(), alone_every=0):
     """a CSR matrix of m windows x N cells with its `order` and `hi`, for the device tests.  Planted rows: 0 empty; 1 one entry; 2 every
     cell; 3 and 4 identical (r == 1); 5 and 6 with disjoint columns; long_rows[j] entries in row 7 + j.  The other rows have about
     mean_len entries (between 0 and min(N, 2 mean_len)) with counts 1 .. max_count.  order: two "chromosomes", so no pair crosses -- rows
     0, 2, 5, 6 and then the other even rows shuffled; rows 3, 4, 3 (one window listed twice), 1, the long rows and then the other odd
     rows shuffled.  Every owner reaches partners // 2 to 2 x partners windows ahead (fewer at its chromosome's end: the last owner has
     none), and one owner in the middle of each chromosome has none (hi[i] == i + 1); the planted rows open their chromosomes, so each is
-    an owner with partners.  Returns dict(indptr, indices, data, N, order, hi)."""
+    an owner with partners.  alone_every = e > 0: every e-th owner of a chromosome (i % e == e - 1) has none either.  Returns
+    dict(indptr, indices, data, N, order, hi)."""
     rng = np.random.default_rng(seed)
     some = lambda k: np.sort(rng.choice(N, k, replace=False))       # noqa: E731
     rows = [(np.zeros(0, np.int64), [])]
@@ -145,10 +146,31 @@ def make_case(seed, m, N, mean_len, partners=10, max_count=5, long_rows=()):
         base, n = len(order), len(mine)
         alone = n // 2
         for i in range(n):
-            reach = 0 if i == alone else int(rng.integers(max(1, partners // 2), 2 * partners + 1))
+            reach = 0 if i == alone or (alone_every and i % alone_every == alone_every - 1) else int(rng.integers(max(1, partners // 2), 2 * partners + 1))
             hi.append(base + min(n, i + 1 + reach))
         order += mine
     return dict(indptr=indptr, indices=indices, data=data, N=N, order=np.array(order, np.int32), hi=np.array(hi, np.int64))
+
+
+STRIDE_PLANTS = ((2, 0), (2, 1), (1, 2), (5, 3), (3, 5), (2, 6))        # (row of owner i, row of owner i + grid): see stride_case
+
+
+def stride_case(seed, grid):
+    """make_case(seed, m, 64, 8, partners=3, alone_every=7) with m = max(3000, 7 / 6 (grid + 600)) windows, so that six owners of seven
+    have partners and those exceed the grid by 500, for a launch of `grid` workgroups, where owner i + grid follows owner i in one
+    workgroup: at six places with partners on both sides, i and i + grid are given the rows of STRIDE_PLANTS -- every cell (row 2, 64
+    entries) followed by the empty row, by the row of one entry and by a row of 32; one entry followed by every cell; 32 entries
+    followed by about 21 and the reverse.  Returns (case, [(i, row of i, row of i + grid)])."""
+    case = make_case(seed, max(3000, (grid + 600) * 7 // 6), 64, 8, partners=3, alone_every=7)
+    order, hi = case["order"].copy(), case["hi"]
+    k = len(order)
+    has = hi - np.arange(k) > 1
+    free = [i for i in range(16, k - grid) if has[i] and has[i + grid]]
+    planted = []
+    for (first, second), i in zip(STRIDE_PLANTS, free[::len(free) // len(STRIDE_PLANTS)]):
+        order[i], order[i + grid] = first, second
+        planted.append((i, first, second))
+    return dict(case, order=order), planted
 
 
 # ---- the command's inputs ----------------------------------------------------------------------------------------------------------------

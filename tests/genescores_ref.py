@@ -1,6 +1,6 @@
 """NumPy restatement of `pyatac genescores` (include/natac.h states the rule), written from the header and shared by the host and the
 GPU tests: both insertion arrays with their cells, per gene two boolean masks and numpy.bincount(cell, weights), the window rule and the
-weight table, and make_case, the crafted chromosome the GPU tests run on."""
+weight table, make_case, the crafted chromosome the GPU tests run on, and what the stride tests ask of a case (window_hits, tile_pairs)."""
 import numpy as np
 
 SHORT_MAX = 64          # NATAC_GENESCORES_SHORT_CAP
@@ -127,6 +127,22 @@ def make_case(seed, n_frags=6000, n_cells=100, n_genes=120, lower=0, upper=1000)
     weight = weight_table(REACH, 1500, 64)
     return dict(pos=pos, tlen=tlen, cell=cell, n_cells=n_cells, win_lo=g[:, 0].copy(), body_lo=g[:, 1].copy(), body_hi=g[:, 2].copy(),
                 win_hi=g[:, 3].copy(), weight=weight, lower=lower, upper=upper, special=special)
+
+
+def window_hits(case):
+    """hits per gene of a make_case by two binary searches in the sorted insertions: gene_cell_scores' hits without its rows"""
+    x, _ = insertions(case["pos"], case["tlen"], case["cell"], case["lower"], case["upper"])
+    x = np.sort(x)
+    return (np.searchsorted(x, case["win_hi"], "left") - np.searchsorted(x, case["win_lo"], "left")).astype(np.int64)
+
+
+def tile_pairs(indptr, indices, rows, tile, n_tiles):
+    """int64[len(rows) * n_tiles]: the entries of row rows[r] whose cell lies in tile t, at r * n_tiles + t -- the table arm's items in
+    the order its workgroups take them"""
+    out = np.zeros(len(rows) * n_tiles, np.int64)
+    for r, g in enumerate(rows):
+        out[r * n_tiles:(r + 1) * n_tiles] = np.bincount(indices[indptr[g]:indptr[g + 1]] // tile, minlength=n_tiles)
+    return out
 
 
 def planted_world(seed=7, n_groups=3, per_group=30, n_genes=30, background=300, extra=15):

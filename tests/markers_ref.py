@@ -1,7 +1,8 @@
 """The restatement of `pyatac markers` the tests compare with (NumPy / scipy / exact rationals on the CPU; of the package only the
 MatrixMarket writer of `cellcounts` is used, for the command's input files):
 the four integer arrays of natac_group_rank_sums by exact midranks (rank_sums), the host statistics one window and group at a time
-(statistics), Benjamini-Hochberg (bh), the cases of the device tests (make_case) and the command's inputs (write_counts, planted_case).
+(statistics), Benjamini-Hochberg (bh), the cases of the device tests (make_case; short_stride_case, block_stride_case, border_case and big_case for
+the launch edges) and the command's inputs (write_counts, planted_case).
 include/natac.h states the rule."""
 import math
 from fractions import Fraction
@@ -148,6 +149,103 @@ def make_case(seed, N, G, m=300, all_in_one=False):
     indices = np.array([c for r in rows for c in r[0]], np.int32)
     data = np.array([a for r in rows for a in r[1]], np.int32)
     return dict(indptr=indptr, indices=indices, data=data, depth=depth, group=group, N=N, G=G)
+
+
+# ---- the cases of tests/test_gpu_markers_launch_edges.py (sized on the CPU by tests/test_markers_host.py) -----------------------------------
+def case_of_rows(rows, depth, group, G):
+    """make_case's dict from rows of (cells ascending, counts)"""
+    indptr = np.zeros(len(rows) + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r[0]) for r in rows])
+    indices = np.concatenate([np.asarray(r[0], np.int64) for r in rows]).astype(np.int32)
+    data = np.concatenate([np.asarray(r[1], np.int64) for r in rows]).astype(np.int32)
+    return dict(indptr=indptr, indices=indices, data=data, depth=np.asarray(depth, np.int64), group=np.asarray(group, np.int32), N=len(depth), G=G)
+
+
+def _case_of_lengths(rng, L, N, G):
+    """a case whose row p has L[p] cells drawn without replacement, counts 1 .. 5 over depths 1 .. 39 (many tied values), every group drawn
+    evenly"""
+    L = np.asarray(L, np.int64)
+    first = np.argsort(rng.random((len(L), N)), axis=1)                 # a permutation of the cells per row: its first L[p] are the row's
+    member = np.zeros((len(L), N), bool)
+    np.put_along_axis(member, first, np.arange(N)[None, :] < L[:, None], axis=1)
+    indptr = np.zeros(len(L) + 1, np.int64)
+    np.cumsum(L, out=indptr[1:])
+    indices = np.nonzero(member)[1].astype(np.int32)                    # row-major: ascending within a row
+    return dict(indptr=indptr, indices=indices, data=rng.integers(1, 6, len(indices)).astype(np.int32),
+                depth=rng.integers(1, 40, N).astype(np.int64), group=rng.integers(0, G, N).astype(np.int32), N=N, G=G)
+
+
+def short_stride_case(seed, n_rows, per_trip, N=48, G=5, top=8, lead=None):
+    """n_rows rows of 0 .. top entries for the short arm, whose workgroups take per_trip rows a trip (rows a workgroup x grid): row
+    per_trip + j follows row j in one lane group.  Two of three such pairs are a full row (top entries) followed by an empty row and by
+    a row of one entry, so that what the first leaves in the counters would be counted.  lead: the entries of row 0 (it sets the lanes)."""
+    rng = np.random.default_rng(seed)
+    L = rng.integers(0, top + 1, n_rows)
+    j = np.arange(max(0, n_rows - per_trip))
+    L[j[j % 3 != 2]] = top
+    L[per_trip + j[j % 3 == 0]] = 0
+    L[per_trip + j[j % 3 == 1]] = 1
+    if lead is not None:
+        L[0] = lead
+    return _case_of_lengths(rng, L, N, G)
+
+
+def block_stride_case(seed, n_block, grid, short_max=4, N=48, G=5):
+    """n_block rows of short_max + 1 .. 40 entries for the block arm under NATAC_MARKERS_SHORT_MAX = short_max, launched with `grid`
+    workgroups: block row grid + j follows block row j in one workgroup.  Two of three such pairs are a row of 40 entries followed by one
+    of short_max + 1 and of short_max + 2.  After every fourth block row stands a row of 0 .. short_max entries (the short arm's).
+    Returns (case, the index of every block row)."""
+    rng = np.random.default_rng(seed)
+    Lb = rng.integers(short_max + 1, 41, n_block)
+    j = np.arange(max(0, n_block - grid))
+    Lb[j[j % 3 != 2]] = 40
+    Lb[grid + j[j % 3 == 0]] = short_max + 1
+    Lb[grid + j[j % 3 == 1]] = short_max + 2
+    L, where = [], []
+    for b in range(n_block):
+        where.append(len(L))
+        L.append(int(Lb[b]))
+        if b % 4 == 3:
+            L.append((b // 4) % (short_max + 1))
+    return _case_of_lengths(rng, L, N, G), np.array(where)
+
+
+BORDER_ROWS = (0, 1, 64, 65, 4096, 4097, 8192, 8193, 9000)             # entries of the first rows of border_case: every arm's borders
+
+
+def border_case(seed, G, N=9000):
+    """rows of BORDER_ROWS entries with counts 1 .. 5 over depths 1 .. 39; row 9: 8500 entries whose values are all 1 through (d, d);
+    row 10: 8700 entries that hold the pair COLLIDING in cells 0 and 1.  Groups as make_case draws them."""
+    rng = np.random.default_rng(seed)
+    group = np.zeros(N, np.int32) if G == 1 else rng.integers(0, G - 1 if G > 2 else G, N).astype(np.int32)
+    depth = rng.integers(1, 40, N).astype(np.int64)
+    depth[0], depth[1] = COLLIDING[0][1], COLLIDING[1][1]
+    some = lambda k: np.sort(rng.choice(N, k, replace=False))       # noqa: E731
+    rows = []
+    for k in BORDER_ROWS:
+        rows.append((some(k), rng.integers(1, 6, k)))
+    cells = some(8500)
+    rows.append((cells, depth[cells]))
+    cells = np.union1d([0, 1], 2 + np.sort(rng.choice(N - 2, 8698, replace=False)))
+    counts = rng.integers(1, 6, len(cells))
+    counts[0], counts[1] = COLLIDING[0][0], COLLIDING[1][0]
+    rows.append((cells, counts))
+    return case_of_rows(rows, depth, group, G)
+
+
+def big_case(seed, N=1 << 20, G=3):
+    """N cells: row 0 empty; 1 the last cell only; 2 the first cell only; 3 10,000 entries (the long arm); 4 5,000 entries (the block
+    arm); 5 40 entries"""
+    rng = np.random.default_rng(seed)
+    group = rng.integers(0, G, N).astype(np.int32)
+    depth = rng.integers(1, 40, N).astype(np.int64)
+    rows = [(np.zeros(0, np.int64), np.zeros(0, np.int64)), (np.array([N - 1]), np.array([3])), (np.array([0]), np.array([2]))]
+    for k in (10000, 5000, 40):
+        cells = np.sort(rng.choice(N, k, replace=False))
+        if k == 10000:
+            cells[-1] = N - 1                                           # the long row reaches the last cell
+        rows.append((cells, rng.integers(1, 6, k)))
+    return case_of_rows(rows, depth, group, G)
 
 
 # ---- the command's inputs ----------------------------------------------------------------------------------------------------------------

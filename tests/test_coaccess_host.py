@@ -319,3 +319,48 @@ def test_plan_pins_the_arms_and_the_forced_values(monkeypatch):
             plan(*bad)
     with pytest.raises(L.NatacError):
         plan(10, 100, 10, 5, 2, n_cu=0)
+
+
+# ---- the cases of tests/test_gpu_coaccess_launch_edges.py: sized for the grid before they reach a GPU -----------------------------------------
+def _plan_of(case, n_cu):
+    from nucleoatac_amd.device import window_pair_sums_plan as plan
+    L = np.diff(case["indptr"])
+    return plan(len(L), case["N"], int(L.sum()), len(case["order"]), int(L[case["order"]].sum()), n_cu=n_cu)
+
+
+@pytest.mark.parametrize("n_cu", [256, 304])
+def test_stride_case_exceeds_the_grid_in_both_arms(n_cu, monkeypatch):
+    from nucleoatac_amd.device import window_pair_sums_plan as plan
+    monkeypatch.delenv("NATAC_COACCESS_TABLE_MAX", raising=False)
+    monkeypatch.delenv("NATAC_COACCESS_CHUNK", raising=False)
+    grid = plan(1 << 20, 64, 8 << 20, 1 << 20, 8 << 20, n_cu=n_cu)["grid"]
+    assert grid == 8 * n_cu
+    case, planted = R.stride_case(17, grid)
+    k, L = len(case["order"]), np.diff(case["indptr"])
+    has = case["hi"] - np.arange(k) > 1
+    p = _plan_of(case, n_cu)
+    assert p == dict(arm="table", table_max=16384, lanes=16, chunk=8192, wg=256, lds_bytes=256, grid=grid)
+    assert has.sum() > p["grid"] + 500 and (has[grid:] & has[:k - grid]).sum() > 500 and (~has[grid:]).sum() >= 100 and (~has[:grid]).sum() >= 100
+    assert [(a, b) for _, a, b in planted] == list(R.STRIDE_PLANTS) and L[[0, 1, 2, 5, 6]].tolist() == [0, 1, 64, 32, 32] and 16 < L[3] < 32
+    for i, a, b in planted:
+        assert case["order"][i] == a and case["order"][i + grid] == b and has[i] and has[i + grid] and i + grid < k
+    assert (case["hi"] > np.arange(k)).all() and case["hi"].max() <= k and case["order"].min() >= 0 and case["order"].max() < len(L)
+    monkeypatch.setenv("NATAC_COACCESS_TABLE_MAX", "1")
+    assert _plan_of(case, n_cu) == dict(arm="search", table_max=1, lanes=16, chunk=8192, wg=256, lds_bytes=65536, grid=grid)
+    monkeypatch.setenv("NATAC_COACCESS_CHUNK", "16")
+    assert _plan_of(case, n_cu) == dict(arm="search", table_max=1, lanes=16, chunk=16, wg=256, lds_bytes=128, grid=grid)
+    own = L[case["order"]] * has
+    assert (own[:grid] > 16).sum() >= 5 and (own[grid:] > 16).sum() >= 3           # owners of more than one chunk on either trip
+
+
+@pytest.mark.parametrize("n_cu", [256, 304])
+def test_table_size_cases_plan_their_arms(n_cu, monkeypatch):
+    monkeypatch.delenv("NATAC_COACCESS_TABLE_MAX", raising=False)
+    monkeypatch.delenv("NATAC_COACCESS_CHUNK", raising=False)
+    for n, arm, lds in ((16384, "table", 65536), (16385, "search", 65536), (5000, "table", 20000)):
+        case = R.make_case(n, 40, n, 3000, partners=6)
+        p = _plan_of(case, n_cu)
+        assert p == dict(arm=arm, table_max=16384, lanes=64, chunk=8192, wg=256, lds_bytes=lds, grid=len(case["order"])) and p["grid"] == 41
+        L, ip, ix = np.diff(case["indptr"]), case["indptr"], case["indices"]
+        last = [w for w in range(40) if L[w] and ix[ip[w + 1] - 1] == n - 1]
+        assert L[2] == n and 2 in last and len(last) >= 3 and set(last) <= set(case["order"].tolist()) and L[7:].max() > 4096

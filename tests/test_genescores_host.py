@@ -295,6 +295,50 @@ def test_plan_pins_the_arms_and_the_forced_values(monkeypatch):
         plan(10, 100, 5, n_cu=0)
 
 
+# ---- the cases of tests/test_gpu_genescores_launch_edges.py: sized for the grid before they reach a GPU ---------------------------------------
+@pytest.mark.parametrize("n_cu", [256, 304])
+def test_table_stride_case_exceeds_the_grid(n_cu, monkeypatch):
+    from nucleoatac_amd.device import gene_cell_scores_plan as plan
+    monkeypatch.setenv("NATAC_GENESCORES_SHORT_MAX", "1")
+    monkeypatch.setenv("NATAC_GENESCORES_TILE", "16")
+    most = plan(1 << 20, 200, 1 << 20, n_cu=n_cu)
+    assert (most["tile"], most["n_tiles"], most["grid"]) == (16, 13, 8 * n_cu)
+    n_genes = max(400, (most["grid"] + 500) // 13 + 60)
+    case = R.make_case(seed=200, n_frags=6000, n_cells=200, n_genes=n_genes)
+    ptr, col, val, hits = R.gene_cell_scores(*R.case_args(case), with_hits=True)
+    assert np.array_equal(hits, R.window_hits(case))
+    rows = np.flatnonzero(hits > 1)
+    p = plan(n_genes, 200, len(rows), n_cu=n_cu)
+    assert p == dict(short_max=1, tile=16, n_tiles=13, wg=256, lds_bytes=64, grid=8 * n_cu) and len(rows) * p["n_tiles"] > p["grid"] + 500
+    pairs = R.tile_pairs(ptr, col, rows, 16, 13)
+    assert pairs.sum() == sum(ptr[g + 1] - ptr[g] for g in rows) and pairs.max() == 16
+    a, b = pairs[:len(pairs) - p["grid"]], pairs[p["grid"]:]            # the items a workgroup serves one after the other
+    assert ((a >= 8) & (b == 0)).sum() >= 40 and ((a == 0) & (b >= 8)).sum() >= 30 and ((a > 0) & (b > 0) & (a != b)).sum() >= 500
+    assert (hits == 1).sum() >= 1
+    monkeypatch.setenv("NATAC_GENESCORES_TILE", "64")
+    assert plan(n_genes, 200, len(rows), n_cu=n_cu)["n_tiles"] == 4
+    monkeypatch.delenv("NATAC_GENESCORES_TILE")
+    assert (plan(n_genes, 200, len(rows), n_cu=n_cu)["tile"], plan(n_genes, 200, len(rows), n_cu=n_cu)["n_tiles"]) == (256, 1)
+
+
+def test_wave_stride_case_gives_waves_a_second_row(monkeypatch):
+    """the wave kernels' grid does not follow the CU count: min(ceil(n_genes / 4), 16384) workgroups of 4 waves"""
+    from nucleoatac_amd.device import gene_cell_scores_plan as plan
+    waves = 4 * 16384
+    case = R.make_case(seed=50, n_frags=1500, n_cells=50, n_genes=66000)
+    hits = R.window_hits(case)
+    assert len(hits) > waves + 400
+    a, b = hits[:len(hits) - waves], hits[waves:]
+    both = (a >= 1) & (a <= 64) & (b >= 1) & (b <= 64)
+    assert both.sum() >= 100 and (both & (a != b)).sum() >= 50 and (b == 0).sum() >= 5 and (b > 64).sum() >= 5 and ((b == 1) & (a > 1)).sum() >= 3
+    assert ((hits > 0) & (hits <= 64)).sum() >= 1000 and (hits == 1).sum() >= 1000
+    monkeypatch.setenv("NATAC_GENESCORES_SHORT_MAX", "1")
+    monkeypatch.delenv("NATAC_GENESCORES_TILE", raising=False)
+    for n_cu in (256, 304):
+        p = plan(66000, 50, int((hits > 1).sum()), n_cu=n_cu)
+        assert (p["tile"], p["n_tiles"], p["grid"]) == (256, 1, 8 * n_cu) and (hits > 1).sum() > p["grid"] + 500
+
+
 # ---- gene names through `pyatac markers` ---------------------------------------------------------------------------------------------------
 def test_markers_carries_region_names(tmp_path):
     X, barcodes, grp = MR.planted_case(seed=5, n_groups=3, per_group=30, n_windows=90, planted=15)

@@ -301,3 +301,65 @@ def test_plan_pins_every_arm_and_the_forced_thresholds(monkeypatch):
             plan(*bad)
     with pytest.raises(L.NatacError):
         plan(10, 100, 10, 5, 2, n_cu=0)
+
+
+# ---- the cases of tests/test_gpu_markers_launch_edges.py: sized for the grid before they reach a GPU ------------------------------------------
+def _plan_of(case, n_cu):
+    from nucleoatac_amd.device import group_rank_sums_plan as plan
+    L = np.diff(case["indptr"])
+    return plan(len(L), case["N"], int(L.sum()), int(L.max()), case["G"], n_cu=n_cu)
+
+
+@pytest.mark.parametrize("n_cu", [256, 304])
+def test_stride_cases_exceed_the_grid(n_cu, monkeypatch):
+    from nucleoatac_amd.device import group_rank_sums_plan as plan
+    monkeypatch.delenv("NATAC_MARKERS_BLOCK_MAX", raising=False)
+    for short_max, lanes, lead in ((None, 64, 40), (16, 16, None)):
+        if short_max is None:
+            monkeypatch.delenv("NATAC_MARKERS_SHORT_MAX", raising=False)
+        else:
+            monkeypatch.setenv("NATAC_MARKERS_SHORT_MAX", str(short_max))
+        most = plan(1 << 20, 48, (lead or 8) << 20, lead or 8, 5, n_cu=n_cu)
+        assert most["lanes"] == lanes and most["grid"]["short"] == 8 * n_cu
+        per_trip = (256 // lanes) * most["grid"]["short"]
+        case = R.short_stride_case(40 + lanes, per_trip + 501, per_trip, lead=lead)
+        L = np.diff(case["indptr"])
+        p = _plan_of(case, n_cu)
+        assert p["lanes"] == lanes and p["grid"]["short"] == 8 * n_cu and len(L) > (256 // lanes) * p["grid"]["short"] + 500
+        assert L.max() == (lead or 8) <= p["short_max"] and p["lds_bytes"]["block"] == 0               # every row is the short arm's
+        second = np.arange(per_trip, len(L))
+        assert (L[second - per_trip] == 8).sum() >= 300 and (L[second] == 0).sum() >= 150 and (L[second] == 1).sum() >= 150
+        assert all(np.all(np.diff(case["indices"][a:b]) > 0) for a, b in zip(case["indptr"][:400], case["indptr"][1:401]))
+    monkeypatch.setenv("NATAC_MARKERS_SHORT_MAX", "4")
+    grid = plan(1 << 20, 48, 40 << 20, 40, 5, n_cu=n_cu)["grid"]["block"]
+    case, where = R.block_stride_case(77, grid + 301, grid)
+    L = np.diff(case["indptr"])
+    p = _plan_of(case, n_cu)
+    assert grid == 8 * n_cu == p["grid"]["block"] and p["short_max"] == 4 and len(where) > p["grid"]["block"] + 300
+    assert (L[where] > 4).all() and L.max() == 40 and (L <= 4).sum() == len(L) - len(where) >= 500
+    assert p["lds_bytes"]["block"] == (5 * 20 + 15) // 16 * 16 + 16 + 64 * 9 and p["lds_bytes"]["long"] == 0
+    first, second = L[where[:len(where) - grid]], L[where[grid:]]
+    assert len(second) == 301 and (first == 40).sum() >= 200 and (second <= 6).sum() >= 200 and (first != second).sum() >= 250
+
+
+@pytest.mark.parametrize("n_cu", [256, 304])
+def test_default_threshold_cases_plan_the_block_arm_past_64_kib(n_cu, monkeypatch):
+    monkeypatch.delenv("NATAC_MARKERS_SHORT_MAX", raising=False)
+    ctr = lambda G: (G * 20 + 15) // 16 * 16                                # noqa: E731
+    for G in (1, 255):
+        case = R.border_case(900 + G, G)
+        L = np.diff(case["indptr"])
+        assert L.tolist() == [0, 1, 64, 65, 4096, 4097, 8192, 8193, 9000, 8500, 8700] and case["N"] == 9000 and case["group"].max() == max(0, G - 2)
+        monkeypatch.delenv("NATAC_MARKERS_BLOCK_MAX", raising=False)
+        p = _plan_of(case, n_cu)
+        assert (p["short_max"], p["block_max"], p["chunk"]) == (64, 8192, 4096)
+        assert p["lds_bytes"]["block"] == ctr(G) + 16 + 8192 * 9 > 65536 and p["lds_bytes"]["long"] == max(4096 * 8, ctr(G) + 16)
+        monkeypatch.setenv("NATAC_MARKERS_BLOCK_MAX", "4096")
+        p = _plan_of(case, n_cu)
+        assert (p["block_max"], p["chunk"]) == (4096, 4096) and p["lds_bytes"]["block"] == ctr(G) + 16 + 4096 * 9 < 65536
+    monkeypatch.delenv("NATAC_MARKERS_BLOCK_MAX", raising=False)
+    case = R.big_case(31)
+    L = np.diff(case["indptr"])
+    assert case["N"] == 1 << 20 and L.tolist() == [0, 1, 1, 10000, 5000, 40] and case["indices"][case["indptr"][4] - 1] == (1 << 20) - 1
+    p = _plan_of(case, n_cu)
+    assert p["lds_bytes"]["block"] == ctr(3) + 16 + 8192 * 9 > 65536 and p["lds_bytes"]["long"] == 4096 * 8 and p["grid"] == dict(short=2, block=6)
