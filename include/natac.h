@@ -57,8 +57,9 @@ extern "C" {
  * `pyatac motifs`; 19: added natac_motif_deviations and natac_window_base_counts for `pyatac deviations`; 20: added
  * natac_motif_deviations_plan; 21: added natac_group_rank_sums and natac_group_rank_sums_plan for `pyatac markers`; 22: added
  * natac_window_pair_sums and natac_window_pair_sums_plan for `pyatac coaccess`; 23: added natac_gene_cell_scores and
- * natac_gene_cell_scores_plan for `pyatac genescores`); the binding refuses another version */
-#define NATAC_ABI_VERSION 23
+ * natac_gene_cell_scores_plan for `pyatac genescores`; 24: added natac_knn and natac_knn_plan for `pyatac doublets`); the binding refuses
+ * another version */
+#define NATAC_ABI_VERSION 24
 
 enum {
     NATAC_OK = 0,
@@ -758,6 +759,68 @@ int natac_gene_cell_scores(natac_ctx *ctx, int64_t n_frags, const int64_t *pos, 
  * table_rows outside [0, n_genes], n_cu < 1. */
 int natac_gene_cell_scores_plan(int64_t n_genes, int32_t n_cells, int64_t table_rows, int32_t n_cu, int32_t *short_max, int32_t *tile,
                                 int32_t *n_tiles, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
+/* `pyatac doublets` (this package's own command: the reference has no such tool): a doublet score per cell of a `cellcounts` matrix, by
+ * the usual method -- simulate doublets by adding two cells' counts, put them into the LSI space of the real cells, and score every real
+ * cell by the share of simulated doublets among its nearest neighbours (Scrublet's likelihood, ArchR's removal rule).
+ * Space.  Everything up to V is `cluster`'s, with the same flags and checks: tfidf_weights, r = components + oversample <= 64, the same
+ * natac_sparse_lsi call.  g = numpy.random.default_rng(seed); q0 = g.standard_normal((windows, r)) is drawn first, so the LSI is bit for
+ * bit `cluster`'s for that seed.  N cells are kept (total > 0), N >= 2.
+ * Simulated doublets.  S = int(rint(ratio * N)), ratio in (0, 8], S >= 1.  a = g.integers(0, N, S), then b = g.integers(0, N, S), index
+ * the kept cells; a[i] == b[i] is allowed.  Doublet i has the counts x[a] + x[b] and the total total[a] + total[b]; with --binarize every
+ * window of the union counts 1.
+ * Projection (host, fp64).  Every column, real and simulated alike, goes through one function: the weighted entry is
+ * t = a' * (1 / total) * row_weight[w], or log1p(10000 t) with --method log, the row weights those of the real cells, and
+ * E = A V[:, :components] is one scipy.sparse CSR-times-dense product with sorted indices.  The real cells are projected this way too,
+ * not taken from U sigma.  depth_correlation of the real rows against their totals decides the components kept, as in `cluster`;
+ * P = unit_rows of the kept components has N + S rows, the real cells first, and d <= 64 columns.
+ * Neighbours.  k = --neighbors in [1, 1024] if given, else max(1, int(rint(0.5 sqrt(N)))); k_adj = int(rint(k (1 + S / N))) clipped to
+ * [1, min(1024, N + S - 1)] (the summary says when the cap of 1024 applied).  For every real cell: its k_adj nearest rows of P, itself
+ * excluded, by natac_knn's rule below.
+ * Score (host, fp64, in this order).  n_syn = the neighbours with index >= N; q = (n_syn + 1) / (k_adj + 2); rr = S / N;
+ * rho = --expected_rate in (0, 0.5]; score = q * rho / rr / (1 - rho - q * (1 - rho - rho / rr)).  The denominator is positive for q < 1.
+ * Flag.  --filter_ratio F and --max_score X exclude each other.  With --max_score a cell is flagged when score > X.  Otherwise, F in
+ * [0, 100] (default 1.0): n_remove = min(N - 1, int(F * N * N / 100000)) and the first n_remove cells by (score descending, index
+ * ascending) are flagged.  No knee or histogram threshold is searched for.
+ * Not done: approximate search, ArchR's down-sampling of the simulated counts, an automatic threshold, UMAP or graph clustering on the
+ * graph, writing V into `cluster`'s BASE.lsi.npz.
+ *
+ * natac_knn is the device part and a general exact k-nearest-neighbour search.  x[nr, dim] are the references and q[nq, dim] the queries,
+ * both row-major fp64.  d2(i, j) starts at acc = 0; for c = 0 .. dim - 1 in order t = q[i, c] - x[j, c], then acc = acc + t * t, each of
+ * the three operations rounded once, no contraction.  Reference j is excluded for query i when self_offset >= 0 and j == i + self_offset.
+ * Row i of idx[nq, k] and dist2[nq, k] holds the k smallest references by (d2, j) ascending; with fewer than k references available the
+ * tail is idx = -1, dist2 = +inf.  The rule is a sequence of IEEE operations and a total order: the result is exact.
+ * Limits: 1 <= dim <= NATAC_KNN_MAX_DIM, 1 <= k <= NATAC_KNN_MAX_K, 1 <= nr <= NATAC_KNN_MAX_REFS, nq >= 0, nq * k <= NATAC_KNN_MAX_OUT
+ * (Context.knn cuts the queries into blocks under it; the result does not depend on the cut), self_offset -1 or in [0, nr - nq], every
+ * value finite with |v| <= 2^NATAC_KNN_MAX_EXP, so that no sum can overflow (64 * 2^1002 < 2^1024).  All checks run on the host before any
+ * launch; a refusal is NATAC_E_ARG, names the array and the first bad index and leaves the outputs untouched.  nq == 0 returns NATAC_OK
+ * without a launch.  arm_queries[2] (may be NULL): the queries the wave and the lds arm took.  kernel_ms (may be NULL): the kernel's
+ * device time.
+ * Kernel (csrc/natac_knn.hpp).  A workgroup of 4 waves owns a tile of queries, a wave its share of them, and walks the references in tiles
+ * staged transposed and padded in LDS; a lane holds one reference and the accumulators of the wave's queries, whose coordinates are LDS
+ * broadcast reads.  Per query the k-th best so far is a threshold; candidates below it are appended to a buffer by ballot and prefix
+ * count, and a full buffer is reduced with the list to the k best by a bitonic sort on (bits of d2, j).  Wave arm, k <= wave_k_max (64
+ * unless forced): the list is one entry per lane in registers.  Lds arm, larger k: list and buffer are one LDS array of the power of two
+ * >= max(k + 64, 128) entries.  No scratch, no atomics: the same bytes from two calls and under every arm and tile.  The environment's
+ * NATAC_KNN_WAVE_K_MAX (1 .. 64), NATAC_KNN_QUERY_TILE (a power of two in 4 .. 32) and NATAC_KNN_REF_TILE (a power of two in 64 .. 256)
+ * force them, for the tests; a value outside its rule, or one whose LDS would pass NATAC_KNN_LDS_CAP, is ignored. */
+#define NATAC_KNN_MAX_DIM 64
+#define NATAC_KNN_MAX_K 1024
+#define NATAC_KNN_MAX_REFS 16777216
+#define NATAC_KNN_MAX_OUT 268435456
+#define NATAC_KNN_MAX_EXP 500
+#define NATAC_KNN_LDS_CAP 163840
+int natac_knn(natac_ctx *ctx, int64_t nq, int64_t nr, int32_t dim, const double *q, const double *x, int64_t self_offset, int32_t k,
+              int32_t *idx, double *dist2, int64_t *arm_queries, double *kernel_ms);
+/* How natac_knn launches for nq queries against nr references of dim columns with k neighbours on a device of n_cu compute units (host
+ * only: no context, no GPU needed; it reads the three NATAC_KNN_ variables as the call does).  *arm: 0 wave, 1 lds.  *wave_k_max: the
+ * largest k of the wave arm.  *query_tile: the queries of a workgroup, 4 times a wave's 1, 2, 4 or 8 -- unless forced, 8 a wave, halved
+ * while the query tiles are fewer than 4 n_cu (wave arm) or 8 n_cu (lds arm) or the workgroup takes more than 80 KiB of LDS.  *ref_tile: the references staged at a
+ * time -- unless forced, the largest of 256, 128, 64 whose copy stays within 24 KiB.  *capacity: the candidates a query's buffer holds,
+ * 64 (wave) or the array's entries minus k (lds).  *wg: the threads of a workgroup.  *lds_bytes: its dynamic LDS, at most
+ * NATAC_KNN_LDS_CAP.  *grid: min(ceil(nq / *query_tile), 8 n_cu), at least 1; the workgroups stride over the query tiles.  NATAC_E_ARG
+ * for the limits above and n_cu < 1. */
+int natac_knn_plan(int64_t nq, int64_t nr, int32_t dim, int32_t k, int32_t n_cu, int32_t *arm, int32_t *wave_k_max, int32_t *query_tile,
+                   int32_t *ref_tile, int32_t *capacity, int32_t *wg, int64_t *lds_bytes, int32_t *grid);
 /* _nucleotideHelper, pyatac/get_nucleotide.py:19-38, with chunk.center / chunk.slop (pyatac/chunk.py:26-54) and seq.get_sequence /
  * seq_to_mat (pyatac/seq.py:11-45), for the sites of one chromosome: seq[n] is the chromosome as the FASTA has it, case included;
  * center[i] in [0, n) the centred site, minus[i] != 0 a minus-strand site (minus == NULL: all plus).  word = 1 counts the rows

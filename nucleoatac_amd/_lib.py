@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 23    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
+ABI_VERSION = 24    # NATAC_ABI_VERSION of include/natac.h (tests/test_abi.py compares the two)
 LIB_PATH = os.environ.get("NATAC_LIB") or os.path.join(_HERE, "libnatac_hip.so")   # NATAC_LIB: A/B builds of the same ABI
 
 # enums of include/natac.h
@@ -28,6 +28,7 @@ MARKERS_SHORT_CAP, MARKERS_BLOCK_CAP = 64, 8192     # the most NATAC_MARKERS_SHO
 COACCESS_MAX_PAIRS, COACCESS_MAX_CELLS = 33554432, 1048576      # NATAC_COACCESS_*: natac_window_pair_sums' limits
 COACCESS_TABLE_CAP, COACCESS_CHUNK_CAP = 16384, 8192            # the most NATAC_COACCESS_TABLE_MAX / NATAC_COACCESS_CHUNK may force
 GENESCORES_SHORT_CAP, GENESCORES_TILE_CAP, GENESCORES_MAX_WEIGHT = 64, 16384, 1048576     # NATAC_GENESCORES_*: natac_gene_cell_scores' limits
+KNN_MAX_DIM, KNN_MAX_K, KNN_MAX_REFS, KNN_MAX_OUT, KNN_MAX_EXP, KNN_LDS_CAP = 64, 1024, 16777216, 268435456, 500, 163840   # NATAC_KNN_*: natac_knn's limits
 SPLIT_MAX_BARCODES = 8388608        # NATAC_SPLIT_MAX_BARCODES: the most cells a barcode table holds
 K_FRAG_GATHER, K_BACKGROUND, K_SMOOTH_NUC, K_OCC_MLE, K_OCC_SMOOTH, K_OCC_FILL, K_INS, K_CAND, K_SIZE_HIST = range(9)
 K_INS_SMOOTH, K_CENTER_COV, K_PWM_TRACK = 9, 10, 11
@@ -122,6 +123,8 @@ SIGNATURES = {
     "natac_gene_cell_scores": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, C.c_int, C.c_int, _vp, _i64, _vp, _vp,
                                          _vp, _vp, C.POINTER(_f64)]),
     "natac_gene_cell_scores_plan": (C.c_int, [_i64, _i32, _i64, _i32] + [C.POINTER(_i32)] * 4 + [C.POINTER(_i64), C.POINTER(_i32)]),
+    "natac_knn": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, C.POINTER(_f64)]),
+    "natac_knn_plan": (C.c_int, [_i64, _i64, _i32, _i32, _i32] + [C.POINTER(_i32)] * 6 + [C.POINTER(_i64), C.POINTER(_i32)]),
     "natac_site_seq_counts": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.POINTER(_i64),
                                         C.POINTER(_f64)]),
     "natac_site_signal": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.POINTER(_f64)]),

@@ -34,6 +34,7 @@
 #include "natac_markers.hpp"
 #include "natac_coaccess.hpp"
 #include "natac_genescores.hpp"
+#include "natac_knn.hpp"
 #include "natac_peaks.hpp"
 #include "natac_tracks.hpp"
 #include "natac_dropins.hpp"

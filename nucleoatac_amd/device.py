@@ -122,6 +122,17 @@ def gene_cell_scores_plan(n_genes, n_cells, table_rows, n_cu=256):
     return dict(short_max=v[0].value, tile=v[1].value, n_tiles=v[2].value, wg=v[3].value, lds_bytes=lds.value, grid=grid.value)
 
 
+def knn_plan(nq, nr, dim, k, n_cu=256):
+    """how knn launches for nq queries against nr references of dim columns with k neighbours on n_cu compute units (natac_knn_plan; needs
+    no GPU, reads NATAC_KNN_WAVE_K_MAX / NATAC_KNN_QUERY_TILE / NATAC_KNN_REF_TILE as the call does): dict of arm ("wave" / "lds"),
+    wave_k_max, query_tile, ref_tile, capacity, wg, lds_bytes and grid"""
+    v = [C.c_int32() for _ in range(6)]
+    lds, grid = C.c_int64(), C.c_int32()
+    L.check(L.load().natac_knn_plan(int(nq), int(nr), int(dim), int(k), int(n_cu), *([C.byref(x) for x in v] + [C.byref(lds), C.byref(grid)])))
+    return dict(arm=("wave", "lds")[v[0].value], wave_k_max=v[1].value, query_tile=v[2].value, ref_tile=v[3].value, capacity=v[4].value,
+                wg=v[5].value, lds_bytes=lds.value, grid=grid.value)
+
+
 class TrackStore(object):
     """device-resident copies of batch tracks as their .bedgraph file shows them (natac_store_*; see occstore.py)"""
 
@@ -502,6 +513,45 @@ class Context(object):
             res += (hits,)
         if with_arm_rows:
             res += (arms,)
+        return res + (ms_all,) if with_kernel_ms else res
+
+    def knn(self, points, k, queries=None, self_offset=None, max_out=None, with_arm_queries=False, with_kernel_ms=False):
+        """exact k nearest neighbours (natac_knn; include/natac.h states the rule): (idx int32[nq, k], dist2 float64[nq, k]), row i the k
+        smallest references by (d2, index) ascending, d2 the plain column-ordered sum of squared differences in fp64; where fewer than k
+        references are available the tail is -1 / +inf.  points float64[nr, dim] are the references.  queries=None: every point queries
+        all points with itself excluded.  Otherwise queries float64[nq, dim], and self_offset (None or -1: nothing excluded) says that
+        query i is reference i + self_offset and is left out of its own row.  The queries are cut into blocks of at most max_out // k
+        rows (default and most NATAC_KNN_MAX_OUT); the result does not depend on the cut.  with_arm_queries: also int64[2], the queries
+        the wave and the lds arm took; with_kernel_ms: also the kernels' device time.  A refused operand raises before anything is
+        returned."""
+        x = _f64(points)
+        if x.ndim != 2:
+            raise ValueError("points must be a 2-d array [nr, dim]")
+        if queries is None:
+            q, so = x, 0
+        else:
+            q, so = _f64(queries), -1 if self_offset is None else int(self_offset)
+            if q.ndim != 2 or q.shape[1] != x.shape[1]:
+                raise ValueError("queries must be a 2-d array with the columns of points")
+        k = int(k)
+        if not 1 <= k <= L.KNN_MAX_K:       # before it sizes the outputs
+            raise ValueError("k must be in [1, %d] (got %d)" % (L.KNN_MAX_K, k))
+        max_out = L.KNN_MAX_OUT if max_out is None else min(int(max_out), L.KNN_MAX_OUT)
+        block = max(max_out // k, 1)
+        nq, nr, dim = q.shape[0], x.shape[0], x.shape[1]
+        idx, d2 = np.empty((nq, k), dtype=np.int32), np.empty((nq, k), dtype=np.float64)
+        arms, arms_all = np.zeros(2, dtype=np.int64), np.zeros(2, dtype=np.int64)
+        ms, ms_all = C.c_double(0), 0.0
+        for lo in range(0, max(nq, 1), block):
+            n = min(block, nq - lo)
+            qb, ib, db = q[lo:lo + n], idx[lo:lo + n], d2[lo:lo + n]
+            L.check(self._lib.natac_knn(self._h, n, nr, dim, _ptr(qb), _ptr(x), so + lo if so >= 0 else -1, k, _ptr(ib), _ptr(db), _ptr(arms),
+                                        C.byref(ms)))
+            arms_all += arms
+            ms_all += ms.value
+        res = (idx, d2)
+        if with_arm_queries:
+            res += (arms_all,)
         return res + (ms_all,) if with_kernel_ms else res
 
     def sparse_lsi(self, indptr, indices, data, n_cells, row_weight, col_scale, r, n_iter, q0, scale=1e4, transform="log", binarize=False,

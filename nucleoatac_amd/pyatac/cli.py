@@ -1,4 +1,4 @@
-"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | cluster | deviations | markers | coaccess | genescores | peaks | motifs` command line with the reference's flag names and defaults
+"""`pyatac pwm | sizes | ins | cov | bias | counts | nucleotide | signal | cells | cellqc | split | cellcounts | doublets | cluster | deviations | markers | coaccess | genescores | peaks | motifs` command line with the reference's flag names and defaults
 (pyatac/cli.py:90-193, 270-352).  `pwm` and `sizes` make the --pwm and --sizes inputs of `nucleoatac occ` / `nuc`; `ins` and `cov`
 write the per-base insertion and fragment-centre coverage tracks, `bias` the per-base log Tn5 preference of a FASTA under a PWM;
 `counts` gives the fragment count of every BED window, `nucleotide` the mono- or dinucleotide frequency around a set of sites
@@ -16,7 +16,10 @@ on those.  `peaks`, this package's own as well, makes the peak set the other com
 two local rates, as a narrowPeak file and, with --fixed_width, as disjoint windows of one width; run per cell group behind `split`, it is
 the last link before `nucleoatac run`.  `cluster`, this package's own too, makes the group column `split --groups` wants from the matrix
 `cellcounts` wrote: TF-IDF weighting, a truncated SVD of the weighted matrix on the GPU (LSI), the depth-tracking components removed and
-k-means with a given number of clusters.  The single-cell chain is `cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` ->
+k-means with a given number of clusters.  `doublets`, this package's own as well, comes before it: it simulates doublets by adding two
+cells' counts, puts them into the same LSI space, scores every cell by the share of simulated doublets among its nearest neighbours (an
+exact search on the GPU) and writes the table of the cells to keep, which `cellcounts --cells` takes unchanged.  The single-cell chain is
+`cells` -> `cellqc` -> `peaks` (whole file) -> `cellcounts` -> `doublets` -> `cellcounts --cells` ->
 `cluster` -> `deviations` / `markers` / `coaccess` / `genescores` / `split` -> `peaks` per group -> `nucleoatac run`, with no outside tool.  `motifs`, this package's own as well, makes the
 sites that `signal --bed`, `nucleotide --bed` and `cellqc --tss` aggregate around: it scans the FASTA, or the windows of a BED file, for
 the motifs of a MEME or JASPAR file on the GPU and writes the sites and the window-by-motif match matrix.  `deviations`, this package's
@@ -223,6 +226,31 @@ def add_cluster_parser(sub):
     p.add_argument("--out", metavar="basename", help="Basename for output. Default is the matrix file's name without .cellcounts and its suffix")
 
 
+def add_doublets_parser(sub):
+    p = sub.add_parser("doublets", help="doublet score per cell: simulated doublets among the nearest neighbours in LSI space")
+    p.add_argument("--counts", metavar="matrix", required=True,
+                   help="BASE.cellcounts.npz or BASE.cellcounts.mtx.gz (with its .barcodes.tsv beside it) as `cellcounts` writes them")
+    p.add_argument("--components", metavar="int", default=30, type=int, help="LSI components kept for the embedding. Default is 30")
+    p.add_argument("--oversample", metavar="int", default=10, type=int,
+                   help="Further columns of the iterated block; components + oversample is at most 64. Default is 10")
+    p.add_argument("--iterations", metavar="int", default=4, type=int, help="Rounds of subspace iteration. Default is 4")
+    p.add_argument("--method", choices=("log", "linear"), default="log", help="log1p(10000 x TF-IDF) (default) or TF-IDF itself")
+    p.add_argument("--binarize", action="store_true", default=False, help="Every count becomes 1; a simulated doublet is the union")
+    p.add_argument("--min_cells", metavar="int", default=1, type=int, help="Windows seen in fewer cells are dropped. Default is 1")
+    p.add_argument("--max_depth_cor", metavar="float", default=0.75, type=float,
+                   help="A component whose correlation with log10 of the cells' totals exceeds this in magnitude is removed. Default is 0.75")
+    p.add_argument("--seed", metavar="int", default=1, type=int,
+                   help="Seed of the block the iteration starts from and of the simulated pairs. Default is 1")
+    p.add_argument("--ratio", metavar="float", default=2.0, type=float, help="Simulated doublets per kept cell, in (0, 8]. Default is 2.0")
+    p.add_argument("--neighbors", metavar="int", default=None, type=int,
+                   help="Neighbours k before the simulated ones are allowed for, in [1, 1024]. Default is round(0.5 sqrt(cells))")
+    p.add_argument("--expected_rate", metavar="float", default=0.06, type=float, help="Expected doublet rate, in (0, 0.5]. Default is 0.06")
+    p.add_argument("--filter_ratio", metavar="float", default=None, type=float,
+                   help="Flag the int(F * cells^2 / 100000) highest-scoring cells, F in [0, 100]. Default is 1.0; excludes --max_score")
+    p.add_argument("--max_score", metavar="float", default=None, type=float, help="Flag the cells that score above this; excludes --filter_ratio")
+    p.add_argument("--out", metavar="basename", help="Basename for output. Default is the matrix file's name without .cellcounts and its suffix")
+
+
 def add_coaccess_parser(sub):
     p = sub.add_parser("coaccess", help="the pairs of nearby windows that open and close together, by a correlation over the cells")
     p.add_argument("--counts", metavar="matrix", required=True,
@@ -361,6 +389,7 @@ def pyatac_parser():
     add_cellqc_parser(sub)
     add_split_parser(sub)
     add_cellcounts_parser(sub)
+    add_doublets_parser(sub)
     add_cluster_parser(sub)
     add_deviations_parser(sub)
     add_markers_parser(sub)
@@ -475,6 +504,16 @@ def pyatac_main(args):
             get_cellcounts(args)
         except (CountsError, BedColumnError, CellGroupError, NatacError) as e:
             sys.stderr.write("pyatac cellcounts: %s\n" % e)
+            return 1
+    elif args.call == "doublets":
+        from .._lib import NatacError
+        from .get_cluster import ClusterError
+        from .get_doublets import get_doublets
+        print("---------Scoring the cells of the count matrix for doublets----------------------------")
+        try:
+            get_doublets(args)
+        except (ClusterError, NatacError) as e:
+            sys.stderr.write("pyatac doublets: %s\n" % e)
             return 1
     elif args.call == "cluster":
         from .._lib import NatacError
